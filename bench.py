@@ -14,9 +14,15 @@ over one batch of synthetic input, per GPU:
       -> row gather by ancestor [N > 1: all-to-all-v of the rows whose output slot another rank owns]
 
 Prints ONE JSON line (rank 0).  value = K_total * steps / wall time of the timed region (max over
-ranks), inputs resident in HBM.  roofline.achieved = algorithmic bytes of the propagate+reweight
+ranks), inputs resident in HBM; the timed region is exactly --steps steps after --warmup untimed ones,
+and ms_per_step = its wall time / steps.  A plain run does only that (set up, warm up, time, print);
+--dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy.
+
+--full adds everything else: roofline.achieved = algorithmic bytes of the propagate+reweight
 kernel (4*D + 12 = 76 B per particle, 0 read) / its average duration measured with
-HIP events on the launch stream inside the timed region.
+HIP events on the launch stream inside the timed region, kernel figures from runs of their own, CPU
+baselines, the closed-form log-ML comparison, the short ssm / hmc runs (other_configs) and the full
+record written to --extra-file.
 
 Other §8 rows can be measured with --workload ssm (config 3: bootstrap filter, T = 256, K = 2^18) and
 --workload hmc (config 5: 2^16 chains x L = 1000 leapfrog steps); they print the same JSON shape.
@@ -40,7 +46,8 @@ import torch.distributed as dist
 K_PER_GPU = 1 << 20
 D, C = 16, 8
 ALGO_BYTES_PER_PARTICLE = 4 * D + 12          # z + x[D] + score + log_weight, written once; nothing read
-MIN_TIMED_S = 0.05                             # the timed region is repeated until this much has been timed (median reported)
+DUMP_MAX_COLUMNS = 1 << 18                     # --dump-outputs: per-particle arrays beyond this many columns are sampled (seeded)
+DUMP_MAX_BYTES = 64 << 20
 HBM_PEAK_GBS = 8000.0                          # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable)
 FP32_PEAK_TFLOPS = 157.3                       # vector / f32-MFMA peak
 
@@ -48,6 +55,36 @@ FP32_PEAK_TFLOPS = 157.3                       # vector / f32-MFMA peak
 def golden(name):
     with open(os.path.join(ROOT, "tests", "golden", "closed_form.json")) as f:
         return json.load(f)[name]
+
+
+# ---------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path's last step returned to its caller, as DIR/<name>.npy (float32 / float64)
+# ---------------------------------------------------------------------------------------------
+def host_outputs(arrays: dict, K: int) -> dict:
+    """device tensors -> host arrays (float32 stays float32, any other type becomes float64).  An array whose last dimension is K
+    (one entry per particle or chain) keeps all K columns up to DUMP_MAX_COLUMNS, beyond that the same fixed, seeded sample of
+    DUMP_MAX_COLUMNS columns (in ascending order) for every such array."""
+    idx = None
+    if K > DUMP_MAX_COLUMNS:
+        idx = np.sort(np.random.default_rng(0).choice(K, DUMP_MAX_COLUMNS, replace=False))
+    out = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        if idx is not None and a.ndim >= 1 and a.shape[-1] == K:
+            a = a[..., idx]
+        out[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+    return out
+
+
+def write_outputs(path: str, arrays: dict) -> None:
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -205,7 +242,8 @@ def run_gmm(args, rank, world, dev):
     anc = torch.empty(K, dtype=torch.int32, device=dev)
     lse_rec = torch.empty(4, dtype=torch.float32, device=dev)
     n_part = kernels.run_partials_count(prog, K, off)
-    n_samp = max(1, min(args.event_samples, args.steps))
+    # (--full only: a plain run times the steps and nothing inside them)
+    n_samp = max(1, min(args.event_samples, args.steps)) if args.full else 0
     sample_at = {int(round(j * (args.steps - 1) / max(n_samp - 1, 1))): j for j in range(n_samp)}
     # per sampled step: HIP events attached to the kernel's own dispatch (gjx_run_opts.start_event / stop_event: begin / end of the
     # kernel, what rocprofv3's kernel trace reports) on even samples, and a plain event pair recorded around the call
@@ -309,17 +347,37 @@ def run_gmm(args, rank, world, dev):
             return lse_rec
         # collective transport: 8-byte all-gather of per-rank {max, sumexp} (reduced in the prefix-sum prologue), 8-byte
         # all-gather of weight totals, device-side plan, local gather + all-to-all-v of the surplus children
-        _, lse_g = resampler.step(out["choices"], out["logw"], out["lse"], u)
+        coll["rows"], lse_g = resampler.step(out["choices"], out["logw"], out["lse"], u)
         return lse_g
+
+    coll = {}
+
+    def last_outputs(lse):
+        """what the last step left for its caller (this rank's particles): propagated particles, scores, log weights, the
+        resampled particles and the LSE record the step returned"""
+        if fused_step:
+            src = dict(choices=step_out["choices"], score=step_out["score"], logw=step_out["logw"], resampled=step_out["rows"],
+                       ancestors=step_out["ancestors"], lse=lse)
+        elif peer is not None:
+            po = peer_out[(peer_calls[0] - 1) & 1]
+            src = dict(choices=po["choices"], score=out["score"], logw=po["logw"], resampled=rows, lse=lse)
+        elif resampler is not None:
+            src = dict(choices=out["choices"], score=out["score"], logw=out["logw"], resampled=coll["rows"], lse=lse)
+        else:
+            src = dict(choices=out["choices"], score=out["score"], logw=out["logw"], resampled=rows, lse=lse)
+            if not two_launch:
+                src["ancestors"] = anc
+        return host_outputs(src, K)
 
     # One-off costs that belong to neither W nor the timed region: RCCL sets up channels lazily per collective, and
     # the HIP runtime grows its signal / kernel-argument pools the first time the launch queue gets deep — a single
     # 35-45 ms host stall inside one launch call (seen with a per-call timer around the launches), 2-3x the whole default timed region.  A deep
-    # un-synchronised burst here triggers it before the clock starts.
-    for i in range(300):
+    # un-synchronised burst here triggers it before the clock starts (at least as deep as the timed region).
+    for i in range(max(300, args.steps)):
         step(i, False)
     torch.cuda.synchronize()
     dt, lse = timed_loop(args, world, dev, step)
+    outputs = last_outputs(lse) if (args.dump_outputs and rank == 0) else None
     exch = dict(transport="none")
     status_word = None
     if peer is not None:
@@ -338,6 +396,23 @@ def run_gmm(args, rank, world, dev):
         exch = _exchange_record(exch, dev, status_word)      # (collective: every rank's view travels to rank 0)
     if rank != 0:
         return None
+    lml = float(lse[3])
+    res = dict(
+        metric="particle_steps_per_sec", value=K_total * args.steps / dt, unit="particle-steps/s",
+        n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=dt / args.steps * 1e3,
+        higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
+        config=dict(workload="gmm_c8_d16 ImportanceK: propagate+reweight+LSE, systematic resample, gather "
+                             "(BASELINE.json configs[1])",
+                    k_particles_per_gpu=K, k_particles_total=K_total, rng_stream="flat", sharding=f"particles x{world}",
+                    exchange=exch["transport"], exchange_stats=exch),
+        log_ml=lml, timed_total_ms=dt * 1e3,
+        timing_note="exactly `steps` steps enqueued back to back between one pair of barrier + synchronize (after `warmup` untimed "
+                    "steps); ms_per_step = that bracket / steps",
+    )
+    if outputs is not None:
+        res["_outputs"] = outputs
+    if not args.full:
+        return res
     disp = [timers[j].elapsed_us() for j in range(n_samp) if j % 2 == 0]
     brk = [ev[j][0].elapsed_time(ev[j][1]) * 1e3 for j in range(n_samp) if j % 2 == 1]
     kern_ms = sum(disp) / len(disp) * 1e-3
@@ -351,7 +426,6 @@ def run_gmm(args, rank, world, dev):
     kernel_name = "gjx::k_run_gmm_flat<16,4,256,STEP>" if fused_step else "gjx::k_run_gmm_flat<16,4,256>"
     achieved = algo_bytes / (kern_ms * 1e-3) / 1e9
     exact = golden("gmm_c8_d16_seed0")
-    lml = float(lse[3])
     # HBM bytes per launch from the PMC counters are NOT measured in this run (counters need their own rocprofv3 passes):
     # `traffic` stays null and the figure of the committed counter run is reported beside it, labelled as such
     traffic_prof = None
@@ -366,14 +440,7 @@ def run_gmm(args, rank, world, dev):
                 traffic_prof = dict(bytes_per_launch=v, file="profiles/%s_pmc_traffic.json" % tag,
                                     note="rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, committed; not measured in this run")
                 break
-    res = dict(
-        metric="particle_steps_per_sec", value=K_total * args.steps / dt, unit="particle-steps/s",
-        n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=dt / args.steps * 1e3,
-        higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
-        config=dict(workload="gmm_c8_d16 ImportanceK: propagate+reweight+LSE, systematic resample, gather "
-                             "(BASELINE.json configs[1])",
-                    k_particles_per_gpu=K, k_particles_total=K_total, rng_stream="flat", sharding=f"particles x{world}",
-                    exchange=exch["transport"], exchange_stats=exch),
+    res.update(
         roofline=dict(bound="hbm", kernel=kernel_name, achieved=achieved, peak=HBM_PEAK_GBS,
                       unit="GB/s", frac=achieved / HBM_PEAK_GBS, traffic=None, traffic_from_profiles=traffic_prof,
                       stream="flat (the build's own stream layout and samplers, not the reference's key structure: "
@@ -385,12 +452,7 @@ def run_gmm(args, rank, world, dev):
                       note=("the whole importance step is this one launch: propagate+reweight (76 B/particle), resampling (8), "
                             "gather of 17 rows (136); " if fused_step else "") +
                            "the propagate+reweight phase is bound by integer VALU issue (Threefry-2x32-20), see DESIGN.md §5; frac is vs HBM"),
-        log_ml=lml, log_ml_exact=exact, log_ml_rel_err=abs(lml - exact) / abs(exact),
-        timed_regions=len(timed_loop.last_regions), timed_units_per_region=timed_loop.last_reps,
-        timed_total_ms=sum(timed_loop.last_regions) * timed_loop.last_reps * 1e3,
-        timing_note="one unit = exactly `steps` steps; `timed_units_per_region` units are enqueued back to back between one pair "
-                    "of barrier + synchronize and the bracket is divided by that count; median of `timed_regions` brackets",
-        timed_region_ms_min_median_max=[min(timed_loop.last_regions) * 1e3, dt * 1e3, max(timed_loop.last_regions) * 1e3],
+        log_ml_exact=exact, log_ml_rel_err=abs(lml - exact) / abs(exact),
     )
     # the same kernel launched back to back with itself (a train of VALU-bound launches runs at a lower shader clock than
     # the kernel does behind the memory-bound gather inside the step: DESIGN.md section 7)
@@ -476,9 +538,13 @@ def run_ssm(args, rank, world, dev):
         step(i, False)
     torch.cuda.synchronize()
     dt, lml = timed_loop(args, world, dev, step)
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        o = last["out"]
+        outputs = host_outputs(dict(log_ml=o["log_ml"], increments=o.get("increments"), x=o.get("x"), logw=o.get("logw")), K_local)
     lml = float(lml)
     other = None
-    if world == 1:                           # the other weight scheme beside it, same keys, untimed warm-up then 3 runs
+    if world == 1 and args.full:             # the other weight scheme beside it, same keys, untimed warm-up then 3 runs
         o_name = "global_max" if scheme == "tile_scaled" else "tile_scaled"
         bo = BootstrapFilter(LinearGaussianSSM(s["A"], s["q"], s["r"]), K, weights=o_name)
         for i in range(3):
@@ -503,7 +569,6 @@ def run_ssm(args, rank, world, dev):
         exch = _exchange_record(exch, dev, status_word)      # (collective: every rank's view travels to rank 0)
     if rank != 0:
         return None
-    exact = golden("ssm_dx8_T256_seed0")
     per_step_us = dt / args.steps / T * 1e6
     algo = (8 * 8 + 24) * K_local            # 8*d_x + 16..24 B per particle-step
     res = dict(
@@ -527,8 +592,14 @@ def run_ssm(args, rank, world, dev):
                       algorithmic_bytes_per_launch=algo,
                       note="latency-bound at K=2^18: grid rendezvous (~3.5 us each) + the ancestor search + the propagate phase per "
                            "step, no kernel boundary (phase timeline: profiles/, DESIGN.md section 5); kernel_us = wall time per filter step"),
-        log_ml=float(lml), log_ml_exact=exact, log_ml_rel_err=abs(float(lml) - exact) / abs(exact),
+        log_ml=float(lml),
     )
+    if outputs is not None:
+        res["_outputs"] = outputs
+    if not args.full:
+        return res
+    exact = golden("ssm_dx8_T256_seed0")
+    res.update(log_ml_exact=exact, log_ml_rel_err=abs(float(lml) - exact) / abs(exact))
     # rtol 1e-4 is NOT a single-run property at K = 2^18: an ideal float64 bootstrap filter of this size has an rms relative error of
     # 7.0e-5 over its seeds (tests/golden/ssm_pf_float64.json, make_ssm_pf_float64.py).  The honest single-run figure is the z-score of
     # this run's log-ML against that filter's single-run distribution (|z| < 3 expected; the tests hold the 32-seed rms to its rms).
@@ -557,7 +628,8 @@ def run_hmc(args, rank, world, dev):
     assert engine in (2, 3), "fused logistic-regression HMC kernel not selected"
     ch0 = torch.as_tensor((np.random.default_rng(rank).standard_normal((P + 1, n)) * 0.1).astype(np.float32), device=dev)
     state = {"ch": ch0.clone(), "ws": None}
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 8))]
+    # (--full only: a plain run times the steps and nothing inside them)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 8) if args.full else 0)]
 
     def step(i, timed):
         j = i if (timed and i < len(ev)) else None
@@ -567,27 +639,36 @@ def run_hmc(args, rank, world, dev):
         if j is not None:
             ev[j][1].record()
         state["ws"] = out["_ws"]
+        state["out"] = out
         return out["accepted"]
 
     dt, acc = timed_loop(args, world, dev, step)
     if rank != 0:
         return None
-    kern_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
-    flops = n * L * (2 * 2 * N * P + 10 * N)            # X beta and X^T r (2 flop per FMA) + sigmoid
-    tf = flops / (kern_ms * 1e-3) / 1e12
+    o = state["out"]
+    outputs = host_outputs(dict(choices=o["choices"], score=o["score"], alpha=o["alpha"], accepted=o["accepted"]), n) if args.dump_outputs else None
     res = dict(
         metric="chain_leapfrogs_per_sec", value=n * world * L * args.steps / dt, unit="chain-leapfrogs/s", n_gpus=world,
         steps=args.steps, warmup=args.warmup, ms_per_step=dt / args.steps * 1e3, higher_is_better=True, scaling="weak",
         vs_baseline=None, dtype="f32", data="synthetic",
         config=dict(workload="hier_logreg_N1024_P16 HMC with fused MH accept (BASELINE.json configs[4]); one bench step = "
                              f"one move of L={L} leapfrog steps", chains_per_gpu=n, leapfrog=L, eps=0.01, rng_stream="flat"),
+        accept_rate=float(acc.mean()),
+    )
+    if outputs is not None:
+        res["_outputs"] = outputs
+    if not args.full:
+        return res
+    kern_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
+    flops = n * L * (2 * 2 * N * P + 10 * N)            # X beta and X^T r (2 flop per FMA) + sigmoid
+    tf = flops / (kern_ms * 1e-3) / 1e12
+    res.update(
         roofline=dict(bound="mfma", kernel=("gjx::k_hmc_logreg_mfma2<FLAT,false,1024>" if engine == 3 else "gjx::k_hmc_logreg<FLAT,16,false>"), achieved=tf, peak=FP32_PEAK_TFLOPS, unit="TFLOP/s",
                       frac=tf / FP32_PEAK_TFLOPS, traffic=None, kernel_us=kern_ms * 1e3,
                       note="both contractions on v_mfma_f32_16x16x4_f32 (exact f32).  The f32 MFMA occupies the SIMD's own f32 lanes: vector "
                            "instructions beside it cost their full issue time on top of its 32 cycles (profiles/r03_mfma_valu_overlap_microbench.txt), "
                            "so per 32 observations a wave needs 32 MFMAs (1024 cycles) + 48 sigmoid instructions (~330) + ~80 of LDS reads and loop: "
                            "MFMA busy 0.72 by SQ_VALU_MFMA_BUSY_CYCLES; ~0 HBM bytes"),
-        accept_rate=float(acc.mean()),
     )
     if not args.no_cpu_baseline and world == 1:
         res["cpu_baseline"] = cpu_baseline_hmc(prog, P, L)
@@ -1759,8 +1840,9 @@ def headline_record(res: dict, extra_path=None) -> dict:
     if isinstance(ex, dict) and ex.get("transport", "none") != "none":
         out["config"]["exchange_summary"] = _pick(ex, ("transport", "ranks", "status", "transports_agree", "any_status_bit"))
     rf = res.get("roofline", {})
-    out["roofline"] = {k: _short(v, 100) for k, v in _pick(rf, ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "kernel_us",
-                                                                "algorithmic_bytes_per_launch", "launches_per_step")).items()}
+    if rf:
+        out["roofline"] = {k: _short(v, 100) for k, v in _pick(rf, ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "kernel_us",
+                                                                    "algorithmic_bytes_per_launch", "launches_per_step")).items()}
     tp = rf.get("traffic_from_profiles")
     if isinstance(tp, dict):
         out["roofline"]["traffic_from_profiles"] = _pick(tp, ("bytes_per_launch", "file"))
@@ -1837,44 +1919,28 @@ def respawn(n: int) -> None:
 
 
 def timed_loop(args, world, dev, step):
+    """args.warmup untimed steps, then args.steps timed steps -> (seconds of the timed steps, max over ranks; what the last step returned)"""
     def barrier():
         if dist.is_initialized():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def region(reps):
-        """reps x args.steps steps enqueued back to back between ONE pair of barriers -> seconds per args.steps steps (max over ranks)"""
-        last = None
-        barrier()
-        t0 = time.perf_counter()
-        for r in range(reps):
-            for i in range(args.steps):
-                last = step(i, r == 0)              # the kernel's HIP-event samples ride in the first unit of every bracket (events are not free)
-        barrier()
-        dt = time.perf_counter() - t0
-        if dist.is_initialized():
-            t = torch.tensor([dt], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt = float(t.item())
-        return dt / reps, last
-
     for i in range(args.warmup):
         step(i % max(args.steps, 1), False)
-    # The timed unit is EXACTLY args.steps steps.  A short unit (20 steps = 1.2 ms) between two host barriers is mostly barrier
-    # and queue-drain edge, so `reps` units are enqueued back to back between ONE pair of barriers (reps sized from a first,
-    # calibrating unit so that a bracket spans >= MIN_TIMED_S) and the bracket's time is divided by reps; that bracket is
-    # repeated and the MEDIAN reported.  Every rank takes the same decisions (they see the same max-reduced times).
-    est, last = region(1)
-    reps = max(1, min(4096, int(math.ceil(MIN_TIMED_S / max(est, 1e-7)))))
-    dts = []
-    for _ in range(5 if reps > 1 else 1):
-        dt, last = region(reps)
-        dts.append(dt)
-    if reps == 1:
-        dts.append(est)
-    timed_loop.last_regions = dts
-    timed_loop.last_reps = reps
-    return sorted(dts)[len(dts) // 2], last
+    # The timed region is EXACTLY args.steps steps, enqueued back to back between ONE pair of barriers + synchronize; the
+    # caller picks args.steps large enough that the barrier and queue-drain edges are small against the region.
+    last = None
+    barrier()
+    t0 = time.perf_counter()
+    for i in range(args.steps):
+        last = step(i, True)
+    barrier()
+    dt = time.perf_counter() - t0
+    if dist.is_initialized():
+        t = torch.tensor([dt], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    return dt, last
 
 
 def main():
@@ -1891,12 +1957,19 @@ def main():
                     help="ssm on one GPU: fixed-point scheme of the filter's systematic resampler (include/gjx.h)")
     ap.add_argument("--ssm-k-total", type=int, default=0, help="ssm: total number of particles (overrides the config-3/4 sizes)")
     ap.add_argument("--api", action="store_true", help="gmm on one GPU: print only the API-level measurement (extra.api)")
-    ap.add_argument("--no-extra", action="store_true", help="gmm on one GPU: skip the short ssm / hmc runs summarised under other_configs")
+    ap.add_argument("--no-extra", action="store_true", help="gmm on one GPU with --full: skip the short ssm / hmc runs summarised under other_configs")
     ap.add_argument("--extra", action="store_true",
-                    help="gmm on one GPU: also run the round's other measurements (generated kernels, generic filter, plates, HMC engines, "
+                    help="gmm on one GPU (implies --full): also run the round's other measurements (generated kernels, generic filter, plates, HMC engines, "
                          "config-4 dry run, API step); they are written to the side file (--extra-file), not to the line")
     ap.add_argument("--extra-file", default=os.environ.get("GJX_BENCH_EXTRA", os.path.join(ROOT, "bench_extra.json")),
-                    help="where the full record (everything measured, incl. long notes) is written; the stdout line stays compact")
+                    help="with --full: where the full record (everything measured, incl. long notes) is written; the stdout line stays compact")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: kernel / roofline figures, CPU baselines, the "
+                         "closed-form log-ML comparison, the short ssm / hmc runs of gmm on one GPU (other_configs), the full record "
+                         "written to --extra-file.  A plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB; per-particle arrays of more than 2^18 particles are a fixed, seeded sample of columns)")
     ap.add_argument("--event-samples", type=int, default=16,
                     help="number of timed steps whose propagate+reweight kernel is bracketed with HIP events "
                          "(timing events are not free on ROCm — hundreds of live ones slow every launch — so the "
@@ -1905,6 +1978,9 @@ def main():
     dflt = {"gmm": (200, 20), "ssm": (10, 2), "hmc": (5, 1)}[args.workload]
     args.steps = dflt[0] if args.steps is None else args.steps
     args.warmup = dflt[1] if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    args.full = args.full or args.extra
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         respawn(args.gpus)                   # plain `python bench.py --gpus N`: become N ranks, one per GPU
@@ -1920,12 +1996,13 @@ def main():
         print(json.dumps(dict(metric="particle_steps_per_sec_api", **run_api(dev, args.k_per_gpu))))
         return
     res = {"gmm": run_gmm, "ssm": run_ssm, "hmc": run_hmc}[args.workload](args, rank, world, dev)
-    if args.workload == "gmm" and world == 1 and res is not None and not args.no_extra:
+    outputs = res.pop("_outputs", None) if res is not None else None
+    if args.workload == "gmm" and world == 1 and res is not None and args.full and not args.no_extra:
         # the other single-GPU rows of BASELINE.json, short runs: their summaries ride in the line under other_configs
         extra = {}
         for name, fn, st in (("ssm", run_ssm, 3), ("hmc", run_hmc, 2)):
             a2 = argparse.Namespace(**vars(args))
-            a2.workload, a2.steps, a2.warmup, a2.no_cpu_baseline = name, st, 1, True
+            a2.workload, a2.steps, a2.warmup, a2.no_cpu_baseline, a2.dump_outputs = name, st, 1, True, None
             r2 = fn(a2, rank, world, dev)
             extra[name] = {k: r2[k] for k in ("metric", "value", "unit", "steps", "ms_per_step", "config", "roofline") if k in r2}
             for k in ("log_ml_rel_err", "log_ml_z", "accept_rate", "other_weight_scheme"):
@@ -1948,7 +2025,9 @@ def main():
     if rank == 0 and res is not None:
         from genjax_amd import kernels
         res["jit"] = kernels.jit_stats()
-        path = write_full_record(res, args)
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
+        path = write_full_record(res, args) if args.full else None
         print(headline_line(res, path))            # the LAST stdout line: compact, what the driver parses
     if dist.is_initialized():
         dist.destroy_process_group()

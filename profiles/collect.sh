@@ -7,14 +7,14 @@ cd $R
 for w in $WL; do
   # the compact line the driver parses -> <tag>_bench_<w>.json; the full record (incl. --extra's measurements) -> <tag>_bench_<w>_full.json
   xa=; [ $w = gmm ] && xa=--extra
-  python bench.py --workload $w $xa --extra-file $OUT/${TAG}_bench_${w}_full.json 2>/dev/null | tail -1 > $OUT/${TAG}_bench_$w.json
+  python bench.py --full --workload $w $xa --extra-file $OUT/${TAG}_bench_${w}_full.json 2>/dev/null | tail -1 > $OUT/${TAG}_bench_$w.json
 done
 cd /tmp; export TMPDIR=/tmp
 for w in $WL; do
   # gmm: the headline command WITHOUT the extra workloads (they launch the same kernels at other sizes, which would mix into
   # the per-kernel averages); the extras get their own trace below
   st=100; xf=--no-extra; [ $w != gmm ] && st=3 && xf=
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$w -o $w -- python $R/bench.py --workload $w --no-cpu-baseline $xf --steps $st --warmup 1 > $OUT/prof_$w.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$w -o $w -- python $R/bench.py --full --workload $w --no-cpu-baseline $xf --steps $st --warmup 1 > $OUT/prof_$w.log 2>&1
   cp $(find $OUT/prof_$w -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_${w}_kernel_stats.csv
 done
 if echo $WL | grep -q gmm; then

@@ -61,3 +61,32 @@ def test_headline_line_survives_oversized_optional_blocks():
     line = bench.headline_line(res, None)
     rec = json.loads(line)
     assert len(line) < bench.HEADLINE_MAX_BYTES and rec["roofline"]["frac"] == 0.435 and rec["cpu_baseline"]["value"] == 1.05e7
+
+
+def test_dump_outputs_keep_small_arrays_whole_and_sample_large_ones(tmp_path):
+    """--dump-outputs: float32 stays float32, other types become float64; per-particle arrays beyond DUMP_MAX_COLUMNS columns are the
+    same fixed, seeded, ascending sample of columns for every array and every run."""
+    import numpy as np
+    import pytest
+    import torch
+    import bench
+    K = bench.DUMP_MAX_COLUMNS + 12345
+    cols = torch.arange(K, dtype=torch.float32)
+    arrays = dict(choices=torch.stack([cols, cols + 0.5]), ancestors=torch.arange(K, dtype=torch.int32), lse=torch.tensor([1.0, 2.0, 3.0, 4.0]),
+                  log_ml=torch.tensor(-43.8, dtype=torch.float64), skipped=None)
+    a, b = bench.host_outputs(arrays, K), bench.host_outputs(arrays, K)
+    assert sorted(a) == ["ancestors", "choices", "log_ml", "lse"]
+    assert a["choices"].dtype == np.float32 and a["ancestors"].dtype == np.float64 and a["log_ml"].dtype == np.float64
+    assert a["choices"].shape == (2, bench.DUMP_MAX_COLUMNS) and a["lse"].shape == (4,)
+    idx = a["ancestors"].astype(np.int64)
+    assert (np.diff(idx) > 0).all() and idx[-1] < K and np.array_equal(a["choices"][0], idx.astype(np.float32))
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    small = bench.host_outputs(dict(x=torch.ones((3, 1000))), 1000)
+    assert small["x"].shape == (3, 1000)
+    bench.write_outputs(str(tmp_path / "out"), a)
+    for k in a:
+        got = np.load(tmp_path / "out" / (k + ".npy"))
+        assert got.dtype == a[k].dtype and np.array_equal(got, a[k])
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), dict(x=np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)))
+    assert not (tmp_path / "big").exists()

@@ -121,11 +121,11 @@ def test_rccl_two_ranks_exchange_equals_unsharded(spread, method):
 
 
 def _run_bench(extra_args, env_extra=None, timeout=900):
-    """-> the compact line bench.py prints LAST (what the driver parses: < 4 KB, parseable, roofline inside), with the full record it
-    points to (the side file) under "_full" """
+    """-> the compact line `bench.py --full` prints LAST (what the driver parses: < 4 KB, parseable, roofline inside), with the full
+    record it points to (the side file) under "_full" """
     import tempfile
     side = tempfile.NamedTemporaryFile(suffix=".json", delete=False).name
-    extra_args = list(extra_args) + ["--extra-file", side]
+    extra_args = ["--full"] + list(extra_args) + ["--extra-file", side]
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
