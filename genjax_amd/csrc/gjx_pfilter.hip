@@ -1,5 +1,5 @@
-// gjx_pfilter.hip — host side of k_pf_persistent (gjx_pfilter.inl): grid / tiles-per-block plan, the step keys of a
-// filter run, and the single-GPU launch used by gjx_ssm_filter_scheme for particle counts beyond one slot per lane.
+// gjx_pfilter.hip — host side of k_pf_persistent (gjx_pfilter.inl): grid / tiles-per-block plan and the step keys of a
+// filter run (the single-GPU launch is in gjx_ssm.hip, the sharded one in gjx_peer.hip).
 #include <math.h>
 #include <string.h>
 
@@ -68,16 +68,8 @@ int upload_words(void* dst_dev, const void* src_host, size_t n_words, hipStream_
 }
 
 void host_threefry2x32(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t out[2]) {
-  static const int R[8] = {13, 15, 26, 6, 17, 29, 16, 24};
-  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
-  uint32_t x0 = c0 + ks[0], x1 = c1 + ks[1];
-  for (int g = 0; g < 5; ++g) {
-    const int* r = (g & 1) ? R + 4 : R;
-    for (int j = 0; j < 4; ++j) { x0 += x1; x1 = (x1 << r[j]) | (x1 >> (32 - r[j])); x1 ^= x0; }
-    x0 += ks[(g + 1) % 3];
-    x1 += ks[(g + 2) % 3] + (uint32_t)(g + 1);
-  }
-  out[0] = x0; out[1] = x1;
+  const uint64_t h = gjx_host_threefry2x32(k0, k1, c0, c1);
+  out[0] = (uint32_t)(h >> 32); out[1] = (uint32_t)h;
 }
 
 // Key discipline of inference/pf.py: k_t = fold_in(k_{t-1}, t) (scan.py:268); (k_prop, k_res) = split(k_t); the comb

@@ -6,10 +6,10 @@
 //   x_t ~ N(A x_{t-1}[ancestor], q^2 I),  log w_t = log N(y_t; H x_t, r^2 I)          (k_ssm_step's arithmetic and streams)
 // with an optional resample-move rejuvenation of the gathered x_{t-1} (requests/rejuvenate.py:70-94 fused into the filter).
 //
-// k_ssm_persistent<TILED> (gjx_ssm.hip) gives every lane ONE slot, so its grid of K / 1024 blocks must be co-resident:
-// K <= 2^18 on a full MI355X.  Here a block owns SPL consecutive quantisation tiles of 1024 slots (a lane: SPL slots, one
-// per tile); the rendezvous cost (one per step) is shared by SPL tiles.  Same scheme (GJX_WEIGHTS_TILE_SCALED,
-// include/gjx.h), same streams, same ancestors.
+// It is the one-launch filter of the tile-scaled scheme (GJX_WEIGHTS_TILE_SCALED, include/gjx.h) at every K: a block owns SPL
+// consecutive quantisation tiles of 1024 slots (a lane: SPL slots, one per tile), SPL = 1 while the grid of K / 1024 blocks
+// is co-resident (K <= 2^18 on a full MI355X); beyond that the rendezvous cost (one per step) is shared by SPL tiles.  Same
+// streams and ancestors as the step-by-step form (k_ssm_step + gjx_resample_indices_tiled).
 #pragma once
 #include "gjx_pfcore.h"
 #include "gjx_pfilter_host.h"

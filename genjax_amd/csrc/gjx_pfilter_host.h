@@ -11,7 +11,7 @@
 namespace gjx {
 
 constexpr int kPfThreads = 1024;
-constexpr int kPfGranulePad = 8;                         // granules one per 64-byte line (as k_ssm_persistent: gjx_ssm.hip kGranulePad)
+constexpr int kPfGranulePad = 8;                         // granules one per 64-byte line (256 blocks storing into shared lines serialise in the L2)
 constexpr int kPfMaxTiles = 4096;                        // quantisation tiles over all ranks (K_total <= 2^22)
 constexpr int kPfPer = kPfMaxTiles / kPfThreads;         // granules / ring entries / ready words a thread looks at
 
@@ -71,7 +71,7 @@ struct PfPlan {
 // Picks the smallest number of tiles per block whose grid is co-resident on the current device (`share` ranks on one
 // device split its capacity: dry runs).  GJX_EUNSUPPORTED when the shape does not fit this kernel.
 int pf_plan(int rng_mode, int dx, int dy, int64_t K_local, int n_ranks, int share, PfPlan* out, bool move = false);
-void host_threefry2x32(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t out[2]);
+void host_threefry2x32(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t out[2]);   // gjx_host_threefry2x32 as two words
 void pf_step_keys(uint32_t key0, uint32_t key1, int T, std::vector<uint32_t>& keys, std::vector<double>& us);
 // the same, and the resampling key k_res of every step ([T][2]): multinomial resampling draws one uniform per slot from it
 void pf_step_keys_res(uint32_t key0, uint32_t key1, int T, std::vector<uint32_t>& keys, std::vector<double>& us, std::vector<uint32_t>& res_keys);

@@ -11,14 +11,6 @@
 #include "gjx_tile.h"
 #include "gjx_pfilter_host.h"
 #include <string.h>
-// pollers per granule in the one-launch filter's rendezvous (tile-scaled scheme, up to 256 blocks) and the stagger between their
-// first looks in units of s_sleep (64 cycles): see k_ssm_persistent
-#ifndef GJX_POLLERS
-#define GJX_POLLERS 4
-#endif
-#ifndef GJX_POLL_STAGGER
-#define GJX_POLL_STAGGER 12
-#endif
 #include <vector>
 
 namespace gjx {
@@ -40,13 +32,14 @@ struct SsmArgs {
   float* lse;
   float log_k_total;
   // resample-move (MOVE kernels): Metropolis-Hastings rejuvenation of the resampled x_{t-1} before it is propagated
-  const float* m_prev;   // [DX][K] E[x_{t-1} | parent] of every particle of step t-1 (NULL at t-1 == 0: prior mean 0)
-  float* m_out;          // [DX][K] A x_{t-1} of the particles of this step
-  const float* y_prev;   // y_{t-1}
-  int n_moves;
-  float move_scale;
-  float* accepted;       // [K] number of accepted moves (or NULL)
-  float* x_moved;        // [DX][K] the moved x_{t-1} each slot was propagated from (or NULL)
+  // (off unless gjx_ssm_step_move sets them)
+  const float* m_prev = nullptr;   // [DX][K] E[x_{t-1} | parent] of every particle of step t-1 (NULL at t-1 == 0: prior mean 0)
+  float* m_out = nullptr;          // [DX][K] A x_{t-1} of the particles of this step
+  const float* y_prev = nullptr;   // y_{t-1}
+  int n_moves = 0;
+  float move_scale = 0.0f;
+  float* accepted = nullptr;       // [K] number of accepted moves (or NULL)
+  float* x_moved = nullptr;        // [DX][K] the moved x_{t-1} each slot was propagated from (or NULL)
 };
 
 template <int RNG, int DX, bool MOVE = false>
@@ -419,27 +412,19 @@ __global__ __launch_bounds__(256) void k_ssm_fused_step(SsmFusedArgs f) {
 
 
 // ------------------------------------------------------------------------------------------------------------
-// The whole filter in ONE launch (steps 1 .. T-1; step 0 is k_ssm_step).  No kernel boundary: a block keeps the
+// The whole filter in ONE launch (steps 1 .. T-1; step 0 is k_ssm_step), global-maximum scheme: the fixed point of
+// gjx_resample_indices (every weight against the exact GLOBAL maximum).  No kernel boundary: a block keeps the
 // log-weights of the slots it produced (they are the particles it scans next), the ancestors are found on the consumer
 // side exactly as in k_ssm_fused_step, and the state and log-weights other blocks read cross the chip through
 // write-through (sc1) stores and sc1 loads, ordered by `s_waitcnt vmcnt(0)` before a block publishes its granule.
 // Ping-pong buffers are safe without further fences: a block can only overwrite the buffer of step t-1 in step t+1,
 // after every block has published its granule of step t+1, i.e. has finished reading it.  The standard-normal draws of
 // step t depend on (key_t, slot) only, not on the ancestor: they are generated while the granules travel.
-//
-// TILED == false — the fixed point of gjx_resample_indices (every weight against the exact GLOBAL maximum): the blocks
-//   meet twice per step, all-gather of the block maxima of log w_{t-1}, then of the tile totals.  Same ancestors, same
-//   streams, same values as the per-step kernels.
-// TILED == true — TILE-SCALED fixed point (GJX_WEIGHTS_TILE_SCALED, include/gjx.h): a tile of kTileQ = 1024 consecutive
-//   particles is quantised against its OWN power-of-two reference 2^e_b, e_b = ceil(max_tile(log w) * log2 e):
-//   q_i = floor(2^29 * exp2(log w_i * log2 e - e_b)), S_b = sum of the tile's q_i.  One granule {e_b, S_b} per block, ONE
-//   rendezvous per step; then E = max e_b, the tile counts G_b = S_b >> (E - e_b) units of 2^(E-29) on the global weight
-//   line, comb thresholds T_j on the prefix of the G_b, and inside the source tile the residual (T_j - P_b) << (E - e_b)
-//   is looked up in the tile's own cumulative q.  A tile loses less than one global unit (< 2^-28 of the largest
-//   weight); nothing else is approximated.  Restated by the test oracle (gjxo_resample_systematic_tiled); the
-//   multi-launch form is gjx_resample_indices_tiled (bit-identical ancestors).
+// The blocks meet twice per step: all-gather of the block maxima of log w_{t-1}, then of the tile totals.  Same
+// ancestors, same streams, same values as the per-step kernels.  (The tile-scaled scheme's one-launch filter is
+// k_pf_persistent, gjx_pfilter.inl.)
 // The LSE record of step t-1 needs the exact float maximum: blocks leave {block max, block sum-exp} in a 3-deep ring
-// (TILED) and block (t-1) mod gridDim finishes the record inside the NEXT step's granule wait, off the critical path.
+// and block (t-1) mod gridDim finishes the record inside the NEXT step's granule wait, off the critical path.
 // ------------------------------------------------------------------------------------------------------------
 struct SsmPersistArgs {
   const float* A; const float* H; const float* ys;   // ys [T][dy]
@@ -454,21 +439,19 @@ struct SsmPersistArgs {
   int32_t* ancestors;              // [K]: of the last step
   unsigned long long* aggA; unsigned long long* aggB;
   float* bsum;                     // [3][gridDim.x] per-block sum of exp(log w - block max) (ring over steps)
-  float* bmax;                     // [3][gridDim.x] per-block max (TILED)
-  unsigned* ready;                 // [gridDim.x] TILED: epoch + t once the block's stores of step t-1 have completed
+  float* bmax;                     // [3][gridDim.x] per-block max
   unsigned* ctrl;
   float log_k;
   unsigned long long* timeline;    // debug (gjx_debug_timeline): 16 realtime stamps per block for step T / 2
 };
 
-// granules of the persistent filter's rendezvous (both weight schemes) sit one per 64-byte line: 256 blocks storing into 32 shared lines serialise in the
-// L2 (11.6 -> 11.0 us per filter step; 128-byte spacing and padding the `ready` words as well measured the same)
+// granules of the persistent filter's rendezvous sit one per 64-byte line: 256 blocks storing into 32 shared lines serialise
+// in the L2 (11.6 -> 11.0 us per filter step; 128-byte spacing measured the same)
 constexpr int kGranulePad = 8;
-template <int RNG, int DX, int THREADS, bool TILED>
+template <int RNG, int DX, int THREADS>
 __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
   // THREADS = 1024 (one block per CU, 256 blocks at K = 2^18) quarters the granules of each all-gather: a rendezvous
   // among 256 blocks measures 3.5 us, among 1024 blocks 5.4 us
-  static_assert(!TILED || THREADS == kTileQ, "the tile-scaled fixed point quantises per 1024-particle tile");
   constexpr int NW = THREADS / 64;               // waves per block
   constexpr int WPT = THREADS / 256;             // waves that re-scan one source tile together (256 particles each)
   constexpr int kChunk = NW / WPT;               // source tiles re-scanned per round (= 4)
@@ -477,7 +460,6 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
   __shared__ float lse_pm[NW], lse_ps[NW];       // finisher: per-wave {max, sumexp} of the ring entries it read
   __shared__ uint64_t wsum[NW];
   __shared__ uint64_t P[kSsmFusedMaxTiles + 1];
-  __shared__ int32_t Eb[TILED ? kSsmFusedMaxTiles : 1];
   __shared__ uint64_t cumL[kChunk * THREADS];
   // model constants in LDS: inside the step loop the compiler must assume the kernel's own stores may alias A, H, ys, us
   // and re-reads them with VECTOR loads every step (16 dependent global_load_dwordx4 for A alone: 1.6 us per step)
@@ -485,11 +467,6 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
   __shared__ double sU;
   __shared__ uint32_t sKey[2][2];
   __shared__ int s_range[2];
-  // TILED, nb <= 256: every granule has kPollers pollers — lanes b, b + 256, ... of the block — whose loads leave a quarter of a
-  // round trip apart; whoever sees the tag first publishes the granule in LDS and sets seen[b], the others leave their loop at their
-  // next look.  A poll is one fabric round trip (~1.7 us): with one poller a block learns of the last granule up to a round trip
-  // after it landed, and that block is then the last to publish in the NEXT step — the skew feeds itself.
-  __shared__ unsigned seen[256];
   for (int e = threadIdx.x; e < DX * DX; e += THREADS) sA[e] = f.A[e];
   if (f.H) for (int e = threadIdx.x; e < f.dy * DX; e += THREADS) sH[e] = f.H[e];
   const unsigned epoch = __hip_atomic_load(&f.ctrl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -503,7 +480,7 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
   const float rr = fast_rcp(f.r);
   const float lconst = -(float)f.dy * (kHalfLog2Pi + fast_log(f.r));
   float lw_own = active ? lw_buf(0)[j] : -INFINITY;               // step 0 ran in the previous launch
-  // finisher of the LSE record of step s from ring slot s % 3 (TILED): all threads read, per-wave partials to LDS
+  // finisher of the LSE record of step s from ring slot s % 3: all threads read, per-wave partials to LDS
   auto lse_ring_partials = [&](int s) {
     const float* rm = f.bmax + (size_t)(s % 3) * nb;
     const float* rs = f.bsum + (size_t)(s % 3) * nb;
@@ -570,24 +547,6 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
     GJX_PSTAMP(0);
     SsmNoiseBits<RNG, DX> nbits;
     float mx = -INFINITY;
-    int eb = kTileDead, Emax = kTileDead;
-    unsigned rdy[kPer];
-    const unsigned rtag = epoch + (unsigned)t;                // `ready` word of this step: never repeats, the epoch advances by 2 T per launch
-    auto check_ready = [&]() {                                // every block's stores of step t-1 have completed (TILED)
-      unsigned budget = kPollBudget;
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) {
-        const int b = threadIdx.x + k * THREADS;
-        if (b >= nb) break;
-        unsigned r = rdy[k];
-        while (r != rtag && budget) {
-          __builtin_amdgcn_s_sleep(1);
-          r = __hip_atomic_load(&f.ready[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          --budget;
-        }
-        if (r != rtag) __hip_atomic_fetch_or(&f.ctrl[2], kStatusPollTimeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    };
     // ---- block maximum of log w_{t-1} ----
     float bm;
     {
@@ -599,230 +558,84 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
 #pragma unroll
       for (int w = 1; w < NW; ++w) bm = fmaxf(bm, fred[w]);
     }
-    if constexpr (!TILED) {
-      // ---- rendezvous A: exact global maximum (nothing else rides on it: published as early as possible) ----
-      const unsigned long long tagA = (unsigned long long)((epoch + 2u * (unsigned)(t - 1)) % 16383u) + 1ull;
-      if (threadIdx.x == 0) grid_publish<kGranulePad>(f.aggA, tagA, (unsigned long long)__float_as_uint(bm));
-      GJX_PSTAMP(1);
-      // while the granules travel: this block's sum of exp(log w - block max), for the LSE record (read after
-      // rendezvous B; ring of 2: a block rewrites its entry only after the finisher published its next granule A),
-      // and the draws of step t
-      {
-        const float e = (active && bm > -INFINITY) ? fast_exp(lw_own - bm) : 0.0f;
-        const float ws = wave_sum_dpp(e);
-        if (lane == 0) fred[NW + wid] = ws;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-          float bs = 0.0f;
-          for (int w = 0; w < NW; ++w) bs += fred[NW + w];
-          const size_t slot = (size_t)((t - 1) % 3) * nb + blockIdx.x;   // ring over steps (complete before granule B goes out)
-          store_agent(&f.bsum[slot], bs);
-          store_agent(&f.bmax[slot], bm);
-        }
-      }
-      stage_step_constants(t);
-      // the record of step t-2, if this block is its finisher, off the critical path: ring loads out before the hashes,
-      // reduced behind them, written by thread 0 behind the next barrier (every block's entry of step t-2 was complete
-      // before its granule B of step t-1, which this block has gathered)
-      const bool fin = t >= 2 && (int)blockIdx.x == (t - 2) % nb;
-      float rpm[kPer], rps[kPer];
-      if (fin) lse_ring_issue(t - 2, rpm, rps);
-      if (t < T) ssm_noise_bits<RNG, DX>(key2{sKey[t & 1][0], sKey[t & 1][1]}, (uint64_t)j, nbits);
-      if (fin) lse_ring_reduce(rpm, rps);
-      grid_gather<kGranulePad>(f.aggA, tagA, f.ctrl, [&](int, unsigned long long v) { mx = fmaxf(mx, __uint_as_float((uint32_t)v)); });
-      mx = wave_max_dpp(mx);     // (no acquire fence: everything read from other blocks goes through agent-scope loads)
+    // ---- rendezvous A: exact global maximum (nothing else rides on it: published as early as possible) ----
+    const unsigned long long tagA = (unsigned long long)((epoch + 2u * (unsigned)(t - 1)) % 16383u) + 1ull;
+    if (threadIdx.x == 0) grid_publish<kGranulePad>(f.aggA, tagA, (unsigned long long)__float_as_uint(bm));
+    GJX_PSTAMP(1);
+    // while the granules travel: this block's sum of exp(log w - block max), for the LSE record (read after
+    // rendezvous B; ring of 2: a block rewrites its entry only after the finisher published its next granule A),
+    // and the draws of step t
+    {
+      const float e = (active && bm > -INFINITY) ? fast_exp(lw_own - bm) : 0.0f;
+      const float ws = wave_sum_dpp(e);
+      if (lane == 0) fred[NW + wid] = ws;
       __syncthreads();
-      if (lane == 0) fred[wid] = mx;
-      __syncthreads();
-      mx = fred[0];
-#pragma unroll
-      for (int w = 1; w < NW; ++w) mx = fmaxf(mx, fred[w]);
-      if (fin && threadIdx.x == 0) lse_ring_write(t - 2);
-      GJX_PSTAMP(2);
-      // ---- rendezvous B: tile totals of the fixed-point weights.  The granule goes out only after this lane's
-      //      write-through (sc1) stores of step t-1 — x, log w, the block sum — have completed; readers use sc1 loads: no
-      //      cache maintenance on either side (MI355X guide G16 form R2; a release fence per wave cost 60 us per step).
-      //      At t == T only the ordering matters (the last LSE record is finished behind it). ----
-      const unsigned long long tagB = (unsigned long long)((epoch + 2u * (unsigned)(t - 1) + 1u) % 16383u) + 1ull;
-      {
-        float xv[1] = {lw_own};
-        const uint64_t qv = (active && t < T) ? weight_q(xv, 0, 1, mx) : 0;
-        const uint64_t wt = wave_total_u64(qv);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) wsum[wid] = wt;     // (wsum was last read in the previous step's re-scan, barriers ago)
-        __syncthreads();
-        if (wid == 0) {
-          static_assert(NW <= 16, "the wave partials fit one DPP row");
-          const uint64_t tt = row_scan_u64(lane < NW ? wsum[lane] : 0);   // lane 15 = sum of lanes 0..15
-          if (lane == 15) __hip_atomic_store(&f.aggB[(size_t)blockIdx.x * kGranulePad], (tagB << 50) | (tt & kAggMask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      GJX_PSTAMP(3);
-      grid_gather<kGranulePad>(f.aggB, tagB, f.ctrl, [&](int b, unsigned long long val) { P[b + 1] = val; });
-    } else {
-      // ---- the ONE rendezvous: {e_b, S_b}.  The granule depends on registers only and goes out at once; that the block's
-      //      sc1 stores of step t-1 (x, log w, its ring entry) have completed is signalled separately (`ready`), behind
-      //      the granule and off the rendezvous' critical path: consumers look at it only right before their first
-      //      foreign read, several microseconds later ----
-      const unsigned long long tag = (unsigned long long)((epoch + (unsigned)t) % 15u) + 1ull;
-      unsigned long long* agg = (t & 1) ? f.aggA : f.aggB;   // alternate: a slow block may still poll step t-1's granules
-      eb = tile_exponent(bm);
-      {
-        const uint64_t qv = (active && t < T) ? tile_q(lw_own, eb) : 0;
-        const float e = (active && bm > -INFINITY) ? fast_exp(lw_own - bm) : 0.0f;
-        const uint64_t wt = wave_total_u64(qv);
-        const float ws = wave_sum_dpp(e);
-        if (lane == 0) { wsum[wid] = wt; fred[NW + wid] = ws; }
-        __syncthreads();
-        if (wid == 0) {                    // the NW wave partials, summed across the first lanes of wave 0
-          static_assert(NW <= 16, "the wave partials fit one DPP row");
-          uint64_t tt = row_scan_u64(lane < NW ? wsum[lane] : 0);       // lane 15 = sum of lanes 0..15
-          float bs = row_sum_to_lane15(lane < NW ? fred[NW + lane] : 0.0f);
-          if (lane == 15) {
-            __hip_atomic_store(&agg[(size_t)blockIdx.x * kGranulePad], tile_granule(tag, eb, tt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const size_t slot = (size_t)((t - 1) % 3) * nb + blockIdx.x;
-            store_agent(&f.bsum[slot], bs);
-            store_agent(&f.bmax[slot], bm);
-          }
-        }
-      }
-      GJX_PSTAMP(1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      constexpr int kPollers = (THREADS == 1024 && GJX_POLLERS > 1) ? GJX_POLLERS : 1;
-      const bool multi = kPollers > 1 && nb <= 256;                      // block-uniform
-      if (multi && threadIdx.x < 256) seen[threadIdx.x] = 0u;           // (the previous step's pollers are barriers behind; this step's start behind the next barrier)
-      // the record of step t-2 if this block is its finisher: its ring entries were complete before the `ready` words
-      // this block checked in step t-1; the loads go out here and are consumed behind the draws
-      const bool fin = t >= 2 && (int)blockIdx.x == (t - 2) % nb;
-      float rpm[kPer], rps[kPer];
-      if (fin) lse_ring_issue(t - 2, rpm, rps);
-      __syncthreads();
-      if (threadIdx.x == 0) __hip_atomic_store(&f.ready[blockIdx.x], rtag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      stage_step_constants(t);
-      // a first look at the granules goes out BEFORE the draws: for the block that is last to publish (the one everybody
-      // else is waiting for, hence the one whose own chain sets the step time) they are all there already, and the load
-      // latency hides behind the draws
-      unsigned long long gv[kPer];
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) {         // (fixed trip count: the loads stay in flight, in registers)
-        const int b = threadIdx.x + k * THREADS;
-        gv[k] = b < nb ? __hip_atomic_load(&agg[(size_t)b * kGranulePad], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-      }
-      // while the granules travel: the draws of step t.  (Looking at the missing granules again between the hashes was
-      // measured and dropped: the polling waves then stall inside the draws, 13.5 -> 14.1 us per step.)
-      if (t < T) ssm_noise_bits<RNG, DX>(key2{sKey[t & 1][0], sKey[t & 1][1]}, (uint64_t)j, nbits);
-      if (fin) lse_ring_reduce(rpm, rps);
-      GJX_PSTAMP(2);
-      if (multi) {
-        unsigned budget = kPollBudget;
-        float em = (float)kTileDead;
-        const int b = threadIdx.x & 255, grp = threadIdx.x >> 8;
-        if (b < nb && grp < kPollers) {
-          unsigned long long v = gv[0];
-          if (grp > 0) {                                  // the later pollers: first look a fraction of a round trip behind the one before
-            v = 0ull;
-            __builtin_amdgcn_s_sleep(1);
-            for (int w = 0; w < grp; ++w) __builtin_amdgcn_s_sleep(GJX_POLL_STAGGER);
-            if (!__hip_atomic_load(&seen[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-              v = __hip_atomic_load(&agg[(size_t)b * kGranulePad], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          bool other = false;
-          while ((v >> 60) != tag && budget) {
-            if (__hip_atomic_load(&seen[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) { other = true; break; }
-            --budget;
-            __builtin_amdgcn_s_sleep(1);
-            v = __hip_atomic_load(&agg[(size_t)b * kGranulePad], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          if ((v >> 60) == tag) {
-            const uint64_t S = v & ((1ull << 40) - 1);
-            const int e = S ? (int)((v >> 40) & 0xFFFFFu) + kTileDead : kTileDead;
-            P[b + 1] = S;
-            Eb[b] = e;
-            em = (float)e;
-            __hip_atomic_store(&seen[b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          } else if (!other && grp == 0) {                // (only the first poller reports: it runs the whole budget)
-            __hip_atomic_fetch_or(&f.ctrl[2], kStatusPollTimeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            P[b + 1] = 0;
-            Eb[b] = kTileDead;
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-          const int bb = threadIdx.x + k * THREADS;
-          rdy[k] = bb < nb ? __hip_atomic_load(&f.ready[bb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : rtag;
-        }
-        em = wave_max_dpp(em);
-        if (lane == 0) fred[wid] = em;
-      } else {
-        unsigned budget = kPollBudget;
-        float em = (float)kTileDead;
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-          const int b = threadIdx.x + k * THREADS;
-          if (b >= nb) break;
-          unsigned long long v = gv[k];
-          while ((v >> 60) != tag && budget) {
-            --budget;
-            __builtin_amdgcn_s_sleep(1);
-            v = __hip_atomic_load(&agg[(size_t)b * kGranulePad], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          if ((v >> 60) != tag) { __hip_atomic_fetch_or(&f.ctrl[2], kStatusPollTimeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); v = 0; }
-          const uint64_t S = v & ((1ull << 40) - 1);
-          const int e = S ? (int)((v >> 40) & 0xFFFFFu) + kTileDead : kTileDead;
-          P[b + 1] = S;
-          Eb[b] = e;
-          em = fmaxf(em, (float)e);
-        }
-        // the `ready` words: loads issued now, looked at after the tile search
-#pragma unroll
-        for (int k = 0; k < kPer; ++k) {
-          const int b = threadIdx.x + k * THREADS;
-          rdy[k] = b < nb ? __hip_atomic_load(&f.ready[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : rtag;
-        }
-        em = wave_max_dpp(em);
-        if (lane == 0) fred[wid] = em;   // (fred[0..NW) was last read for the block maximum, two barriers ago)
+      if (threadIdx.x == 0) {
+        float bs = 0.0f;
+        for (int w = 0; w < NW; ++w) bs += fred[NW + w];
+        const size_t slot = (size_t)((t - 1) % 3) * nb + blockIdx.x;   // ring over steps (complete before granule B goes out)
+        store_agent(&f.bsum[slot], bs);
+        store_agent(&f.bmax[slot], bm);
       }
     }
+    stage_step_constants(t);
+    // the record of step t-2, if this block is its finisher, off the critical path: ring loads out before the hashes,
+    // reduced behind them, written by thread 0 behind the next barrier (every block's entry of step t-2 was complete
+    // before its granule B of step t-1, which this block has gathered)
+    const bool fin = t >= 2 && (int)blockIdx.x == (t - 2) % nb;
+    float rpm[kPer], rps[kPer];
+    if (fin) lse_ring_issue(t - 2, rpm, rps);
+    if (t < T) ssm_noise_bits<RNG, DX>(key2{sKey[t & 1][0], sKey[t & 1][1]}, (uint64_t)j, nbits);
+    if (fin) lse_ring_reduce(rpm, rps);
+    grid_gather<kGranulePad>(f.aggA, tagA, f.ctrl, [&](int, unsigned long long v) { mx = fmaxf(mx, __uint_as_float((uint32_t)v)); });
+    mx = wave_max_dpp(mx);     // (no acquire fence: everything read from other blocks goes through agent-scope loads)
+    __syncthreads();
+    if (lane == 0) fred[wid] = mx;
+    __syncthreads();
+    mx = fred[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) mx = fmaxf(mx, fred[w]);
+    if (fin && threadIdx.x == 0) lse_ring_write(t - 2);
+    GJX_PSTAMP(2);
+    // ---- rendezvous B: tile totals of the fixed-point weights.  The granule goes out only after this lane's
+    //      write-through (sc1) stores of step t-1 — x, log w, the block sum — have completed; readers use sc1 loads: no
+    //      cache maintenance on either side (MI355X guide G16 form R2; a release fence per wave cost 60 us per step).
+    //      At t == T only the ordering matters (the last LSE record is finished behind it). ----
+    const unsigned long long tagB = (unsigned long long)((epoch + 2u * (unsigned)(t - 1) + 1u) % 16383u) + 1ull;
+    {
+      float xv[1] = {lw_own};
+      const uint64_t qv = (active && t < T) ? weight_q(xv, 0, 1, mx) : 0;
+      const uint64_t wt = wave_total_u64(qv);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (lane == 0) wsum[wid] = wt;     // (wsum was last read in the previous step's re-scan, barriers ago)
+      __syncthreads();
+      if (wid == 0) {
+        static_assert(NW <= 16, "the wave partials fit one DPP row");
+        const uint64_t tt = row_scan_u64(lane < NW ? wsum[lane] : 0);   // lane 15 = sum of lanes 0..15
+        if (lane == 15) __hip_atomic_store(&f.aggB[(size_t)blockIdx.x * kGranulePad], (tagB << 50) | (tt & kAggMask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    GJX_PSTAMP(3);
+    grid_gather<kGranulePad>(f.aggB, tagB, f.ctrl, [&](int b, unsigned long long val) { P[b + 1] = val; });
     if (threadIdx.x == 0) P[0] = 0;
     __syncthreads();
-    if constexpr (TILED) {
-      float em = fred[0];
-#pragma unroll
-      for (int w = 1; w < NW; ++w) em = fmaxf(em, fred[w]);
-      Emax = (int)em;
-      if (t >= 2 && (int)blockIdx.x == (t - 2) % nb && threadIdx.x == 0) lse_ring_write(t - 2);
-      GJX_PSTAMP(3);
-    }
     if (wid == 0) {
-      // prefix of the (shifted) tile totals by ONE wave — ceil(nb / 64) entries per lane, one DPP scan — instead of four
-      // waves and a barrier between their partial sums
+      // prefix of the tile totals by ONE wave — ceil(nb / 64) entries per lane, one DPP scan — instead of four waves and a
+      // barrier between their partial sums
       const int per = (nb + 63) >> 6;
       const int e0 = lane * per < nb ? lane * per : nb, e1 = (e0 + per) < nb ? (e0 + per) : nb;
       uint64_t loc = 0;
-      for (int e = e0; e < e1; ++e) {
-        if constexpr (TILED) { const int sh = Emax - Eb[e]; P[e + 1] = sh < 64 ? P[e + 1] >> sh : 0; }
-        loc += P[e + 1];
-      }
+      for (int e = e0; e < e1; ++e) loc += P[e + 1];
       uint64_t run = wave_scan_u64(loc) - loc;
       for (int e = e0; e < e1; ++e) { run += P[e + 1]; P[e + 1] = run; }
     }
     __syncthreads();
     const uint64_t total = P[nb];
     GJX_PSTAMP(4);
-    if constexpr (!TILED) {
-      if (t == T && (int)blockIdx.x == (T - 1) % nb) {             // the last record: its ring entries preceded granule B of this step
-        lse_ring_partials(T - 1);
-        __syncthreads();
-        if (threadIdx.x == 0) lse_ring_write(T - 1);
-      }
-    } else if (t == T) {                                            // the last record, once every block's ring entry is complete
-      check_ready();
+    if (t == T && (int)blockIdx.x == (T - 1) % nb) {               // the last record: its ring entries preceded granule B of this step
+      lse_ring_partials(T - 1);
       __syncthreads();
-      if ((int)blockIdx.x == (T - 1) % nb) {
-        lse_ring_partials(T - 1);
-        __syncthreads();
-        if (threadIdx.x == 0) lse_ring_write(T - 1);
-      }
+      if (threadIdx.x == 0) lse_ring_write(T - 1);
     }
     if (t == T) break;
     if (total == 0 && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_fetch_or(&f.ctrl[2], kStatusZeroTotal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -834,8 +647,8 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
       // the slot's source tile: first tile t with P[t + 1] > T = number of tiles whose inclusive prefix is <= T (fixed-trip
       // descent in the LDS prefix).  The tile index is non-decreasing in the slot index, so the block's source tiles are
       // the range between its first and its last slot's tile: no list to build, the two ends travel through LDS behind
-      // the one barrier the `ready` check needs anyway
-      uint64_t Tj = comb_threshold(active ? j : K - 1, sU, step, total);
+      // one barrier
+      const uint64_t Tj = comb_threshold(active ? j : K - 1, sU, step, total);
       // A block's slots draw from tiles near its own index (equal tile totals would make it exactly its own): the nine
       // boundaries of the eight tiles around blockIdx.x are read together (one LDS latency, same addresses in every lane)
       // and the tile is counted off; a threshold outside that window takes the fixed-trip descent (nine dependent reads)
@@ -856,10 +669,6 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
       }
       if (threadIdx.x == 0) s_range[0] = tile;
       if (threadIdx.x == THREADS - 1) s_range[1] = tile;                // (inactive lanes searched slot K - 1)
-      if constexpr (TILED) {
-        Tj = (Tj - P[tile]) << (Emax - Eb[tile]);                      // residual in the source tile's own units (< S_tile)
-        check_ready();                                                // before the barrier in front of the first foreign read
-      }
       GJX_PSTAMP(9);
       __syncthreads();
       const int tmin = s_range[0], ntiles = s_range[1] - tmin + 1;    // (tiles without weight inside the range are scanned for nothing)
@@ -887,11 +696,9 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
             for (int k = 0; k < 4; ++k) if (p0 + k < K) lw4[k] = load_agent(lw_prev + p0 + k);
           }
           if (f.timeline && c0 == 0) { asm volatile("" :: "v"(lw4[0]), "v"(lw4[3])); GJX_PSTAMP(10); }
-          const int es = TILED ? Eb[tsrc] : 0;
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            if constexpr (TILED) sacc += p0 + k < K ? tile_q(lw4[k], es) : 0;
-            else sacc += p0 + k < K ? weight_q(lw4, k, 1, mx) : 0;
+            sacc += p0 + k < K ? weight_q(lw4, k, 1, mx) : 0;
             qi[k] = sacc;
           }
           inc = wave_scan_u64(sacc);
@@ -899,7 +706,7 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
         }
         if (WPT > 1) __syncthreads();
         if (on) {
-          uint64_t base = (TILED ? 0 : P[tsrc]) + (inc - sacc);
+          uint64_t base = P[tsrc] + (inc - sacc);
           for (int w = 0; w < part; ++w) base += wsum[tl * WPT + w];
 #pragma unroll
           for (int k = 0; k < 4; ++k) cumL[tl * THREADS + part * 256 + lane * 4 + k] = base + qi[k];
@@ -919,8 +726,6 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
           src = (int64_t)tile * THREADS + l2;
         }
       }
-    } else if constexpr (TILED) {
-      check_ready();              // (a dead step reads nothing foreign, but the ring entries count on every step's check)
     }
     GJX_PSTAMP(5);
     if (active && t == T - 1 && f.ancestors) f.ancestors[j] = (int32_t)src;
@@ -969,7 +774,7 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
 }
 
 // ---- the tile-scaled systematic resampler as three plain launches (gjx_resample_indices_tiled): the step-by-step
-//      form of what k_ssm_persistent<TILED> does inside its loop; bit-identical ancestors ----
+//      form of what k_pf_persistent (gjx_pfilter.inl) does inside its loop; bit-identical ancestors ----
 __global__ __launch_bounds__(kTileQ) void k_tiled_quantise(const float* logw, int64_t K, uint64_t* cq, uint64_t* S, int32_t* E,
                                                            uint32_t* q_out, int32_t* e_out) {
   constexpr int NW = kTileQ / 64;
@@ -1150,7 +955,7 @@ int launch_ssm_move(const SsmArgs& a, int dx, int nblocks, hipStream_t st) {
   }
 }
 template <int RNG>
-int launch_ssm(const SsmArgs& a, int dx, int nblocks, hipStream_t st) {
+int launch_ssm_rng(const SsmArgs& a, int dx, int nblocks, hipStream_t st) {
   switch (dx) {
     case 1: hipLaunchKernelGGL((k_ssm_step<RNG, 1>), dim3(nblocks), dim3(256), 0, st, a); return 0;
     case 2: hipLaunchKernelGGL((k_ssm_step<RNG, 2>), dim3(nblocks), dim3(256), 0, st, a); return 0;
@@ -1160,6 +965,24 @@ int launch_ssm(const SsmArgs& a, int dx, int nblocks, hipStream_t st) {
     case 32: hipLaunchKernelGGL((k_ssm_step<RNG, 32>), dim3(nblocks), dim3(256), 0, st, a); return 0;
     default: return -1;
   }
+}
+// k_ssm_step over ceil(K / 256) blocks; -1 when dx has no kernel
+int launch_ssm(const SsmArgs& a, int32_t rng_mode, int dx, hipStream_t st) {
+  const int nblocks = (int)((a.K + 255) / 256);
+  return rng_mode == GJX_RNG_JAX32 ? launch_ssm_rng<GJX_RNG_JAX32>(a, dx, nblocks, st) : launch_ssm_rng<GJX_RNG_FLAT>(a, dx, nblocks, st);
+}
+
+// the argument block of one k_ssm_step / k_ssm_fused_step launch, every field but the move fields (which stay off) from
+// gjx_ssm_step's arguments
+SsmArgs ssm_args(const gjx_ssm* m, key2 key, int t, int64_t K, int64_t offset, const float* x_prev, int64_t prev_stride,
+                 const int32_t* anc, const float* y, float* x_out, float* logw, unsigned long long* partials, unsigned* ticket,
+                 float* lse, int64_t K_total) {
+  SsmArgs a;
+  a.A = m->A_dev; a.H = m->H_dev; a.y = y; a.q = m->q; a.r = m->r; a.q0 = m->q0; a.dy = m->dy; a.t = t;
+  a.key = key; a.K = K; a.offset = offset; a.prev_stride = prev_stride;
+  a.x_prev = x_prev; a.anc = anc; a.x_out = x_out; a.logw = logw; a.partials = partials; a.ticket = ticket; a.lse = lse;
+  a.log_k_total = (float)log((double)K_total);
+  return a;
 }
 }  // namespace
 
@@ -1178,16 +1001,9 @@ extern "C" int gjx_ssm_step(const gjx_ssm* m, uint32_t key0, uint32_t key1, int3
     ticket = (unsigned*)workspace;
     partials = (unsigned long long*)((char*)workspace + kWsHeaderBytes);
   }
-  SsmArgs a;
-  a.A = m->A_dev; a.H = m->H_dev; a.y = y_dev; a.q = m->q; a.r = m->r; a.q0 = m->q0; a.dy = m->dy; a.t = t;
-  a.key = key2{key0, key1}; a.K = K; a.offset = particle_offset; a.prev_stride = prev_stride;
-  a.x_prev = x_prev; a.anc = anc; a.x_out = x_out; a.logw = logw; a.partials = partials; a.ticket = ticket; a.lse = lse;
-  a.log_k_total = (float)log((double)K_total);
-  a.m_prev = nullptr; a.m_out = nullptr; a.y_prev = nullptr; a.n_moves = 0; a.move_scale = 0.0f; a.accepted = nullptr; a.x_moved = nullptr;
-  const int nblocks = (int)((K + 255) / 256);
-  const int rc = rng_mode == GJX_RNG_JAX32 ? launch_ssm<GJX_RNG_JAX32>(a, m->dx, nblocks, st)
-                                           : launch_ssm<GJX_RNG_FLAT>(a, m->dx, nblocks, st);
-  if (rc) return gjx_fail(GJX_EUNSUPPORTED, "gjx_ssm_step: dx must be one of 1,2,4,8,16,32");
+  const SsmArgs a = ssm_args(m, key2{key0, key1}, t, K, particle_offset, x_prev, prev_stride, anc, y_dev, x_out, logw, partials,
+                             ticket, lse, K_total);
+  if (launch_ssm(a, rng_mode, m->dx, st)) return gjx_fail(GJX_EUNSUPPORTED, "gjx_ssm_step: dx must be one of 1,2,4,8,16,32");
   GJX_CHECK_LAUNCH("gjx_ssm_step");
   return GJX_OK;
 }
@@ -1210,11 +1026,8 @@ extern "C" int gjx_ssm_step_move(const gjx_ssm* m, uint32_t key0, uint32_t key1,
     ticket = (unsigned*)workspace;
     partials = (unsigned long long*)((char*)workspace + kWsHeaderBytes);
   }
-  SsmArgs a;
-  a.A = m->A_dev; a.H = m->H_dev; a.y = y_dev; a.q = m->q; a.r = m->r; a.q0 = m->q0; a.dy = m->dy; a.t = t;
-  a.key = key2{key0, key1}; a.K = K; a.offset = particle_offset; a.prev_stride = prev_stride;
-  a.x_prev = x_prev; a.anc = anc; a.x_out = x_out; a.logw = logw; a.partials = partials; a.ticket = ticket; a.lse = lse;
-  a.log_k_total = (float)log((double)K_total);
+  SsmArgs a = ssm_args(m, key2{key0, key1}, t, K, particle_offset, x_prev, prev_stride, anc, y_dev, x_out, logw, partials, ticket,
+                       lse, K_total);
   a.m_prev = t > 1 ? m_prev : nullptr; a.m_out = m_out; a.y_prev = y_prev_dev; a.n_moves = t > 0 ? n_moves : 0;
   a.move_scale = move_scale; a.accepted = accepted; a.x_moved = t > 0 ? x_moved_out : nullptr;
   const int nblocks = (int)((K + 255) / 256);
@@ -1225,27 +1038,6 @@ extern "C" int gjx_ssm_step_move(const gjx_ssm* m, uint32_t key0, uint32_t key1,
   return GJX_OK;
 }
 
-
-// ---- whole bootstrap filter on one GPU: the T-step loop runs in C++ so that the per-step launches
-// (one-launch resampling indices, fused step) are issued back to back without Python in between.
-// Key discipline as in inference/pf.py: k_t = fold_in(k_{t-1}, t) (scan.py:268); (k_prop, k_res) = split(k_t);
-// the systematic comb offset is uniform(k_res).
-extern "C" int gjx_weight_cumsum(const float*, int64_t, int32_t, const float*, int32_t, uint64_t*, uint64_t*, float*, int64_t, void*, size_t, void*);
-extern "C" int gjx_resample_systematic(const uint64_t*, int64_t, const uint64_t*, double, int64_t, int64_t, int64_t, int32_t*, void*);
-extern "C" int gjx_resample_indices(const float*, int64_t, int32_t, const float*, int32_t, double, int64_t, int32_t*, uint64_t*, uint64_t*, float*, int64_t, void*, size_t, void*);
-
-static void host_threefry(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t out[2]) {
-  static const int R[8] = {13, 15, 26, 6, 17, 29, 16, 24};
-  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
-  uint32_t x0 = c0 + ks[0], x1 = c1 + ks[1];
-  for (int g = 0; g < 5; ++g) {
-    const int* r = (g & 1) ? R + 4 : R;
-    for (int j = 0; j < 4; ++j) { x0 += x1; x1 = (x1 << r[j]) | (x1 >> (32 - r[j])); x1 ^= x0; }
-    x0 += ks[(g + 1) % 3];
-    x1 += ks[(g + 2) % 3] + (uint32_t)(g + 1);
-  }
-  out[0] = x0; out[1] = x1;
-}
 
 extern "C" int gjx_resample_indices_tiled(const float* logw, int64_t K, double u, int64_t N, int32_t* ancestors, uint64_t* cum,
                                           uint32_t* q_out, int32_t* e_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1297,13 +1089,32 @@ extern "C" int gjx_resample_sorted_multinomial_tiled(const float* logw, int64_t 
 }
 
 
-// ---- k_pf_persistent on one GPU: step 0 as a plain launch, then steps 1 .. T-1 in ONE launch (gjx_pfilter.inl) ----
+// ---- whole bootstrap filter on one GPU: the T-step loop runs in C++ so that the per-step launches are issued back to back
+// without Python in between, or the whole filter is one launch after step 0.  Every form takes its step keys and comb
+// offsets from pf_step_keys (the key discipline of inference/pf.py). ----
+
+// the one-launch filters may run: no GJX_WEIGHTS_PLAIN_LAUNCHES in effect and GJX_SSM_PERSISTENT not 0
+static bool one_launch_allowed() {
+  const char* e = getenv("GJX_SSM_PERSISTENT");
+  return !gjx_plain_launches_forced() && !(e && atoi(e) == 0);
+}
+
+// step 0 of the one-launch filters, from the prior: a plain k_ssm_step launch that leaves no LSE partials (the one-launch
+// kernel finishes step 0's record from its log-weights)
+static int ssm_step0(const gjx_ssm* m, const std::vector<uint32_t>& keys, int32_t rng_mode, int64_t K, const float* ys_dev, float* x_out,
+                     float* logw, hipStream_t st) {
+  const SsmArgs a = ssm_args(m, key2{keys[0], keys[1]}, 0, K, 0, nullptr, K, nullptr, ys_dev, x_out, logw, nullptr, nullptr, nullptr, K);
+  if (launch_ssm(a, rng_mode, m->dx, st)) return gjx_fail(GJX_EUNSUPPORTED, "gjx_ssm_filter: dx must be one of 1,2,4,8,16,32");
+  GJX_CHECK_LAUNCH("gjx_ssm_filter(step 0)");
+  return GJX_OK;
+}
+
+// ---- k_pf_persistent on one GPU (tile-scaled scheme): step 0 as a plain launch, then steps 1 .. T-1 in ONE launch (gjx_pfilter.inl) ----
 struct PfMove { float* m_a; float* m_b; int n_moves; float move_scale; unsigned long long* acc_total; };
 // GJX_EUNSUPPORTED when the shape does not fit the kernel or its grid would not be co-resident (the caller falls back)
 static int pf_filter_launch(const gjx_ssm* m, uint32_t key0, uint32_t key1, int32_t rng_mode, int32_t T, int64_t K, const float* ys_dev,
-                            float* x_a, float* x_b, float* logw, float* lw_alt, int32_t* ancestors, float* lse_steps, char* ws1, char* ws2,
+                            float* x_a, float* x_b, float* logw, float* lw_alt, int32_t* ancestors, float* lse_steps, char* ws2,
                             size_t need, void* stream, const PfMove* mv) {
-  const int64_t nblk = (K + 255) / 256;
   PfPlan pf;
   if (pf_plan(rng_mode, m->dx, m->dy, K, 1, 1, &pf, mv != nullptr) != GJX_OK ||
       256 + (16 * (size_t)kPfGranulePad + 24) * (size_t)pf.nt + 8 * (size_t)pf.grid + 16 * (size_t)T + 64 > need)
@@ -1328,17 +1139,7 @@ static int pf_filter_launch(const gjx_ssm* m, uint32_t key0, uint32_t key1, int3
   // (step keys and comb offsets travel as kernel arguments: no host buffer outlives this call, no per-thread staging state)
   if (int rcu = upload_words(us_dev, h_us.data(), (size_t)T, st)) return rcu;
   if (int rcu = upload_words(keys_dev, h_keys.data(), (size_t)T, st)) return rcu;
-  {   // step 0: from the prior (no move: there is nothing to rejuvenate yet)
-    SsmArgs a;
-    a.A = m->A_dev; a.H = m->H_dev; a.y = ys_dev; a.q = m->q; a.r = m->r; a.q0 = m->q0; a.dy = m->dy; a.t = 0;
-    a.key = key2{h_keys[0], h_keys[1]}; a.K = K; a.offset = 0; a.prev_stride = K;
-    a.x_prev = nullptr; a.anc = nullptr; a.x_out = x_a; a.logw = lw_of(0);
-    a.partials = nullptr; a.ticket = (unsigned*)ws1; a.lse = nullptr; a.log_k_total = (float)log((double)K);
-    a.m_prev = nullptr; a.m_out = nullptr; a.y_prev = nullptr; a.n_moves = 0; a.move_scale = 0.0f; a.accepted = nullptr; a.x_moved = nullptr;
-    const int rc = rng_mode == GJX_RNG_JAX32 ? launch_ssm<GJX_RNG_JAX32>(a, m->dx, (int)nblk, st) : launch_ssm<GJX_RNG_FLAT>(a, m->dx, (int)nblk, st);
-    if (rc) return gjx_fail(GJX_EUNSUPPORTED, "gjx_ssm_filter: dx must be one of 1,2,4,8,16,32");
-    GJX_CHECK_LAUNCH("gjx_ssm_filter(step 0)");
-  }
+  if (int rc0 = ssm_step0(m, h_keys, rng_mode, K, ys_dev, x_a, lw_of(0), st)) return rc0;   // (no move: there is nothing to rejuvenate yet)
   PfArgs f;
   memset(&f, 0, sizeof(f));
   f.A = m->A_dev; f.H = m->H_dev; f.ys = ys_dev; f.q = m->q; f.r = m->r; f.dy = m->dy; f.T = T;
@@ -1356,9 +1157,121 @@ static int pf_filter_launch(const gjx_ssm* m, uint32_t key0, uint32_t key1, int3
   if (e != hipSuccess) return gjx_fail_hip(e, "gjx_ssm_filter(k_pf_persistent)");
   return GJX_OK;
 }
-extern "C" int gjx_ssm_filter_scheme(const gjx_ssm* m, uint32_t key0, uint32_t key1, int32_t rng_mode, int32_t T, int64_t K,
-                                     const float* ys_dev, float* x_a, float* x_b, float* logw, uint64_t* cum, int32_t* ancestors,
-                                     float* lse_steps, int32_t weight_scheme, void* workspace, size_t workspace_bytes, void* stream);
+
+// ---- k_ssm_persistent on one GPU (global-maximum scheme): step 0 as a plain launch, then steps 1 .. T-1 in ONE launch ----
+template <int RNG, int THREADS>
+static const void* ssm_persistent_kernel(int dx) {
+  switch (dx) {
+    case 2: return (const void*)k_ssm_persistent<RNG, 2, THREADS>;
+    case 4: return (const void*)k_ssm_persistent<RNG, 4, THREADS>;
+    case 8: return (const void*)k_ssm_persistent<RNG, 8, THREADS>;
+    case 16: return (const void*)k_ssm_persistent<RNG, 16, THREADS>;
+    default: return nullptr;
+  }
+}
+// GJX_EUNSUPPORTED when the shape does not fit the kernel or its grid would not be co-resident (the caller falls back)
+static int ssm_persistent_launch(const gjx_ssm* m, uint32_t key0, uint32_t key1, int32_t rng_mode, int32_t T, int64_t K, const float* ys_dev,
+                                 float* x_a, float* x_b, float* logw, float* lw_alt, int32_t* ancestors, float* lse_steps, char* ws2,
+                                 size_t need, hipStream_t st) {
+  // 1024-thread blocks (one per CU) once the grid would have more than 256 blocks of 256: fewer, cheaper rendezvous
+  const int threads = (K + 255) / 256 > 256 ? 1024 : 256;
+  const bool jax = rng_mode == GJX_RNG_JAX32;
+  const void* fn = threads == 1024 ? (jax ? ssm_persistent_kernel<GJX_RNG_JAX32, 1024>(m->dx) : ssm_persistent_kernel<GJX_RNG_FLAT, 1024>(m->dx))
+                                   : (jax ? ssm_persistent_kernel<GJX_RNG_JAX32, 256>(m->dx) : ssm_persistent_kernel<GJX_RNG_FLAT, 256>(m->dx));
+  const int64_t nb = (K + threads - 1) / threads;
+  const size_t gp = (size_t)kGranulePad, NB = (size_t)nb;
+  if (!fn || m->dy > kSsmPersistMaxDy || nb > kSsmFusedMaxTiles || nb > gjx_coresident_blocks(fn, threads, 0) ||
+      256 + (16 * gp + 24) * NB + 16 * (size_t)T + 64 > need)
+    return GJX_EUNSUPPORTED;
+  auto lw_of = [&](int t) { return ((T - 1 - t) & 1) ? lw_alt : logw; };
+  std::vector<uint32_t> h_keys;
+  std::vector<double> h_us;
+  pf_step_keys(key0, key1, T, h_keys, h_us);
+  // ws2: [256 B control][aggA 8 gp NB][aggB 8 gp NB][bsum ring 12 NB][bmax ring 12 NB][us 8 T][keys 8 T]
+  unsigned long long* aggA = (unsigned long long*)(ws2 + kWsHeaderBytes);
+  unsigned long long* aggB = aggA + gp * NB;
+  float* bsum = (float*)(aggB + gp * NB);
+  float* bmax = bsum + 3 * NB;
+  double* us_dev = (double*)(bmax + 3 * NB);
+  uint32_t* keys_dev = (uint32_t*)(us_dev + T);
+  // the weight schemes' kernels (and k_ssm_fused_step) tag their granules differently: no stale granule of another kernel may
+  // pass for one of this launch
+  hipError_t e = hipMemsetAsync(aggA, 0, (16 * gp + 24) * NB, st);
+  if (e != hipSuccess) return gjx_fail_hip(e, "gjx_ssm_filter(workspace)");
+  if (int rcu = upload_words(us_dev, h_us.data(), (size_t)T, st)) return rcu;        // (kernel arguments: nothing outlives this call)
+  if (int rcu = upload_words(keys_dev, h_keys.data(), (size_t)T, st)) return rcu;
+  if (int rc0 = ssm_step0(m, h_keys, rng_mode, K, ys_dev, x_a, lw_of(0), st)) return rc0;
+  SsmPersistArgs f;
+  f.A = m->A_dev; f.H = m->H_dev; f.ys = ys_dev; f.q = m->q; f.r = m->r; f.dy = m->dy; f.T = T; f.K = K;
+  f.x_a = x_a; f.x_b = x_b; f.lw_even = logw; f.lw_odd = lw_alt;
+  f.keys = keys_dev; f.us = us_dev; f.lse_steps = lse_steps; f.ancestors = ancestors;
+  f.aggA = aggA; f.aggB = aggB; f.bsum = bsum; f.bmax = bmax; f.ctrl = (unsigned*)ws2 + 8; f.log_k = (float)log((double)K);
+  f.timeline = gjx::debug_timeline(128 * NB);
+  void* args[] = {&f};
+  e = hipLaunchKernel(fn, dim3((unsigned)nb), dim3((unsigned)threads), args, 0, st);
+  if (e != hipSuccess) return gjx_fail_hip(e, "gjx_ssm_filter(persistent)");
+  return GJX_OK;
+}
+
+// ---- k_ssm_fused_step (global-maximum scheme): step 0 by k_ssm_step, then one launch per step ----
+template <int RNG>
+static const void* ssm_fused_kernel_rng(int dx) {
+  switch (dx) {
+    case 2: return (const void*)k_ssm_fused_step<RNG, 2>;
+    case 4: return (const void*)k_ssm_fused_step<RNG, 4>;
+    case 8: return (const void*)k_ssm_fused_step<RNG, 8>;
+    case 16: return (const void*)k_ssm_fused_step<RNG, 16>;
+    default: return nullptr;
+  }
+}
+// the fused step for this shape when its grid of K / 256 blocks is co-resident and its granules fit the workspace, else NULL
+static const void* ssm_fused_kernel(int32_t rng_mode, int dx, int64_t K, size_t need) {
+  const int64_t nblk = (K + 255) / 256;
+  const void* fn = rng_mode == GJX_RNG_JAX32 ? ssm_fused_kernel_rng<GJX_RNG_JAX32>(dx) : ssm_fused_kernel_rng<GJX_RNG_FLAT>(dx);
+  if (!fn || nblk > kSsmFusedMaxTiles || nblk > gjx_coresident_blocks(fn, 256, 0) || 256 + 16 * (size_t)nblk > need) return nullptr;
+  return fn;
+}
+static int ssm_fused_filter(const void* fused_fn, const gjx_ssm* m, uint32_t key0, uint32_t key1, int32_t rng_mode, int32_t T, int64_t K,
+                            const float* ys_dev, float* x_a, float* x_b, float* logw, float* lw_alt, int32_t* ancestors, float* lse_steps,
+                            char* ws1, char* ws2, hipStream_t st) {
+  const int64_t nblk = (K + 255) / 256;
+  {
+    const hipError_t e0 = hipMemsetAsync(ws2 + kWsHeaderBytes, 0, 8 * (size_t)nblk, st);   // see ssm_persistent_launch
+    if (e0 != hipSuccess) return gjx_fail_hip(e0, "gjx_ssm_filter(granules)");
+  }
+  std::vector<uint32_t> keys;
+  std::vector<double> us;
+  pf_step_keys(key0, key1, T, keys, us);
+  auto lw_of = [&](int t) { return ((T - 1 - t) & 1) ? lw_alt : logw; };   // the last step writes the caller's logw
+  auto part_of = [&](int t) { return (unsigned long long*)(ws1 + kWsHeaderBytes) + (size_t)(t & 1) * nblk; };
+  for (int t = 0; t < T; ++t) {
+    const SsmArgs a = ssm_args(m, key2{keys[2 * t], keys[2 * t + 1]}, t, K, 0, t > 0 ? ((t & 1) ? x_a : x_b) : nullptr, K, nullptr,
+                               ys_dev + (size_t)t * m->dy, (t & 1) ? x_b : x_a, lw_of(t), part_of(t), (unsigned*)ws1,
+                               t == T - 1 ? lse_steps + 4 * (size_t)t : nullptr, K);
+    if (t == 0) {
+      if (launch_ssm(a, rng_mode, m->dx, st)) return gjx_fail(GJX_EUNSUPPORTED, "gjx_ssm_filter: dx must be one of 1,2,4,8,16,32");
+      GJX_CHECK_LAUNCH("gjx_ssm_filter(step 0)");
+      continue;
+    }
+    SsmFusedArgs f;
+    f.s = a;
+    f.logw_prev = lw_of(t - 1);
+    f.partials_prev = (const float*)part_of(t - 1);
+    f.n_partials_prev = (int)nblk;
+    f.lse_prev_out = lse_steps + 4 * (size_t)(t - 1);
+    f.log_k_total_prev = (float)log((double)K);
+    f.u = us[t];
+    f.ancestors = t == T - 1 ? ancestors : nullptr;
+    f.agg = (unsigned long long*)(ws2 + kWsHeaderBytes);
+    f.ctrl = (unsigned*)ws2 + 8;
+    f.timeline = nullptr;   // debug: phase stamps of the middle step (profiles/microbench/ssm_timeline.py)
+    if (t == T / 2) f.timeline = gjx::debug_timeline(64 * (size_t)nblk);
+    void* args[] = {&f};
+    const hipError_t e = hipLaunchKernel(fused_fn, dim3((unsigned)nblk), dim3(256), args, 0, st);
+    if (e != hipSuccess) return gjx_fail_hip(e, "gjx_ssm_filter(fused step)");
+  }
+  return GJX_OK;
+}
 
 extern "C" int gjx_ssm_filter_move(const gjx_ssm* m, uint32_t key0, uint32_t key1, int32_t rng_mode, int32_t T, int64_t K,
                                    const float* ys_dev, float* x_a, float* x_b, float* m_a, float* m_b, float* logw, float* logw_alt,
@@ -1368,10 +1281,10 @@ extern "C" int gjx_ssm_filter_move(const gjx_ssm* m, uint32_t key0, uint32_t key
     return gjx_fail(GJX_EINVAL, "gjx_ssm_filter_move: bad argument");
   const size_t need = gjx_workspace_bytes(GJX_OP_SSM, K);
   if (!workspace || workspace_bytes < 2 * need + 64) return gjx_fail(GJX_EWORKSPACE, "gjx_ssm_filter_move: workspace too small (2x OP_SSM + 64)");
-  if (getenv("GJX_SSM_PERSISTENT") && atoi(getenv("GJX_SSM_PERSISTENT")) == 0)
+  if (!one_launch_allowed())
     return gjx_fail(GJX_EUNSUPPORTED, "gjx_ssm_filter_move: one-launch filters are disabled (GJX_SSM_PERSISTENT=0)");
   PfMove mv{m_a, m_b, (int)n_moves, move_scale, (unsigned long long*)accepted_total};
-  const int rc = pf_filter_launch(m, key0, key1, rng_mode, T, K, ys_dev, x_a, x_b, logw, logw_alt, ancestors, lse_steps, (char*)workspace,
+  const int rc = pf_filter_launch(m, key0, key1, rng_mode, T, K, ys_dev, x_a, x_b, logw, logw_alt, ancestors, lse_steps,
                                   (char*)workspace + need, need, stream, &mv);
   if (rc == GJX_EUNSUPPORTED) return gjx_fail(GJX_EUNSUPPORTED, "gjx_ssm_filter_move: shape or size outside the one-launch filter (use gjx_ssm_step_move per step)");
   return rc;
@@ -1401,182 +1314,41 @@ extern "C" int gjx_ssm_filter_scheme(const gjx_ssm* m, uint32_t key0, uint32_t k
   if (!workspace || workspace_bytes < 2 * need + 64) return gjx_fail(GJX_EWORKSPACE, "gjx_ssm_filter: workspace too small (2x OP_SSM + 64)");
   char* ws1 = (char*)workspace;
   char* ws2 = ws1 + need;
+  hipStream_t st = (hipStream_t)stream;
+  float* lw_alt = (float*)cum;                     // the one-launch and fused forms do not use the prefix sums: second log-weight buffer
+  const bool one_launch = T > 1 && one_launch_allowed();
+  if (tiled) {
+    if (one_launch) {
+      const int rc = pf_filter_launch(m, key0, key1, rng_mode, T, K, ys_dev, x_a, x_b, logw, lw_alt, ancestors, lse_steps, ws2, need, stream, nullptr);
+      if (rc != GJX_EUNSUPPORTED) return rc;
+    }
+  } else if (const void* fused_fn = ssm_fused_kernel(rng_mode, m->dx, K, need)) {
+    // the whole filter in one launch where k_ssm_fused_step's grid is co-resident too, else one fused launch per step
+    if (one_launch) {
+      const int rc = ssm_persistent_launch(m, key0, key1, rng_mode, T, K, ys_dev, x_a, x_b, logw, lw_alt, ancestors, lse_steps, ws2, need, st);
+      if (rc != GJX_EUNSUPPORTED) return rc;
+    }
+    return ssm_fused_filter(fused_fn, m, key0, key1, rng_mode, T, K, ys_dev, x_a, x_b, logw, lw_alt, ancestors, lse_steps, ws1, ws2, st);
+  }
+  // one step at a time: the multi-launch resampler in front of every step after the first
+  std::vector<uint32_t> keys;
+  std::vector<double> us;
+  pf_step_keys(key0, key1, T, keys, us);
   uint64_t* bt = (uint64_t*)(ws2 + need);
-  uint32_t k[2] = {key0, key1};
-  // one launch per step when the grid of K / 256 blocks is co-resident (k_ssm_fused_step); GJX_SSM_TWO_LAUNCH=1 keeps
-  // the resample + step pair
-  const int64_t nblk = (K + 255) / 256;
-  const void* fused_fn = nullptr;
-  if (!tiled && (!getenv("GJX_SSM_TWO_LAUNCH") || atoi(getenv("GJX_SSM_TWO_LAUNCH")) == 0)) {
-    const bool jax = rng_mode == GJX_RNG_JAX32;
-    switch (m->dx) {
-      case 2: fused_fn = jax ? (const void*)k_ssm_fused_step<GJX_RNG_JAX32, 2> : (const void*)k_ssm_fused_step<GJX_RNG_FLAT, 2>; break;
-      case 4: fused_fn = jax ? (const void*)k_ssm_fused_step<GJX_RNG_JAX32, 4> : (const void*)k_ssm_fused_step<GJX_RNG_FLAT, 4>; break;
-      case 8: fused_fn = jax ? (const void*)k_ssm_fused_step<GJX_RNG_JAX32, 8> : (const void*)k_ssm_fused_step<GJX_RNG_FLAT, 8>; break;
-      case 16: fused_fn = jax ? (const void*)k_ssm_fused_step<GJX_RNG_JAX32, 16> : (const void*)k_ssm_fused_step<GJX_RNG_FLAT, 16>; break;
-      default: break;
-    }
-    if (fused_fn && (nblk > kSsmFusedMaxTiles || nblk > gjx_coresident_blocks(fused_fn, 256, 0) || 256 + 16 * (size_t)nblk > need)) fused_fn = nullptr;
-  }
-  // the whole filter in one launch (k_ssm_persistent) when everything fits: GJX_SSM_PERSISTENT=0 keeps one launch per step
-  const void* pers_fn = nullptr;
-  int pthreads = 256;
-  int64_t pblk = nblk;
-  if ((fused_fn || tiled) && T > 1 && (!gjx_plain_launches_forced() && (!getenv("GJX_SSM_PERSISTENT") || atoi(getenv("GJX_SSM_PERSISTENT")) != 0))) {
-    const bool jax = rng_mode == GJX_RNG_JAX32;
-    // 1024-thread blocks (one per CU) once the grid would have more than 256 blocks of 256: fewer, cheaper rendezvous;
-    // always for the tile-scaled scheme (its quantisation tile is 1024 particles)
-    pthreads = (tiled || (nblk > 256 && (!getenv("GJX_SSM_THREADS") || atoi(getenv("GJX_SSM_THREADS")) == 1024))) ? 1024 : 256;
-#define GJX_PERS(DXV) (tiled ? (jax ? (const void*)k_ssm_persistent<GJX_RNG_JAX32, DXV, 1024, true> : (const void*)k_ssm_persistent<GJX_RNG_FLAT, DXV, 1024, true>) \
-                     : pthreads == 1024 ? (jax ? (const void*)k_ssm_persistent<GJX_RNG_JAX32, DXV, 1024, false> : (const void*)k_ssm_persistent<GJX_RNG_FLAT, DXV, 1024, false>) \
-                                        : (jax ? (const void*)k_ssm_persistent<GJX_RNG_JAX32, DXV, 256, false> : (const void*)k_ssm_persistent<GJX_RNG_FLAT, DXV, 256, false>))
-    switch (m->dx) {
-      case 2: pers_fn = GJX_PERS(2); break;
-      case 4: pers_fn = GJX_PERS(4); break;
-      case 8: pers_fn = GJX_PERS(8); break;
-      case 16: pers_fn = GJX_PERS(16); break;
-      default: break;
-    }
-#undef GJX_PERS
-    pblk = (K + pthreads - 1) / pthreads;
-    if (pers_fn && (m->dy > kSsmPersistMaxDy || pblk > kSsmFusedMaxTiles || pblk > gjx_coresident_blocks(pers_fn, pthreads, 0) || 256 + (16 * (size_t)kGranulePad + 32) * (size_t)pblk + 16 * (size_t)T + 64 > need)) pers_fn = nullptr;
-  }
-  // tile-scaled scheme beyond one slot per lane (or GJX_PF=1): k_pf_persistent, several quantisation tiles per block
-  // (the kernel on the shared skeleton, k_pf_persistent, first — since its prefix runs in one wave for few tiles it is the faster of
-  // the two at config 3's size as well: 11.2 against 11.5 us per step; GJX_PF=0 keeps k_ssm_persistent<TILED>)
-  if (tiled && T > 1 && (!pers_fn || !(getenv("GJX_PF") && atoi(getenv("GJX_PF")) == 0)) &&
-      (!gjx_plain_launches_forced() && (!getenv("GJX_SSM_PERSISTENT") || atoi(getenv("GJX_SSM_PERSISTENT")) != 0))) {
-    const int rc_pf = pf_filter_launch(m, key0, key1, rng_mode, T, K, ys_dev, x_a, x_b, logw, (float*)cum, ancestors, lse_steps, ws1, ws2, need,
-                                       stream, nullptr);
-    if (rc_pf != GJX_EUNSUPPORTED) return rc_pf;
-  }
-  if (pers_fn) {
-    hipStream_t st = (hipStream_t)stream;
-    float* lw_alt = (float*)cum;
-    auto lw_of = [&](int t) { return ((T - 1 - t) & 1) ? lw_alt : logw; };
-    std::vector<uint32_t> h_keys(2 * (size_t)T, 0u);
-    std::vector<double> h_us((size_t)T, 0.0);
-    uint32_t kp0[2] = {0u, 0u};
-    for (int t = 0; t < T; ++t) {
-      uint32_t kt[2], kp[2], kr[2], b[2];
-      host_threefry(k[0], k[1], 0u, (uint32_t)t, kt);
-      k[0] = kt[0]; k[1] = kt[1];
-      host_threefry(k[0], k[1], 0u, 0u, kp);
-      host_threefry(k[0], k[1], 0u, 1u, kr);
-      host_threefry(kr[0], kr[1], 0u, 0u, b);
-      h_keys[2 * t] = kp[0]; h_keys[2 * t + 1] = kp[1];
-      h_us[t] = (double)((b[0] ^ b[1]) >> 9) / 8388608.0;
-      if (t == 0) { kp0[0] = kp[0]; kp0[1] = kp[1]; }
-    }
-    // ws2: [256 B control][aggA 8 gp nb][aggB 8 gp nb][bsum ring 12 nb][bmax ring 12 nb][ready 4 nb + 4 nb pad][us 8 T][keys 8 T]
-    const size_t gp = (size_t)kGranulePad;                    // one 64-byte line per granule, both schemes
-    unsigned long long* aggA = (unsigned long long*)(ws2 + kWsHeaderBytes);
-    unsigned long long* aggB = aggA + gp * pblk;
-    float* bsum = (float*)(aggB + gp * pblk);
-    float* bmax = bsum + 3 * pblk;
-    unsigned* ready = (unsigned*)(bmax + 3 * pblk);
-    double* us_dev = (double*)(ready + 2 * pblk);
-    uint32_t* keys_dev = (uint32_t*)(us_dev + T);
-    // the two schemes (and k_ssm_fused_step) tag their granules differently: no stale granule of another kernel may pass for
-    // one of this launch
-    hipError_t e = hipMemsetAsync(aggA, 0, (16 * gp + 32) * (size_t)pblk, st);
-    if (e != hipSuccess) return gjx_fail_hip(e, "gjx_ssm_filter(workspace)");
-    if (int rcu = upload_words(us_dev, h_us.data(), (size_t)T, st)) return rcu;        // (kernel arguments: nothing outlives this call)
-    if (int rcu = upload_words(keys_dev, h_keys.data(), (size_t)T, st)) return rcu;
-    {   // step 0: from the prior
-      SsmArgs a;
-      a.A = m->A_dev; a.H = m->H_dev; a.y = ys_dev; a.q = m->q; a.r = m->r; a.q0 = m->q0; a.dy = m->dy; a.t = 0;
-      a.key = key2{kp0[0], kp0[1]}; a.K = K; a.offset = 0; a.prev_stride = K;
-      a.x_prev = nullptr; a.anc = nullptr; a.x_out = x_a; a.logw = lw_of(0);
-      a.partials = nullptr; a.ticket = (unsigned*)ws1; a.lse = nullptr; a.log_k_total = (float)log((double)K);
-      a.m_prev = nullptr; a.m_out = nullptr; a.y_prev = nullptr; a.n_moves = 0; a.move_scale = 0.0f; a.accepted = nullptr; a.x_moved = nullptr;
-      const int rc = rng_mode == GJX_RNG_JAX32 ? launch_ssm<GJX_RNG_JAX32>(a, m->dx, (int)nblk, st) : launch_ssm<GJX_RNG_FLAT>(a, m->dx, (int)nblk, st);
-      if (rc) return gjx_fail(GJX_EUNSUPPORTED, "gjx_ssm_filter: dx must be one of 1,2,4,8,16,32");
-      GJX_CHECK_LAUNCH("gjx_ssm_filter(step 0)");
-    }
-    SsmPersistArgs f;
-    f.A = m->A_dev; f.H = m->H_dev; f.ys = ys_dev; f.q = m->q; f.r = m->r; f.dy = m->dy; f.T = T; f.K = K;
-    f.x_a = x_a; f.x_b = x_b; f.lw_even = logw; f.lw_odd = lw_alt;
-    f.keys = keys_dev; f.us = us_dev; f.lse_steps = lse_steps; f.ancestors = ancestors;
-    f.aggA = aggA; f.aggB = aggB; f.bsum = bsum; f.bmax = bmax; f.ready = ready; f.ctrl = (unsigned*)ws2 + 8; f.log_k = (float)log((double)K);
-    f.timeline = nullptr;
-    f.timeline = gjx::debug_timeline(128 * (size_t)pblk);
-    void* args[] = {&f};
-    e = hipLaunchKernel(pers_fn, dim3((unsigned)pblk), dim3((unsigned)pthreads), args, 0, st);
-    if (e != hipSuccess) return gjx_fail_hip(e, "gjx_ssm_filter(persistent)");
-    return GJX_OK;
-  }
-  if (fused_fn) {
-    hipStream_t st = (hipStream_t)stream;
-    {
-      const hipError_t e0 = hipMemsetAsync(ws2 + kWsHeaderBytes, 0, 8 * (size_t)nblk, st);   // see the persistent path
-      if (e0 != hipSuccess) return gjx_fail_hip(e0, "gjx_ssm_filter(granules)");
-    }
-    float* lw_alt = (float*)cum;                     // the prefix-sum buffer is free on this path: second log-weight buffer
-    auto lw_of = [&](int t) { return ((T - 1 - t) & 1) ? lw_alt : logw; };   // the last step writes the caller's logw
-    auto part_of = [&](int t) { return (unsigned long long*)(ws1 + kWsHeaderBytes) + (size_t)(t & 1) * nblk; };
-    for (int t = 0; t < T; ++t) {
-      uint32_t kt[2], kp[2], kr[2], b[2];
-      host_threefry(k[0], k[1], 0u, (uint32_t)t, kt);
-      k[0] = kt[0]; k[1] = kt[1];
-      host_threefry(k[0], k[1], 0u, 0u, kp);
-      host_threefry(k[0], k[1], 0u, 1u, kr);
-      float* x_out = (t & 1) ? x_b : x_a;
-      const float* x_prev = (t & 1) ? x_a : x_b;
-      SsmArgs a;
-      a.A = m->A_dev; a.H = m->H_dev; a.y = ys_dev + (size_t)t * m->dy; a.q = m->q; a.r = m->r; a.q0 = m->q0; a.dy = m->dy; a.t = t;
-      a.key = key2{kp[0], kp[1]}; a.K = K; a.offset = 0; a.prev_stride = K;
-      a.x_prev = t > 0 ? x_prev : nullptr; a.anc = nullptr; a.x_out = x_out; a.logw = lw_of(t);
-      a.partials = part_of(t); a.ticket = (unsigned*)ws1; a.lse = t == T - 1 ? lse_steps + 4 * (size_t)t : nullptr;
-      a.log_k_total = (float)log((double)K);
-      a.m_prev = nullptr; a.m_out = nullptr; a.y_prev = nullptr; a.n_moves = 0; a.move_scale = 0.0f; a.accepted = nullptr; a.x_moved = nullptr;
-      if (t == 0) {
-        const int rc = rng_mode == GJX_RNG_JAX32 ? launch_ssm<GJX_RNG_JAX32>(a, m->dx, (int)nblk, st) : launch_ssm<GJX_RNG_FLAT>(a, m->dx, (int)nblk, st);
-        if (rc) return gjx_fail(GJX_EUNSUPPORTED, "gjx_ssm_filter: dx must be one of 1,2,4,8,16,32");
-        GJX_CHECK_LAUNCH("gjx_ssm_filter(step 0)");
-        continue;
-      }
-      host_threefry(kr[0], kr[1], 0u, 0u, b);
-      SsmFusedArgs f;
-      f.s = a;
-      f.logw_prev = lw_of(t - 1);
-      f.partials_prev = (const float*)part_of(t - 1);
-      f.n_partials_prev = (int)nblk;
-      f.lse_prev_out = lse_steps + 4 * (size_t)(t - 1);
-      f.log_k_total_prev = (float)log((double)K);
-      f.u = (double)((b[0] ^ b[1]) >> 9) / 8388608.0;
-      f.ancestors = t == T - 1 ? ancestors : nullptr;
-      f.agg = (unsigned long long*)(ws2 + kWsHeaderBytes);
-      f.ctrl = (unsigned*)ws2 + 8;
-      f.timeline = nullptr;   // debug: phase stamps of the middle step (profiles/microbench/ssm_timeline.py)
-      if (t == T / 2) f.timeline = gjx::debug_timeline(64 * (size_t)nblk);
-      void* args[] = {&f};
-      const hipError_t e = hipLaunchKernel(fused_fn, dim3((unsigned)nblk), dim3(256), args, 0, st);
-      if (e != hipSuccess) return gjx_fail_hip(e, "gjx_ssm_filter(fused step)");
-    }
-    return GJX_OK;
-  }
   for (int t = 0; t < T; ++t) {
-    uint32_t kt[2], kp[2], kr[2], b[2];
-    host_threefry(k[0], k[1], 0u, (uint32_t)t, kt);
-    k[0] = kt[0]; k[1] = kt[1];
-    host_threefry(k[0], k[1], 0u, 0u, kp);
-    host_threefry(k[0], k[1], 0u, 1u, kr);
     float* x_out = (t & 1) ? x_b : x_a;
     const float* x_prev = (t & 1) ? x_a : x_b;
     float* lse = lse_steps + 4 * (size_t)t;
     if (t > 0) {
-      host_threefry(kr[0], kr[1], 0u, 0u, b);
-      const double u = (double)((b[0] ^ b[1]) >> 9) / 8388608.0;
       // the previous step left its per-block LSE partials in ws1; the prefix-sum prologue reduces them and
       // block 0 writes the finished record of step t-1
-      const int rc = tiled ? gjx_resample_indices_tiled(logw, K, u, K, ancestors, cum, nullptr, nullptr, ws2, need, stream)
-                           : gjx_resample_indices(logw, K, 2, (const float*)(ws1 + 256), (int32_t)((K + 255) / 256), u, K, ancestors, cum, bt,
+      const int rc = tiled ? gjx_resample_indices_tiled(logw, K, us[t], K, ancestors, cum, nullptr, nullptr, ws2, need, stream)
+                           : gjx_resample_indices(logw, K, 2, (const float*)(ws1 + 256), (int32_t)((K + 255) / 256), us[t], K, ancestors, cum, bt,
                                                   lse - 4, K, ws2, need, stream);
       if (rc) return rc;
     }
     // tile-scaled scheme: the resampler does not touch the LSE partials, every step finishes its own record
-    const int rc = gjx_ssm_step(m, kp[0], kp[1], rng_mode, t, K, 0, t > 0 ? x_prev : nullptr, K, t > 0 ? ancestors : nullptr,
+    const int rc = gjx_ssm_step(m, keys[2 * t], keys[2 * t + 1], rng_mode, t, K, 0, t > 0 ? x_prev : nullptr, K, t > 0 ? ancestors : nullptr,
                                 ys_dev + (size_t)t * m->dy, x_out, logw, (tiled || t == T - 1) ? lse : nullptr, K, ws1, need, stream);
     if (rc) return rc;
   }
@@ -1597,28 +1369,17 @@ extern "C" int gjx_ssm_filter_sharded(const gjx_ssm* m, uint32_t key0, uint32_t 
   const size_t need = gjx_workspace_bytes(GJX_OP_SSM, K);
   if (!workspace || workspace_bytes < need + 64) return gjx_fail(GJX_EWORKSPACE, "gjx_ssm_filter_sharded: workspace too small (OP_SSM + 64)");
   float* lse_local = (float*)((char*)workspace + need);
-  uint32_t k[2] = {key0, key1};
-  uint32_t kt[2], kp[2], kr[2], b[2];
-  host_threefry(k[0], k[1], 0u, 0u, kt);       // k_0 = fold_in(key, 0)
-  k[0] = kt[0]; k[1] = kt[1];
+  std::vector<uint32_t> keys;
+  std::vector<double> us;
+  pf_step_keys(key0, key1, T, keys, us);
   for (int t = 0; t < T; ++t) {
-    host_threefry(k[0], k[1], 0u, 0u, kp);
-    rc = gjx_ssm_step(m, kp[0], kp[1], rng_mode, t, K, particle_offset, t > 0 ? x_b : nullptr, K, nullptr,
+    rc = gjx_ssm_step(m, keys[2 * t], keys[2 * t + 1], rng_mode, t, K, particle_offset, t > 0 ? x_b : nullptr, K, nullptr,
                       ys_dev + (size_t)t * m->dy, x_a, logw, lse_local, N_total, workspace, need, stream);
     if (rc) return rc;
     float* rec = lse_steps + 4 * (size_t)t;
-    if (t + 1 < T) {
-      // step t+1's key gives the comb offset of the resampling that precedes it; the exchange also yields the
-      // global LSE record of step t
-      host_threefry(k[0], k[1], 0u, (uint32_t)(t + 1), kt);
-      k[0] = kt[0]; k[1] = kt[1];
-      host_threefry(k[0], k[1], 0u, 1u, kr);
-      host_threefry(kr[0], kr[1], 0u, 0u, b);
-      const double u = (double)((b[0] ^ b[1]) >> 9) / 8388608.0;
-      rc = gjx_shard_resample_step(ctx, logw, lse_local, x_a, K, x_b, K, u, rec, nullptr, stream);
-    } else {
-      rc = gjx_shard_global_lse(ctx, lse_local, rec, stream);
-    }
+    // the resampling in front of step t+1 takes that step's comb offset; the exchange also yields the global LSE record of step t
+    rc = t + 1 < T ? gjx_shard_resample_step(ctx, logw, lse_local, x_a, K, x_b, K, us[t + 1], rec, nullptr, stream)
+                   : gjx_shard_global_lse(ctx, lse_local, rec, stream);
     if (rc) return rc;
   }
   return GJX_OK;

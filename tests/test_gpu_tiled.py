@@ -128,33 +128,29 @@ def test_tiled_dead_collection_sets_status(K_):
 
 @pytest.mark.parametrize("K", [10_000, 1 << 16, (1 << 18) - 77])
 def test_tiled_filter_one_launch_equals_step_by_step(K_, K):
-    """k_ssm_persistent<TILED> (one rendezvous per step, everything in registers / LDS) == gjx_ssm_step +
-    gjx_resample_indices_tiled issued from the host: same ancestors, hence bit-identical particles and weights."""
+    """The one-launch filter (tile-scaled: k_pf_persistent; global maximum: k_ssm_persistent) == gjx_ssm_step + the
+    multi-launch resampler issued from the host: same ancestors, hence bit-identical particles and weights."""
     from genjax_amd.inference.pf import BootstrapFilter, LinearGaussianSSM
     s = cf.ssm_problem(T=24)
     for rng in (A.RNG_FLAT, A.RNG_JAX32):
-        bf = BootstrapFilter(LinearGaussianSSM(s["A"], s["q"], s["r"]), K, rng_mode=rng, weights="tile_scaled")
-        a = bf.run(core.key(7), s["y"])                    # (the kernel on the shared skeleton, k_pf_persistent, by default ...)
-        os.environ["GJX_PF"] = "0"                         # ... and k_ssm_persistent<TILED>, the one-slot-per-lane kernel
-        try:
-            a0 = bf.run(core.key(7), s["y"])
-        finally:
-            del os.environ["GJX_PF"]
-        np.testing.assert_array_equal(_np(a["x"]), _np(a0["x"]))
-        np.testing.assert_array_equal(_np(a["logw"]), _np(a0["logw"]))
-        b = bf.run(core.key(7), s["y"], step_by_step=True)
-        assert not a["degenerate"]
-        np.testing.assert_array_equal(_np(a["x"]), _np(b["x"]))
-        np.testing.assert_array_equal(_np(a["logw"]), _np(b["logw"]))
-        np.testing.assert_allclose(_np(a["increments"]), _np(b["increments"]), rtol=2e-6, atol=2e-6)   # LSE finish order differs
-        # the multi-launch fallback of the native loop (no co-resident grid): the same again
-        os.environ["GJX_SSM_PERSISTENT"] = "0"
-        try:
-            c = bf.run(core.key(7), s["y"])
-        finally:
-            del os.environ["GJX_SSM_PERSISTENT"]
-        np.testing.assert_array_equal(_np(a["x"]), _np(c["x"]))
-        np.testing.assert_allclose(_np(a["increments"]), _np(c["increments"]), rtol=2e-6, atol=2e-6)
+        for weights in ("tile_scaled", "global_max"):
+            bf = BootstrapFilter(LinearGaussianSSM(s["A"], s["q"], s["r"]), K, rng_mode=rng, weights=weights)
+            a = bf.run(core.key(7), s["y"])
+            b = bf.run(core.key(7), s["y"], step_by_step=True)
+            assert not a["degenerate"]
+            np.testing.assert_array_equal(_np(a["x"]), _np(b["x"]))
+            np.testing.assert_array_equal(_np(a["logw"]), _np(b["logw"]))
+            np.testing.assert_allclose(_np(a["increments"]), _np(b["increments"]), rtol=2e-6, atol=2e-6)   # LSE finish order differs
+            # the native loop without the one-launch filter (tile-scaled: the multi-launch loop; global maximum:
+            # k_ssm_fused_step, one launch per step): the same again
+            os.environ["GJX_SSM_PERSISTENT"] = "0"
+            try:
+                c = bf.run(core.key(7), s["y"])
+            finally:
+                del os.environ["GJX_SSM_PERSISTENT"]
+            np.testing.assert_array_equal(_np(b["x"]), _np(c["x"]))
+            np.testing.assert_array_equal(_np(b["logw"]), _np(c["logw"]))
+            np.testing.assert_allclose(_np(b["increments"]), _np(c["increments"]), rtol=2e-6, atol=2e-6)
         # and the flag the host layer passes when it repeats a timed-out run (GJX_WEIGHTS_PLAIN_LAUNCHES: per call, no environment)
         import torch
         ys_d = torch.as_tensor(np.asarray(s["y"], np.float32)).cuda()
@@ -167,14 +163,12 @@ def test_tiled_filter_one_launch_equals_step_by_step(K_, K):
             assert K_.workspace_status(pl["_status_ws"], raise_on_error=False) == 0
 
 
-@pytest.mark.parametrize("K,force", [((1 << 18) + 1, False), (300_001, False), (1 << 19, False), (1 << 20, False), (1, True), (2049, True), (70_001, True)])
-def test_any_size_one_launch_filter_equals_step_by_step(K_, K, force, monkeypatch):
-    """k_pf_persistent (the one-launch filter beyond one slot per lane: several quantisation tiles per block, any K; what
-    config 4's 2^19 particles per GPU run; GJX_PF=1 takes it at small sizes too) == the host-driven loop, bit for bit,
-    on both stream layouts and with an observation matrix."""
+@pytest.mark.parametrize("K", [(1 << 18) + 1, 300_001, 1 << 19, 1 << 20, 1, 2049, 70_001])
+def test_any_size_one_launch_filter_equals_step_by_step(K_, K):
+    """k_pf_persistent (the tile-scaled one-launch filter at any K: one quantisation tile per block while the grid is
+    co-resident, several beyond; what config 4's 2^19 particles per GPU run) == the host-driven loop, bit for bit, on both
+    stream layouts and with an observation matrix."""
     from genjax_amd.inference.pf import BootstrapFilter, LinearGaussianSSM
-    if force:
-        monkeypatch.setenv("GJX_PF", "1")
     for rng, dx in ((A.RNG_FLAT, 8), (A.RNG_JAX32, 4)):
         s = cf.ssm_problem(dx=dx, T=9)
         rs = np.random.default_rng(K % 97)
