@@ -5,50 +5,24 @@
 // source of ONE straight-line kernel — every site's kind, mode, event size, parameter forms, table offsets and slot
 // numbers are literals, every element loop is unrolled, particle values live in registers, tables in LDS, and whatever
 // depends on the float table only (log-softmax / running CDF of constant logits, log and reciprocal of constant
-// scales) is computed once per block in the prologue instead of once per particle — compiled with hipRTC for gfx950
-// and cached per structure (in memory, and as a code object next to this library so that a build step can pre-populate
-// the cache; the table VALUES are run-time data, so new observations do not recompile).  The site interpreter
+// scales) is computed once per block in the prologue instead of once per particle.  This file holds the emitters only; gjx_jit.hip
+// compiles their source with hipRTC for gfx950, caches it per structure, loads and launches it.  The site interpreter
 // (k_run_generic) stays as the fallback for what the emitter does not cover (dirichlet sites, vector values wider than
 // 32 that later sites read, non-table categorical logits).
-#include <dlfcn.h>
-#include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
-#include <hip/hiprtc.h>
-#include <unistd.h>
 #include <stdarg.h>
 #include <string.h>
-#include <sys/stat.h>
 
-#include <atomic>
-#include <chrono>
 #include <functional>
-#include <map>
-#include <unordered_map>
-#include <mutex>
 #include <string>
 #include <vector>
 
+#include "gjx_codegen.h"
 #include "gjx_device.h"
 #include "gjx_host.h"
-#include "gjx_pfcore.h"
+
+using gjx_codegen::Generated;
 
 namespace {
-
-const char* kDeviceHeader =
-#include "build/gjx_device_h.inc"
-    ;
-const char* kApiHeader =
-#include "build/gjx_h.inc"
-    ;
-const char* kScanHeader =
-#include "build/gjx_scan_h.inc"
-    ;
-const char* kTileHeader =
-#include "build/gjx_tile_h.inc"
-    ;
-const char* kPfCoreHeader =
-#include "build/gjx_pfcore_h.inc"
-    ;
 
 // ---------------------------------------------------------------------------------------------------------
 // emitter
@@ -189,11 +163,11 @@ struct Plan {
   int n_hoist = 0;
   bool pf = false;
   std::vector<char> skip;           // sites emit_body leaves out (the assess form of a step program: inputs and proposal sites)
-  // plate flavour "wide" (ppt code | 512): a block is 16 waves that ALL hold the same 64 x PPT particles; the instances of a plate
+  // plate flavour "wide" (gjx::kRunWide of the ppt code, gjx_host.h): a block is 16 waves that ALL hold the same 64 x PPT particles; the instances of a plate
   // are dealt to the waves in contiguous chunks and the waves' partial sums meet in LDS (fixed order: deterministic), so a program
   // with few particles and many instances still fills the SIMDs.  Sites outside plates are computed by every wave, stored by wave 0
   bool wide = false;
-  int lpp = 1;                      // wide flavour: lanes per particle (ppt code | 1024: 4, | 2048: 16) — FEW particles over very many instances:
+  int lpp = 1;                      // wide flavour: lanes per particle (gjx::kRunLanes4 / kRunLanes16 of the ppt code) — FEW particles over very many instances:
                                     // a wave holds 64 / lpp particles, the instances are dealt to 16 x lpp chunks (wave, lane within the particle)
   int find(int kind, int off, int n, int len = 0, int dim = 0) {
     for (auto& c : comps) if (c.kind == kind && c.off == off && c.n == n && c.len == len && c.dim == dim) return c.at;
@@ -1223,9 +1197,9 @@ struct GenCtx {
   Plan pl;
 };
 
-void plan_program(const gjx_program* prog_in, int ppt_code, GenCtx& g, bool allow_roll = true) {
-  const int ppt = ppt_code & 255;
-  const bool mfma = ((ppt_code >> 8) & 1) != 0 && ppt == 1;
+void plan_program(const gjx_program* prog_in, const gjx::RunVariant& v, GenCtx& g, bool allow_roll = true) {
+  const int ppt = v.ppt;
+  const bool mfma = v.mfma;
   Roll& roll = g.roll;
   Plan& pl = g.pl;
   g_expr_prog = prog_in;
@@ -1241,8 +1215,8 @@ void plan_program(const gjx_program* prog_in, int ppt_code, GenCtx& g, bool allo
   pl.prog = prog;
   pl.ppt = ppt;
   pl.mfma = mfma;
-  pl.wide = (ppt_code & 512) != 0 && px.any && !mfma;
-  pl.lpp = pl.wide ? ((ppt_code & 2048) ? 16 : ((ppt_code & 1024) ? 4 : 1)) : 1;
+  pl.wide = v.wide && px.any;
+  pl.lpp = pl.wide ? v.lpp : 1;
   pl.seq_rows = !px.any && !roll.ok && !mfma && !getenv("GJX_GEN_NO_SEQ_ROWS");      // (generate_pf clears it: its rows move with the step)
   pl.tab_lds = mfma || (prog->n_tab <= kMaxLdsTab && !getenv("GJX_GEN_TAB_GLOBAL"));   // (the variable: profiling variant, part of the cache key)
   if (roll.ok) {
@@ -1395,10 +1369,13 @@ void emit_companions(Emit& o, Plan& pl) {
   }
 }
 
-std::string generate(const gjx_program* prog_in, int ppt_code) {
-  const int ppt = ppt_code & 255;
+Generated generate(const gjx_program* prog_in, int ppt_code) {
+  Generated out;
+  gjx::RunVariant v;
+  if (!gjx::decode(ppt_code, &v)) return out;
+  const int ppt = v.ppt;
   GenCtx g;
-  plan_program(prog_in, ppt_code, g);
+  plan_program(prog_in, v, g);
   Plan& pl = g.pl;
   const gjx_program* prog = pl.prog;
   const bool mfma = pl.mfma;
@@ -1557,9 +1534,12 @@ std::string generate(const gjx_program* prog_in, int ppt_code) {
           "    a.st_tag = (unsigned long long)((s.epoch + (unsigned)t) %% 15u) + 1ull;\n    a.st_rtag = (unsigned long long)((s.epoch + (unsigned)t - 1u) %% 15u) + 1ull;\n"
           "    gjx_step_<true>(a);\n  }\n}\n");
   }
-  // LDS bytes the kernel needs, as a trailing comment the host parses back (keeps one source of truth)
-  o.f("// LDS_FLOATS %d\n// BT %d\n", mfma ? 0 : (pl.tab_lds ? prog->n_tab : 0) + pl.comp_floats, BT);
-  return o.s;
+  // LDS floats the kernel needs and its block size: what the launcher gets, and a trailing comment for the reader (part of the hashed source)
+  out.lds_floats = mfma ? 0 : (pl.tab_lds ? prog->n_tab : 0) + pl.comp_floats;
+  out.block = BT;
+  o.f("// LDS_FLOATS %d\n// BT %d\n", out.lds_floats, out.block);
+  out.src = std::move(o.s);
+  return out;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1590,7 +1570,7 @@ bool discrete_kind(int k) {
   return is_categorical(k) || k == GJX_FLIP || k == GJX_BERNOULLI_LOGITS || k == GJX_POISSON || k == GJX_GEOMETRIC || k == GJX_NEGATIVE_BINOMIAL;
 }
 
-// may the filter kernel of this step program carry a rejuvenation move (generate_pf, | 512)?  The move re-scores the PREVIOUS step —
+// may the filter kernel of this step program carry a rejuvenation move (generate_pf, gjx::kFilterMoves)?  The move re-scores the PREVIOUS step —
 // the same sites under the previous step's table — at candidate values of its latent choices: every own (non-INPUT) site with rows
 // must be one the next step reads (the latents ARE the carry), no plates, at least one continuous carry row
 bool pf_moves_supported(const gjx_program* p) {
@@ -1606,18 +1586,21 @@ bool pf_moves_supported(const gjx_program* p) {
   return cont > 0 && own_rows == n_in && p->n_slots == 2 * n_in;      // a periodic step: as many carry rows out as in
 }
 
-// spl_code: tiles per block | 256 for the flavour that runs on a collection sharded over peer-mapped windows (gjx_peer.hip)
-//           | 1024 multinomial resampling by sorted uniforms instead of the systematic comb (pf_core's MULTI flavour)
-//           | 512 with a rejuvenation move behind every resampling (GenPfArgs::n_moves random-walk Metropolis steps per particle)
-std::string generate_pf(const gjx_program* prog_in, int spl_code) {
-  if (!pf_supported(prog_in)) return "";
-  const int spl = spl_code & 255;
-  const bool sharded = (spl_code & 256) != 0;
-  const bool moves = (spl_code & 512) != 0;
-  const bool multi = (spl_code & 1024) != 0;         // multinomial resampling by sorted uniforms (pf_core<..., MULTI>)
-  if (moves && !pf_moves_supported(prog_in)) return "";
+// spl_code (gjx::FilterVariant, gjx_host.h): tiles per block | kFilterSharded for the flavour that runs on a collection sharded over
+//           peer-mapped windows (gjx_peer.hip)
+//           | kFilterMultinomial multinomial resampling by sorted uniforms instead of the systematic comb (pf_core's MULTI flavour)
+//           | kFilterMoves with a rejuvenation move behind every resampling (GenPfArgs::n_moves random-walk Metropolis steps per particle)
+Generated generate_pf(const gjx_program* prog_in, int spl_code) {
+  Generated out;
+  gjx::FilterVariant fv;
+  if (!pf_supported(prog_in) || !gjx::decode(spl_code, &fv)) return out;
+  const int spl = fv.tiles;
+  const bool sharded = fv.sharded, moves = fv.moves;
+  const bool multi = fv.multinomial;                 // multinomial resampling by sorted uniforms (pf_core<..., MULTI>)
+  if (moves && !pf_moves_supported(prog_in)) return out;
+  out.block = 1024;                                  // a tile of 1024 particles is one block of 16 waves
   GenCtx g;
-  plan_program(prog_in, 1, g, false);
+  plan_program(prog_in, gjx::RunVariant(), g, false);
   Plan& pl = g.pl;
   const gjx_program* prog = pl.prog;
   pl.pf = true;
@@ -1653,7 +1636,7 @@ std::string generate_pf(const gjx_program* prog_in, int spl_code) {
   }
   int n_input_sites = 0;
   while (n_input_sites < ns && prog->sites[n_input_sites].mode == GJX_MODE_INPUT) ++n_input_sites;
-  for (int j = n_input_sites; j < ns; ++j) if (prog->sites[j].mode == GJX_MODE_INPUT) return "";      // (INPUT sites come first: include/gjx.h)
+  for (int j = n_input_sites; j < ns; ++j) if (prog->sites[j].mode == GJX_MODE_INPUT) return out;      // (INPUT sites come first: include/gjx.h)
   const std::string inputs_s = emit_body(g, 0, n_input_sites);
   const std::string body_s = emit_body(g, n_input_sites, ns);
   int n_in = 0;
@@ -1669,7 +1652,7 @@ std::string generate_pf(const gjx_program* prog_in, int spl_code) {
     for (auto& sa : asites)
       if (sa.mode == GJX_MODE_SAMPLE && !(sa.flags & GJX_SITE_PROPOSAL)) sa.mode = GJX_MODE_OBS_PROPOSED;   // "given, in its registers"
     aprog.sites = asites.data();
-    plan_program(&aprog, 1, ga, false);
+    plan_program(&aprog, gjx::RunVariant(), ga, false);
     ga.pl.pf = true;
     ga.pl.seq_rows = false;
     ga.pl.tab_lds = true;
@@ -1706,7 +1689,7 @@ std::string generate_pf(const gjx_program* prog_in, int spl_code) {
   // ---- stage: the step's table and what derives from it, while the granules travel ----
   o.f("  GJX_DEV void stage(int t, int tid) {\n    cur_ = rows(t);\n    in_ = in_rows(t);\n    const float* __restrict__ tb_ = tbn_;\n"
       "    if (t + 1 < f.core.T) tbn_ = f.tabs[t + 1];\n"
-      "    for (int e = tid; e < NTAB; e += %d) tab_s[e] = tb_[e];\n#define TSRC(i) tb_[i]\n#define BT_ %d\n", 1024, 1024);
+      "    for (int e = tid; e < NTAB; e += %d) tab_s[e] = tb_[e];\n#define TSRC(i) tb_[i]\n#define BT_ %d\n", out.block, out.block);
   {
     Emit c;
     emit_companions(c, pl);
@@ -1716,7 +1699,7 @@ std::string generate_pf(const gjx_program* prog_in, int spl_code) {
   if (moves) {
     o.f("    if (t >= 2) {      // the rejuvenation move re-scores step t - 1: its table, the constants derived from it, its stored inputs\n"
         "      pp_ = rows(t - 1);\n      const float* __restrict__ tq_ = f.tabs[t - 1];\n"
-        "      for (int e = tid; e < NTAB; e += 1024) tabp_s[e] = tq_[e];\n#define TSRC(i) tq_[i]\n#define BT_ 1024\n#undef COMP\n#define COMP(i) tabp_s[NTAB + (i)]\n");
+        "      for (int e = tid; e < NTAB; e += %d) tabp_s[e] = tq_[e];\n#define TSRC(i) tq_[i]\n#define BT_ %d\n#undef COMP\n#define COMP(i) tabp_s[NTAB + (i)]\n", out.block, out.block);
     Emit c;
     emit_companions(c, ga.pl);
     o.s += c.s;
@@ -1830,14 +1813,15 @@ std::string generate_pf(const gjx_program* prog_in, int spl_code) {
   o.f("      store_scoped_u32(cx.chk_cur + j, cx.verify == 2 ? g_ ^ 1u : g_, sys_);\n    }\n");
   o.f("    (void)score;\n    return weight[0];\n  }\n};\n");
   // (one rank: agent-scope accesses and no verify mode compiled in; GJX_PF_SHARDED: the peer-sharded flavour decides both at run time)
-  o.f("extern \"C\" __global__ __launch_bounds__(1024) void gjx_gen_pf(GenPfArgs a) {\n"
+  o.f("extern \"C\" __global__ __launch_bounds__(%d) void gjx_gen_pf(GenPfArgs a) {\n"
       "  extern __shared__ __attribute__((aligned(16))) unsigned char pf_dyn[];\n"
       "  __shared__ __attribute__((aligned(16))) float tab_s[%d];\n"
       "  __shared__ __attribute__((aligned(16))) float tabp_s[%d];\n"
-      "  GenPfModel m(a, tab_s, tabp_s);\n  pf_core<GenPfModel, SPL, %s, %s>(a.core, m, pf_dyn);\n}\n", ((prog->n_tab + pl.comp_floats + 3) & ~3) + 4,
+      "  GenPfModel m(a, tab_s, tabp_s);\n  pf_core<GenPfModel, SPL, %s, %s>(a.core, m, pf_dyn);\n}\n", out.block, ((prog->n_tab + pl.comp_floats + 3) & ~3) + 4,
       moves ? ((prog->n_tab + ga.pl.comp_floats + 3) & ~3) + 4 : 4, sharded ? "2, 2" : "0, 0", multi ? "true" : "false");
-  o.f("// LDS_FLOATS 0\n");
-  return o.s;
+  o.f("// LDS_FLOATS %d\n", out.lds_floats);
+  out.src = std::move(o.s);
+  return out;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2341,9 +2325,10 @@ void hmc_emit_mfma_site(Emit& o, const gjx_program* prog, const HmcPlan& hp, int
 // cpl_code: lanes per chain of a kernel with loops (plates, rolled sites): 0 = 4; 16 or 64 for FEW chains over LONG loops — the loop's
 // trips are dealt to that many lanes, every lane keeps a copy of the chain's register state (hmc_gen_launch picks it by the number of
 // chains; matrix-core kernels have their own layout)
-std::string generate_hmc(const gjx_program* prog_in, int cpl_code = 0) {
+Generated generate_hmc(const gjx_program* prog_in, int cpl_code) {
+  Generated out;
   HmcPlan hp;
-  if (!hmc_plan(prog_in, &hp)) return "";
+  if (!hmc_plan(prog_in, &hp)) return out;
   g_expr_prog = prog_in;
   // the emitted program: the plan's site list (plates: every slot a register, a body site owns one instance's worth)
   gjx_program eprog = *prog_in;
@@ -2671,590 +2656,54 @@ std::string generate_hmc(const gjx_program* prog_in, int cpl_code = 0) {
   o.f("    }\n    if (a.score) a.score[i] = sc;\n    if (a.alpha) a.alpha[i] = al;\n    if (a.accepted) a.accepted[i] = acc ? 1.0f : 0.0f;\n  }\n");
   if (hp.prows) { o.f("  if (acc) {\n"); plate_rows("if (live) a.choices[src_] = wq_[idx_];"); o.f("  }\n"); }
   o.f("}\n");
-  o.f("// PROWS %d\n// CPLMAX %d\n// NOSTALE %d\n", hp.prows, cpl_max, hp.nostale ? 1 : 0);
-  o.f("// CPL %d\n// BT %d\n// LDS_FLOATS 0\n", cpl, hp.block);
-  return o.s;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// hipRTC (resolved at run time: the library must not need it when no program is ever generated)
-// ---------------------------------------------------------------------------------------------------------
-struct Rtc {
-  void* lib = nullptr;
-  decltype(&hiprtcCreateProgram) Create = nullptr;
-  decltype(&hiprtcCompileProgram) Compile = nullptr;
-  decltype(&hiprtcGetProgramLogSize) LogSize = nullptr;
-  decltype(&hiprtcGetProgramLog) Log = nullptr;
-  decltype(&hiprtcGetCodeSize) CodeSize = nullptr;
-  decltype(&hiprtcGetCode) Code = nullptr;
-  decltype(&hiprtcDestroyProgram) Destroy = nullptr;
-  bool ok = false;
-};
-
-Rtc& rtc() {
-  static Rtc r;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    const char* names[] = {getenv("GJX_HIPRTC"), "libhiprtc.so.7", "libhiprtc.so", "/opt/rocm/lib/libhiprtc.so"};
-    for (const char* n : names) {
-      if (!n) continue;
-      r.lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-      if (r.lib) break;
-    }
-    if (!r.lib) return;
-    bool ok = true;
-    auto sym = [&](const char* n) { void* p = dlsym(r.lib, n); ok = ok && p; return p; };
-    r.Create = (decltype(r.Create))sym("hiprtcCreateProgram");
-    r.Compile = (decltype(r.Compile))sym("hiprtcCompileProgram");
-    r.LogSize = (decltype(r.LogSize))sym("hiprtcGetProgramLogSize");
-    r.Log = (decltype(r.Log))sym("hiprtcGetProgramLog");
-    r.CodeSize = (decltype(r.CodeSize))sym("hiprtcGetCodeSize");
-    r.Code = (decltype(r.Code))sym("hiprtcGetCode");
-    r.Destroy = (decltype(r.Destroy))sym("hiprtcDestroyProgram");
-    r.ok = ok;
-  });
-  return r;
-}
-
-uint64_t fnv1a(const void* data, size_t n, uint64_t h = 1469598103934665603ull) {
-  const unsigned char* p = (const unsigned char*)data;
-  for (size_t i = 0; i < n; ++i) { h ^= p[i]; h *= 1099511628211ull; }
-  return h;
-}
-
-std::string cache_dir() {
-  if (const char* e = getenv("GJX_JIT_CACHE")) return e;
-  Dl_info info;
-  if (dladdr((void*)&fnv1a, &info) && info.dli_fname) {
-    std::string p = info.dli_fname;
-    const size_t k = p.rfind('/');
-    return (k == std::string::npos ? std::string(".") : p.substr(0, k)) + "/jit_cache";
-  }
-  return "/tmp/gjx_jit_cache";
-}
-
-struct Compiled {
-  std::vector<char> code;   // code object
-  int lds_floats = 0;
-  int cpl = 1, block = 256; // generated HMC kernels: lanes per chain, threads per block
-  int prows = 0;            // generated HMC kernels: workspace rows (selected sites inside plates), x 4 x n floats
-  int cpl_max = 1;          // generated HMC kernels: the most lanes per chain the program's loops can use
-  int nostale = 0;          // generated HMC kernels, LDS-state flavour without room for the first gradient: no stale-carry mode
-  std::string error;        // non-empty: this structure cannot be generated / compiled
-};
-
-std::mutex g_mu;
-std::map<uint64_t, Compiled> g_compiled;                                 // by structure key
-// gjx_jit_stats: kernels compiled by hipRTC in this process, code objects taken from the on-disk cache, time spent compiling (us)
-std::atomic<int64_t> g_rtc_compiles{0}, g_disk_hits{0}, g_rtc_us{0};
-std::map<std::pair<uint64_t, int>, std::pair<hipModule_t, hipFunction_t>> g_loaded;   // by (key, device)
-
-// per-program analysis cached under gjx_program.uid (0 = no caching): the site-list hash, the emitter's verdict and the
-// register footprint that decides PPT — each of them a walk over the whole site list
-struct ProgMeta { bool roll_pref; uint64_t sites_hash; int supported; int slots; };   // supported / slots: -1 = not computed yet
-std::mutex g_meta_mu;
-std::unordered_map<int32_t, ProgMeta> g_meta;
-
-// the site list AND the expression blocks its GJX_P_EXPR parameters name (node lists are structure: gjx.h)
-uint64_t sites_hash_uncached(const gjx_program* p) {
-  uint64_t h = fnv1a(p->sites, sizeof(gjx_site) * (size_t)p->n_sites);
-  if (p->tab)
-    for (int j = 0; j < p->n_sites; ++j)
-      for (int k = 0; k < GJX_MAX_PARAMS; ++k) {
-        const gjx_param& q = p->sites[j].p[k];
-        if (p->sites[j].mode != GJX_MODE_INPUT && q.op == GJX_P_EXPR && q.off >= 0 && q.n > 0 && q.off + GJX_EXPR_NODE_FLOATS * q.n <= p->n_tab)
-          h = fnv1a(p->tab + q.off, sizeof(float) * GJX_EXPR_NODE_FLOATS * (size_t)q.n, h);
-      }
-  return h | 1ull;
-}
-
-ProgMeta* meta_of(const gjx_program* p) {      // call with g_meta_mu held; nullptr when the program has no uid
-  if (p->uid == 0) return nullptr;
-  ProgMeta& m = g_meta[p->uid];
-  if (m.sites_hash == 0 || m.roll_pref != want_roll()) m = ProgMeta{want_roll(), sites_hash_uncached(p), -1, -1};
-  return &m;
-}
-
-uint64_t sites_hash(const gjx_program* p) {
-  std::lock_guard<std::mutex> lock(g_meta_mu);
-  if (ProgMeta* m = meta_of(p)) return m->sites_hash;
-  return sites_hash_uncached(p);
-}
-
-bool supported(const gjx_program* p) {
-  std::lock_guard<std::mutex> lock(g_meta_mu);
-  ProgMeta* m = meta_of(p);
-  if (!m) return supported_uncached(p);
-  if (m->supported < 0) m->supported = supported_uncached(p) ? 1 : 0;
-  return m->supported == 1;
-}
-
-// values a lane keeps in registers: all slots, or two steps' worth (+ the pre-Scan slots) when the program is rolled
-int register_slots(const gjx_program* p) {
-  std::lock_guard<std::mutex> lock(g_meta_mu);
-  ProgMeta* m = meta_of(p);
-  if (m && m->slots >= 0) return m->slots;
-  int slots = p->n_slots;
-  const PlateXf px = plate_program(p);
-  if (px.any) slots = px.n_regs;
-  else if (want_roll() || !supported_sites(p->sites, p->n_sites, p->n_slots, p)) {
-    const Roll r = detect_roll(p);
-    if (r.ok) slots = r.n_pre + 2 * r.S;
-  }
-  if (m) m->slots = slots;
-  return slots;
-}
-
-uint64_t structure_key(const gjx_program* p, int ppt, int flavour = 0) {   // flavour 0: propagate+reweight kernel, 1: HMC kernel
-  uint64_t h = sites_hash(p);
-  if (flavour == 1) {   // the HMC emitter's data-dependent choice (hmc_fold_ok reads the observations): part of the kernel's identity
-    HmcPlan hp;
-    if (hmc_plan(p, &hp)) h = fnv1a(hp.fold.data(), hp.fold.size(), h);
-  }
-  const int32_t extra[8] = {p->n_sites, p->n_slots, p->n_tab, p->rng_mode, ppt, want_roll() ? 1 : 0, flavour,
-                            (getenv("GJX_GEN_MFMA_DEBUG") ? atoi(getenv("GJX_GEN_MFMA_DEBUG")) : 0) ^
-                                (getenv("GJX_HMC_GEN_BT") ? atoi(getenv("GJX_HMC_GEN_BT")) << 8 : 0) ^ (getenv("GJX_HMC_GEN_NO_MFMA") ? 1 << 20 : 0) ^
-                                (getenv("GJX_HMC_GEN_DEBUG") ? atoi(getenv("GJX_HMC_GEN_DEBUG")) << 21 : 0) ^ (getenv("GJX_GEN_TAB_GLOBAL") ? 1 << 24 : 0) ^
-                                (getenv("GJX_GEN_NO_HOIST") ? 1 << 25 : 0) ^ (getenv("GJX_GEN_NO_FUSE") ? 1 << 26 : 0) ^ (getenv("GJX_GEN_NO_EARLY_STORE") ? 1 << 27 : 0) ^
-                                (getenv("GJX_GEN_NO_SEQ_ROWS") ? 1 << 28 : 0) ^ (getenv("GJX_JIT_FP_CONTRACT") ? 1 << 29 : 0) ^ (getenv("GJX_GEN_WAVES_PER_EU") ? atoi(getenv("GJX_GEN_WAVES_PER_EU")) << 12 : 0)};
-  h = fnv1a(extra, sizeof(extra), h);
-  static const uint64_t header_hash = fnv1a(kDeviceHeader, strlen(kDeviceHeader));   // a new device header invalidates the caches
-  return h ^ header_hash ^ (0x9E3779B97F4A7C15ull * GJX_ABI_VERSION);
-}
-
-const Compiled& compile(const gjx_program* prog, int ppt, int flavour = 0) {
-  const uint64_t key = structure_key(prog, ppt, flavour);
-  auto it = g_compiled.find(key);
-  if (it != g_compiled.end()) return it->second;
-  Compiled& c = g_compiled[key];
-  const std::string src = flavour == 1 ? generate_hmc(prog, ppt) : (flavour == 2 ? generate_pf(prog, ppt) : generate(prog, ppt));
-  if (src.empty()) { c.error = "codegen: program outside the emitter's coverage"; return c; }
-  const size_t m = src.rfind("// LDS_FLOATS ");
-  c.lds_floats = atoi(src.c_str() + m + 14);
-  const size_t mc = src.rfind("// CPL ");
-  if (mc != std::string::npos) c.cpl = atoi(src.c_str() + mc + 7);
-  const size_t mb = src.rfind("// BT ");
-  if (mb != std::string::npos) c.block = atoi(src.c_str() + mb + 6);
-  const size_t mp = src.rfind("// PROWS ");
-  if (mp != std::string::npos) c.prows = atoi(src.c_str() + mp + 9);
-  const size_t mx = src.rfind("// CPLMAX ");
-  if (mx != std::string::npos) c.cpl_max = atoi(src.c_str() + mx + 10);
-  const size_t mn = src.rfind("// NOSTALE ");
-  if (mn != std::string::npos) c.nostale = atoi(src.c_str() + mn + 11);
-  if ((size_t)c.lds_floats * 4 + 256 > 64 * 1024) { c.error = "the program's table does not fit the LDS budget"; return c; }
-  // the code object on disk is named by the SOURCE it was compiled from (and the headers): a changed emitter or header
-  // can never pick up a stale file
-  char name[64];
-  // generated kernels are compiled WITHOUT implicit fused multiply-adds (the explicit fmaf of the emitters and of gjx_device.h stay):
-  // the same site then rounds the same way in every kernel it is compiled into — the filter kernel with one particle per lane and
-  // gjx_gen with four gave a student-t draw that differed in the last bit — at no measurable cost (mixture kernel 31.6 -> 31.9 us,
-  // filter steps unchanged); GJX_JIT_FP_CONTRACT=fast restores the compiler's default for experiments
-  // — for the propagate and filter kernels; the HMC kernels (one kernel per program: nothing to agree with) keep the default, which is
-  // worth 13 - 25 % on gradient sweeps written without explicit fmaf
-  const bool no_contract = flavour != 1 && !(getenv("GJX_JIT_FP_CONTRACT") && !strcmp(getenv("GJX_JIT_FP_CONTRACT"), "fast"));
-  snprintf(name, sizeof(name), "%016llx", (unsigned long long)((no_contract ? 0x5bd1e995ull : 0ull) ^ fnv1a(src.data(), src.size()) ^ fnv1a(kDeviceHeader, strlen(kDeviceHeader)) ^ fnv1a(kApiHeader, strlen(kApiHeader)) ^
-                                                               fnv1a(kScanHeader, strlen(kScanHeader)) ^ (fnv1a(kTileHeader, strlen(kTileHeader)) << 1) ^
-                                                               (flavour == 2 ? fnv1a(kPfCoreHeader, strlen(kPfCoreHeader)) << 2 : 0ull)));
-  const std::string dir = cache_dir(), path = dir + "/" + name + ".hsaco";
-  if (!getenv("GJX_JIT_NO_DISK")) {
-    if (FILE* f = fopen(path.c_str(), "rb")) {
-      fseek(f, 0, SEEK_END);
-      const long n = ftell(f);
-      fseek(f, 0, SEEK_SET);
-      c.code.resize((size_t)n);
-      const size_t got = fread(c.code.data(), 1, (size_t)n, f);
-      fclose(f);
-      if (got == (size_t)n && n > 0) { g_disk_hits++; return c; }
-      c.code.clear();
-    }
-  }
-  if (getenv("GJX_JIT_DUMP")) {
-    if (FILE* f = fopen((std::string(getenv("GJX_JIT_DUMP")) + "/" + name + ".hip").c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
-  }
-  Rtc& r = rtc();
-  if (!r.ok) { c.error = "hipRTC is not available (libhiprtc.so)"; return c; }
-  hiprtcProgram p;
-  const char* hn[] = {"gjx_device.h", "../../include/gjx.h", "gjx_scan.h", "gjx_tile.h", "gjx_pfcore.h"};
-  const char* hs[] = {kDeviceHeader, kApiHeader, kScanHeader, kTileHeader, kPfCoreHeader};
-  if (r.Create(&p, src.c_str(), flavour == 1 ? "gjx_hmc_gen.hip" : (flavour == 2 ? "gjx_gen_pf.hip" : "gjx_gen.hip"), 5, hs, hn) != HIPRTC_SUCCESS) { c.error = "hiprtcCreateProgram failed"; return c; }
-  // (offline clang takes -mllvm -amdgpu-mfma-vgpr-form=1, which would keep matrix-core results out of the AGPRs; this hipRTC's LLVM
-  // does not know the option, so the generated kernels pay 16 v_accvgpr_read per tile: about 3 %)
-  const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
-  const auto t_rtc = std::chrono::steady_clock::now();
-  const hiprtcResult rc = r.Compile(p, no_contract ? 4 : 3, opts);
-  g_rtc_compiles++;
-  g_rtc_us += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_rtc).count();
-  if (rc != HIPRTC_SUCCESS) {
-    size_t ls = 0;
-    r.LogSize(p, &ls);
-    std::string log(ls, 0);
-    if (ls) r.Log(p, &log[0]);
-    c.error = "hipRTC: " + log.substr(0, 1500);
-    r.Destroy(&p);
-    return c;
-  }
-  size_t cs = 0;
-  r.CodeSize(p, &cs);
-  c.code.resize(cs);
-  r.Code(p, c.code.data());
-  r.Destroy(&p);
-  if (!getenv("GJX_JIT_NO_DISK")) {
-    mkdir(dir.c_str(), 0755);
-    const std::string tmp = path + ".tmp" + std::to_string((long)getpid());
-    if (FILE* f = fopen(tmp.c_str(), "wb")) {
-      fwrite(c.code.data(), 1, c.code.size(), f);
-      fclose(f);
-      rename(tmp.c_str(), path.c_str());
-    }
-  }
-  return c;
+  out.prows = hp.prows; out.cpl_max = cpl_max; out.nostale = hp.nostale ? 1 : 0;
+  out.cpl = cpl; out.block = hp.block;
+  o.f("// PROWS %d\n// CPLMAX %d\n// NOSTALE %d\n", out.prows, out.cpl_max, out.nostale);
+  o.f("// CPL %d\n// BT %d\n// LDS_FLOATS %d\n", out.cpl, out.block, out.lds_floats);
+  out.src = std::move(o.s);
+  return out;
 }
 
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------
-// interface used by gjx_run.hip
+// what gjx_jit.hip sees of the emitters (gjx_codegen.h): everything above is local to this file
 // ---------------------------------------------------------------------------------------------------------
-extern "C" int gjx_jit_stats(int64_t* out4) {
-  if (!out4) return GJX_EINVAL;
-  out4[0] = g_rtc_compiles.load();
-  out4[1] = g_disk_hits.load();
-  out4[2] = g_rtc_us.load();
-  { std::lock_guard<std::mutex> lock(g_mu); out4[3] = (int64_t)g_compiled.size(); }
-  return GJX_OK;
-}
+namespace gjx_codegen {
 
-namespace gjx {
+Generated generate(const gjx_program* prog, int ppt_code) { return ::generate(prog, ppt_code); }
+Generated generate_pf(const gjx_program* step, int spl_code) { return ::generate_pf(step, spl_code); }
+Generated generate_hmc(const gjx_program* prog, int cpl_code) { return ::generate_hmc(prog, cpl_code); }
+bool supported_uncached(const gjx_program* p) { return ::supported_uncached(p); }
+bool pf_supported(const gjx_program* p) { return ::pf_supported(p); }
+bool pf_moves_supported(const gjx_program* p) { return ::pf_moves_supported(p); }
+bool has_mfma_site(const gjx_program* p) { return ::has_mfma_site(p); }
+bool want_roll() { return ::want_roll(); }
 
-int gen_pick_ppt(const gjx_program* prog, int64_t K, bool prefer4) {
-  const int slots = register_slots(prog);
-  int ppt = slots <= 6 ? 4 : (slots <= 24 ? 2 : 1);
-  if (prefer4 && slots <= 40) ppt = 4;     // a block-tile of 1024 particles = one quantisation tile (tile totals, GJX_RUN_LEAVE_TILES)
-  // a big affine site goes to the matrix cores: one particle per lane, whole waves (code = ppt | 256: see generate())
-  if (K % 256 == 0 && !getenv("GJX_GEN_PPT") && has_mfma_site(prog)) return 1 | 256;
-  // a long plate: the instances dealt to the 16 waves of a block (code = ppt | 512), unless the particles alone fill the machine
-  // many times over (then the plain form's single pass per particle has less overhead); GJX_GEN_WIDE = 0 / 1 forces the choice
-  {
-    int longest = 0;
-    for (int j = 0; j < prog->n_sites; ++j) if (prog->sites[j].plate && prog->sites[j].plate_n > longest) longest = prog->sites[j].plate_n;
-    const char* e = getenv("GJX_GEN_WIDE");
-    // (measured, vmapped mixture: N = 4096 x K = 2^17 — 256 plain blocks, one wave per SIMD — 4.1x faster wide; N = 1024 x K = 2^20 —
-    // 2048 plain blocks — 8 % slower wide: the plain form wins once the particles alone give every SIMD four waves)
-    const bool want = e ? atoi(e) != 0 : (longest >= 64 && K / (256 * (int64_t)ppt) < 1024);
-    if (want && longest >= 16 && !prefer4) {
-      int wp = slots <= 4 ? 2 : 1;
-      if (const char* pe = getenv("GJX_GEN_PPT")) { const int q = atoi(pe); if (q == 1 || q == 2) wp = q; }
-      while (wp > 1 && K % wp != 0) wp >>= 1;
-      // few particles, very many instances: 4 or 16 lanes per particle (| 1024, | 2048) until the launch has two blocks per CU
-      // (measured, N = 2^16 x K = 2^12: one lane per particle, 64 blocks, 5.36 ms; 4 lanes, 256 blocks, 1.58 ms; 16 lanes, 1024 blocks, 1.28 ms)
-      int lpp = 1;
-      while (lpp < 16 && (K * lpp) / (64 * (int64_t)wp) < 512 && longest >= 16 * (lpp * 4) * 16 && K % (64 * wp / (lpp * 4)) == 0) lpp *= 4;
-      if (const char* le = getenv("GJX_GEN_LPP")) { const int q = atoi(le); if (q == 1 || q == 4 || q == 16) lpp = q; }
-      return wp | 512 | (lpp == 4 ? 1024 : (lpp == 16 ? 2048 : 0));
-    }
+// values a lane of gjx_gen keeps in registers: all slots, or two steps' worth (+ the pre-Scan slots) when the program is rolled
+int register_slots_uncached(const gjx_program* p) {
+  const PlateXf px = plate_program(p);
+  if (px.any) return px.n_regs;
+  if (want_roll() || !supported_sites(p->sites, p->n_sites, p->n_slots, p)) {
+    const Roll r = detect_roll(p);
+    if (r.ok) return r.n_pre + 2 * r.S;
   }
-  if (const char* e = getenv("GJX_GEN_PPT")) ppt = atoi(e);
-  if (ppt != 1 && ppt != 2 && ppt != 4) ppt = 1;
-  while (ppt > 1 && K % ppt != 0) ppt >>= 1;
-  return ppt;
+  return p->n_slots;
 }
 
-// 0: a generated kernel exists (compiled now if need be); otherwise the reason is in gjx_last_error
-int gen_available(const gjx_program* prog, int ppt) {
-  if (!supported(prog)) return gjx_fail(GJX_EUNSUPPORTED, "codegen: program outside the emitter's coverage");
-  std::lock_guard<std::mutex> lock(g_mu);
-  const Compiled& c = compile(prog, ppt);
-  if (!c.error.empty()) return gjx_fail(GJX_EUNSUPPORTED, c.error.c_str());
-  return GJX_OK;
-}
-
-int gen_launch(const gjx_program* prog, int ppt, const GenArgs& args, int grid, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-  hipFunction_t fn = nullptr;
-  int lds_floats = 0;
-  unsigned block = 256;
-  {
-    std::lock_guard<std::mutex> lock(g_mu);
-    const Compiled& c = compile(prog, ppt);
-    if (!c.error.empty()) return gjx_fail(GJX_EUNSUPPORTED, c.error.c_str());
-    lds_floats = c.lds_floats;
-    block = (unsigned)c.block;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return gjx_fail(GJX_EHIP, "codegen: no device");
-    const auto lk = std::make_pair(structure_key(prog, ppt), dev);
-    auto it = g_loaded.find(lk);
-    if (it == g_loaded.end()) {
-      hipModule_t mod;
-      hipError_t e = hipModuleLoadData(&mod, c.code.data());
-      if (e != hipSuccess) return gjx_fail_hip(e, "codegen: hipModuleLoadData");
-      e = hipModuleGetFunction(&fn, mod, "gjx_gen");
-      if (e != hipSuccess) return gjx_fail_hip(e, "codegen: hipModuleGetFunction");
-      g_loaded[lk] = std::make_pair(mod, fn);
-    } else {
-      fn = it->second.second;
-    }
-  }
-  GenArgs a = args;
-  size_t sz = sizeof(a);
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  hipError_t e;
-  if (ev0 && ev1) e = hipExtModuleLaunchKernel(fn, (uint32_t)grid * block, 1, 1, block, 1, 1, (size_t)lds_floats * 4, st, nullptr, config, ev0, ev1, 0);
-  else e = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, block, 1, 1, (unsigned)(lds_floats * 4), st, nullptr, config);
-  if (e != hipSuccess) return gjx_fail_hip(e, "codegen: launch");
-  return GJX_OK;
-}
-
-// ---- the steps kernel of a generated filter (gjx_scanfilter.hip): gjx_gen_steps of the module generated for `prog` ----
-// two programs run through one steps kernel only if they ARE one kernel: same structure key (sites, table size, stream layout)
-bool gen_same_kernel(const gjx_program* p, const gjx_program* q, int ppt) { return structure_key(p, ppt) == structure_key(q, ppt); }
-
-// blocks of gjx_gen_steps that are resident at the same time on the current device, or 0 (no such kernel / query failed)
-static int gen_steps_function(const gjx_program* prog, int ppt, hipFunction_t* fn_out, int* lds_floats) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  const Compiled& c = compile(prog, ppt);
-  if (!c.error.empty()) return gjx_fail(GJX_EUNSUPPORTED, c.error.c_str());
-  *lds_floats = c.lds_floats;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return gjx_fail(GJX_EHIP, "codegen: no device");
-  static std::map<std::pair<uint64_t, int>, hipFunction_t> steps_fn;
-  const auto lk = std::make_pair(structure_key(prog, ppt), dev);
-  auto sit = steps_fn.find(lk);
-  if (sit != steps_fn.end()) { *fn_out = sit->second; return *fn_out ? GJX_OK : GJX_EUNSUPPORTED; }
-  hipModule_t mod;
-  auto it = g_loaded.find(lk);
-  if (it == g_loaded.end()) {
-    hipFunction_t fn;
-    hipError_t e = hipModuleLoadData(&mod, c.code.data());
-    if (e != hipSuccess) return gjx_fail_hip(e, "codegen: hipModuleLoadData");
-    e = hipModuleGetFunction(&fn, mod, "gjx_gen");
-    if (e != hipSuccess) return gjx_fail_hip(e, "codegen: hipModuleGetFunction");
-    g_loaded[lk] = std::make_pair(mod, fn);
-  } else {
-    mod = it->second.first;
-  }
-  hipFunction_t sf = nullptr;
-  if (hipModuleGetFunction(&sf, mod, "gjx_gen_steps") != hipSuccess) { (void)hipGetLastError(); sf = nullptr; }
-  steps_fn[lk] = sf;
-  *fn_out = sf;
-  return sf ? GJX_OK : GJX_EUNSUPPORTED;
-}
-
-int gen_steps_resident_blocks(const gjx_program* prog, int ppt) {
-  hipFunction_t fn = nullptr;
-  int lds_floats = 0;
-  if (gen_steps_function(prog, ppt, &fn, &lds_floats) != GJX_OK) return 0;
-  int per_cu = 0, cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, (size_t)lds_floats * 4) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  if (gjx_plain_launches_forced()) return 0;
-  return (per_cu > 6 ? 6 : per_cu) * cus;        // (as gjx_coresident_blocks: answers above 6 per CU are not exact; tests override through gjx_filter_opts)
-}
-
-int gen_steps_launch(const gjx_program* prog, int ppt, const GenStepsArgs& args, int grid, hipStream_t st) {
-  hipFunction_t fn = nullptr;
-  int lds_floats = 0;
-  const int rc = gen_steps_function(prog, ppt, &fn, &lds_floats);
-  if (rc) return rc;
-  GenStepsArgs a = args;
-  size_t sz = sizeof(a);
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 256, 1, 1, (unsigned)(lds_floats * 4), st, nullptr, config);
-  if (e != hipSuccess) return gjx_fail_hip(e, "codegen: launch (steps kernel)");
-  return GJX_OK;
-}
-
-// ---- generated filter kernels (gjx_scanfilter.hip, gjx_peer.hip): gjx_gen_pf of the module generated for a step program ----
-bool gen_pf_supported(const gjx_program* p) { return pf_supported(p); }
-bool gen_pf_moves_supported(const gjx_program* p) { return pf_moves_supported(p); }
-// two step programs run as steps of one launch only if they ARE one kernel
-bool gen_pf_same_kernel(const gjx_program* p, const gjx_program* q) { return structure_key(p, 1, 2) == structure_key(q, 1, 2); }
-
-static int gen_pf_function(const gjx_program* prog, int spl, hipFunction_t* fn_out) {
-  std::lock_guard<std::mutex> lock(g_mu);
-  const Compiled& c = compile(prog, spl, 2);
-  if (!c.error.empty()) return gjx_fail(GJX_EUNSUPPORTED, c.error.c_str());
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return gjx_fail(GJX_EHIP, "codegen: no device");
-  const auto lk = std::make_pair(structure_key(prog, spl, 2), dev);
-  auto it = g_loaded.find(lk);
-  if (it == g_loaded.end()) {
-    hipModule_t mod;
-    hipFunction_t fn;
-    hipError_t e = hipModuleLoadData(&mod, c.code.data());
-    if (e != hipSuccess) return gjx_fail_hip(e, "codegen: hipModuleLoadData");
-    e = hipModuleGetFunction(&fn, mod, "gjx_gen_pf");
-    if (e != hipSuccess) return gjx_fail_hip(e, "codegen: hipModuleGetFunction");
-    // (static + dynamic LDS is above the 64 KB default once a run has more than ~2000 tiles)
-    if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess) (void)hipGetLastError();
-    g_loaded[lk] = std::make_pair(mod, fn);
-    *fn_out = fn;
-  } else {
-    *fn_out = it->second.second;
-  }
-  return GJX_OK;
-}
-
-int gen_pf_precompile(const gjx_program* prog, int spl) {
-  if (!pf_supported(prog)) return gjx_fail(GJX_EUNSUPPORTED, "codegen: step program outside the filter emitter's coverage");
-  std::lock_guard<std::mutex> lock(g_mu);
-  const Compiled& c = compile(prog, spl, 2);
-  if (!c.error.empty()) return gjx_fail(GJX_EUNSUPPORTED, c.error.c_str());
-  return GJX_OK;
-}
-
-// blocks of gjx_gen_pf<spl> that are resident at the same time on the current device, or 0
-int gen_pf_resident_blocks(const gjx_program* prog, int spl, size_t dyn_lds) {
-  if (gjx_plain_launches_forced()) return 0;
-  hipFunction_t fn = nullptr;
-  if (gen_pf_function(prog, spl, &fn) != GJX_OK) return 0;
-  int per_cu = 0, cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 1024, dyn_lds) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  return (per_cu > 2 ? 2 : per_cu) * cus;
-}
-
-int gen_pf_launch(const gjx_program* prog, int spl, const GenPfArgs& args, int grid, size_t dyn_lds, hipStream_t st) {
-  hipFunction_t fn = nullptr;
-  const int rc = gen_pf_function(prog, spl, &fn);
-  if (rc) return rc;
-  GenPfArgs a = args;
-  size_t sz = sizeof(a);
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  const hipError_t e = hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, 1024, 1, 1, (unsigned)dyn_lds, st, nullptr, config);
-  if (e != hipSuccess) return gjx_fail_hip(e, "codegen: launch (filter kernel)");
-  return GJX_OK;
-}
-
-// ---- generated HMC kernels (gjx_hmc.hip) ----
-int hmc_gen_available(const gjx_program* prog) {
+bool hmc_plan_fold(const gjx_program* p, std::vector<char>* fold) {
   HmcPlan hp;
-  if (!hmc_plan(prog, &hp)) return gjx_fail(GJX_EUNSUPPORTED, "codegen: program outside the HMC emitter's coverage");
-  std::lock_guard<std::mutex> lock(g_mu);
-  const Compiled& c = compile(prog, 0, 1);
-  if (!c.error.empty()) return gjx_fail(GJX_EUNSUPPORTED, c.error.c_str());
-  return GJX_OK;
+  if (!hmc_plan(p, &hp)) return false;
+  if (fold) *fold = hp.fold;
+  return true;
 }
 
-int hmc_gen_launch(const gjx_program* prog, const HmcGenArgs& args, hipStream_t st) {
-  hipFunction_t fn = nullptr;
-  int cpl = 1, block = 256;
-  {
-    std::lock_guard<std::mutex> lock(g_mu);
-    const Compiled& c0 = compile(prog, 0, 1);
-    if (!c0.error.empty()) return gjx_fail(GJX_EUNSUPPORTED, c0.error.c_str());
-    // few chains over long loops (the usual shape of HMC: hundreds of chains, thousands of data): more lanes per chain, until the
-    // launch has about two waves per SIMD (GJX_HMC_GEN_CPL forces 4, 16 or 64)
-    int variant = 0;
-    {
-      int want = 4;
-      while (want < c0.cpl_max && args.n * want < 131072) want *= 4;
-      if (const char* e = getenv("GJX_HMC_GEN_CPL")) want = atoi(e);
-      if ((want == 16 || want == 64) && want <= c0.cpl_max) variant = want;
-    }
-    const Compiled& c = variant ? compile(prog, variant, 1) : c0;
-    if (!c.error.empty()) return gjx_fail(GJX_EUNSUPPORTED, c.error.c_str());
-    cpl = c.cpl;
-    block = c.block;
-    if (c.nostale && args.stale) return gjx_fail(GJX_EUNSUPPORTED, "codegen: the LDS-state HMC kernel of this program has no room for the stale-carry compatibility mode");
-    if (c.prows > 0 && (!args.ws || args.ws_floats < 4 * (int64_t)c.prows * args.n))
-      return gjx_fail(GJX_EWORKSPACE, "gjx_hmc: workspace too small (selected sites inside a plate keep their trajectory state there)");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return gjx_fail(GJX_EHIP, "codegen: no device");
-    const auto lk = std::make_pair(structure_key(prog, variant, 1), dev);
-    auto it = g_loaded.find(lk);
-    if (it == g_loaded.end()) {
-      hipModule_t mod;
-      hipError_t e = hipModuleLoadData(&mod, c.code.data());
-      if (e != hipSuccess) return gjx_fail_hip(e, "codegen: hipModuleLoadData");
-      e = hipModuleGetFunction(&fn, mod, "gjx_hmc_gen");
-      if (e != hipSuccess) return gjx_fail_hip(e, "codegen: hipModuleGetFunction");
-      g_loaded[lk] = std::make_pair(mod, fn);
-    } else {
-      fn = it->second.second;
-    }
-  }
-  HmcGenArgs a = args;
-  size_t sz = sizeof(a);
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  const int64_t threads = a.n * cpl;
-  const unsigned grid = (unsigned)((threads + block - 1) / block);
-  const hipError_t e = hipModuleLaunchKernel(fn, grid, 1, 1, (unsigned)block, 1, 1, 0, st, nullptr, config);
-  if (e != hipSuccess) return gjx_fail_hip(e, "codegen: launch (HMC kernel)");
-  return GJX_OK;
-}
+const Knob kKnobs[] = {
+    {"GJX_GEN_ROLL", true},          {"GJX_GEN_NO_ROLL", false},         {"GJX_GEN_NO_MFMA", false},     {"GJX_GEN_MFMA_DEBUG", true},
+    {"GJX_GEN_NO_FUSE", false},      {"GJX_GEN_NO_EARLY_STORE", false},  {"GJX_GEN_NO_SEQ_ROWS", false}, {"GJX_GEN_TAB_GLOBAL", false},
+    {"GJX_GEN_WAVES_PER_EU", true},  {"GJX_GEN_NO_HOIST", false},        {"GJX_HMC_GEN_NO_FOLD", false}, {"GJX_HMC_GEN_NO_ROLL", false},
+    {"GJX_HMC_GEN_NO_PLATE_SEL", false}, {"GJX_HMC_GEN_NO_BIG", false},  {"GJX_HMC_GEN_NO_MFMA", false}, {"GJX_HMC_GEN_BT", true},
+};
+const int kNumKnobs = (int)(sizeof(kKnobs) / sizeof(kKnobs[0]));
 
-}  // namespace gjx
-
-// source of the generated HMC kernel of a program (GJX_EUNSUPPORTED when the emitter does not cover it)
-extern "C" int64_t gjx_program_hmc_source(const gjx_program* prog, char* out, int64_t cap) {
-  if (!prog || !prog->sites) return GJX_EINVAL;
-  const std::string src = generate_hmc(prog);
-  if (src.empty()) return gjx_fail(GJX_EUNSUPPORTED, "codegen: program outside the HMC emitter's coverage");
-  if (out && cap > 0) {
-    const size_t n = src.size() < (size_t)cap - 1 ? src.size() : (size_t)cap - 1;
-    memcpy(out, src.data(), n);
-    out[n] = 0;
-  }
-  return (int64_t)src.size();
-}
-
-// compile (or load from the disk cache) the generated HMC kernel of a program without launching it
-extern "C" int gjx_program_hmc_precompile(const gjx_program* prog) {
-  if (!prog || !prog->sites) return gjx_fail(GJX_EINVAL, "gjx_program_hmc_precompile: null program");
-  return gjx::hmc_gen_available(prog);
-}
-
-// the generated source of a program (debugging, tests, docs): returns the length, copies at most cap - 1 characters
-extern "C" int64_t gjx_program_source(const gjx_program* prog, int32_t ppt, char* out, int64_t cap) {
-  if (!prog || !prog->sites) return GJX_EINVAL;
-  if (!supported(prog)) return gjx_fail(GJX_EUNSUPPORTED, "codegen: program outside the emitter's coverage");
-  {
-    const int base = ppt & ~(1024 | 2048);
-    if ((base != 1 && base != 2 && base != 4 && base != (1 | 256) && base != (1 | 512) && base != (2 | 512)) || ((ppt & (1024 | 2048)) && !(base & 512)))
-      ppt = gjx::gen_pick_ppt(prog, 4);
-  }
-  const std::string src = generate(prog, ppt);
-  if (out && cap > 0) {
-    const size_t n = src.size() < (size_t)cap - 1 ? src.size() : (size_t)cap - 1;
-    memcpy(out, src.data(), n);
-    out[n] = 0;
-  }
-  return (int64_t)src.size();
-}
-
-// compile (or load from the disk cache) the kernel of a program without launching it — build steps pre-populate the
-// cache with this on machines without a GPU (hipRTC cross-compiles)
-extern "C" int gjx_program_precompile(const gjx_program* prog, int32_t ppt) {
-  if (!prog || !prog->sites) return gjx_fail(GJX_EINVAL, "gjx_program_precompile: null program");
-  const int wide_lanes = ppt & (1024 | 2048);
-  const int base = ppt & ~(1024 | 2048);
-  if ((base != 1 && base != 2 && base != 4 && base != (1 | 256) && base != (1 | 512) && base != (2 | 512)) || (wide_lanes && !(base & 512)) || wide_lanes == (1024 | 2048))
-    return gjx_fail(GJX_EINVAL, "gjx_program_precompile: ppt must be 1, 2, 4, 257 (1 | 256: big affine sites on the matrix cores) or 513 / 514 (| 512: the instances of a plate dealt to the 16 waves of a block; | 1024 / | 2048: and to 4 / 16 lanes per particle)");
-  return gjx::gen_available(prog, ppt);
-}
-
-// the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE of gjx_scan_filter): source, and compile without launch
-extern "C" int64_t gjx_program_filter_source(const gjx_program* step, int32_t tiles_per_block, char* out, int64_t cap) {
-  if (!step || !step->sites) return GJX_EINVAL;
-  const std::string src = generate_pf(step, tiles_per_block);
-  if (src.empty()) return gjx_fail(GJX_EUNSUPPORTED, "codegen: step program outside the filter emitter's coverage");
-  if (out && cap > 0) {
-    const size_t n = src.size() < (size_t)cap - 1 ? src.size() : (size_t)cap - 1;
-    memcpy(out, src.data(), n);
-    out[n] = 0;
-  }
-  return (int64_t)src.size();
-}
-
-extern "C" int gjx_program_filter_precompile(const gjx_program* step, int32_t tiles_per_block) {
-  if (!step || !step->sites) return gjx_fail(GJX_EINVAL, "gjx_program_filter_precompile: null program");
-  const int tpb = tiles_per_block & 255;
-  if ((tiles_per_block & ~(255 | 256 | 512 | 1024)) || (tpb != 1 && tpb != 2 && tpb != 4 && tpb != 8 && tpb != 16) || (tiles_per_block & (256 | 512 | 1024)) > 1024)
-    return gjx_fail(GJX_EINVAL, "gjx_program_filter_precompile: tiles_per_block must be 1, 2, 4, 8 or 16 (| 256: the flavour for sharded collections, | 512: with the rejuvenation move, | 1024: multinomial resampling by sorted uniforms, on its own)");
-  return gjx::gen_pf_precompile(step, tiles_per_block);
-}
+}  // namespace gjx_codegen

@@ -1,4 +1,4 @@
-// gjx_host.h — host-side helpers shared by the launchers (error reporting only; no state).
+// gjx_host.h — host-side helpers shared by the launchers (error reporting, the variant codes of the generated kernels; no state).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -33,14 +33,71 @@ struct gjx_plain_launch_scope {
 bool gjx_plain_launches_forced();
 
 namespace gjx {
+// ---- variant codes of the generated kernels: the integers of the C ABI (gjx_program_precompile, gjx_program_filter_precompile,
+//      genjax_amd/jit_manifest.py), decoded HERE and nowhere else ----
+// run kernel (gjx_gen): particles per lane | flavour bits
+enum : int {
+  kRunPptMask = 255,
+  kRunMfma = 256,       // big affine sites on the matrix cores: one particle per lane, whole waves
+  kRunWide = 512,       // a block of 16 waves shares 64 x ppt particles: the instances of its plates are dealt to the waves ...
+  kRunLanes4 = 1024,    // ... and to 4
+  kRunLanes16 = 2048,   // ... or 16 lanes per particle
+};
+struct RunVariant {
+  int ppt = 1;          // particles per lane
+  bool mfma = false, wide = false;
+  int lpp = 1;          // wide flavour: lanes per particle (1, 4, 16)
+  int particles_per_block() const { return (wide ? 64 / lpp : 256) * ppt; }
+};
+inline int encode(const RunVariant& v) {
+  return v.ppt | (v.mfma ? kRunMfma : 0) | (v.wide ? kRunWide : 0) | (v.lpp == 4 ? kRunLanes4 : (v.lpp == 16 ? kRunLanes16 : 0));
+}
+// false: not a kernel the emitter has (plain: ppt 1, 2, 4; matrix cores: ppt 1; wide: ppt 1, 2 with 1, 4 or 16 lanes per particle)
+inline bool decode(int code, RunVariant* v) {
+  RunVariant r;
+  r.ppt = code & kRunPptMask;
+  r.mfma = (code & kRunMfma) != 0;
+  r.wide = (code & kRunWide) != 0;
+  r.lpp = (code & kRunLanes16) ? 16 : ((code & kRunLanes4) ? 4 : 1);
+  const int max_ppt = r.mfma ? 1 : (r.wide ? 2 : 4);
+  if (code != encode(r) || (r.ppt != 1 && r.ppt != 2 && r.ppt != 4) || r.ppt > max_ppt || (r.mfma && r.wide) || (r.lpp > 1 && !r.wide)) return false;
+  *v = r;
+  return true;
+}
+// filter kernel (gjx_gen_pf): tiles per block | flavour bits
+enum : int {
+  kFilterTilesMask = 255,
+  kFilterSharded = 256,       // runs on a collection sharded over peer-mapped windows (gjx_peer.hip)
+  kFilterMoves = 512,         // a rejuvenation move behind every resampling
+  kFilterMultinomial = 1024,  // multinomial resampling by sorted uniforms instead of the systematic comb (not together with the move)
+};
+struct FilterVariant {
+  int tiles = 1;              // 1024-particle tiles per block: 1, 2, 4, 8, 16
+  bool sharded = false, moves = false, multinomial = false;
+};
+inline int encode(const FilterVariant& v) {
+  return v.tiles | (v.sharded ? kFilterSharded : 0) | (v.moves ? kFilterMoves : 0) | (v.multinomial ? kFilterMultinomial : 0);
+}
+inline bool decode(int code, FilterVariant* v) {
+  FilterVariant r;
+  r.tiles = code & kFilterTilesMask;
+  r.sharded = (code & kFilterSharded) != 0;
+  r.moves = (code & kFilterMoves) != 0;
+  r.multinomial = (code & kFilterMultinomial) != 0;
+  const int t = r.tiles;
+  if (code != encode(r) || (t != 1 && t != 2 && t != 4 && t != 8 && t != 16) || (r.moves && r.multinomial)) return false;
+  *v = r;
+  return true;
+}
+
 // phase-stamp buffer of the profiling scripts (gjx_debug_timeline): the registered device buffer if it holds `need` bytes
 unsigned long long* debug_timeline(size_t need);
 struct GenArgs;
-// per-program generated kernels (gjx_codegen.hip)
+// per-program generated kernels (emitted by gjx_codegen.hip, compiled / loaded / launched by gjx_jit.hip)
 int gen_pick_ppt(const gjx_program* prog, int64_t K, bool prefer4 = false);
 int gen_available(const gjx_program* prog, int ppt);
 int gen_launch(const gjx_program* prog, int ppt, const GenArgs& args, int grid, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
-// the steps kernel of a generated filter (gjx_gen_steps, gjx_codegen.hip): every step of a run in one launch
+// the steps kernel of a generated filter (gjx_gen_steps): every step of a run in one launch
 struct GenStepsArgs;
 bool gen_same_kernel(const gjx_program* p, const gjx_program* q, int ppt);
 int gen_steps_resident_blocks(const gjx_program* prog, int ppt);
@@ -49,7 +106,7 @@ int gen_steps_launch(const gjx_program* prog, int ppt, const GenStepsArgs& args,
 // 16 waves per 1024-particle tile, `spl` tiles per block
 struct GenPfArgs;
 bool gen_pf_supported(const gjx_program* p);
-bool gen_pf_moves_supported(const gjx_program* p);   // the kernel can carry the rejuvenation move (spl | 512)
+bool gen_pf_moves_supported(const gjx_program* p);   // the kernel can carry the rejuvenation move (FilterVariant::moves)
 bool gen_pf_same_kernel(const gjx_program* p, const gjx_program* q);
 int gen_pf_precompile(const gjx_program* prog, int spl);
 int gen_pf_resident_blocks(const gjx_program* prog, int spl, size_t dyn_lds);
@@ -57,7 +114,7 @@ int gen_pf_launch(const gjx_program* prog, int spl, const GenPfArgs& args, int g
 // n 8-byte words from HOST memory to device memory through kernel arguments (small per-run argument arrays: step keys, comb
 // offsets, table pointers): no host buffer has to outlive the call, unlike an asynchronous copy from pageable memory
 int upload_words(void* dst_dev, const void* src_host, size_t n_words, hipStream_t st);
-// per-program generated HMC kernels (gjx_codegen.hip)
+// per-program generated HMC kernels (gjx_codegen.hip, gjx_jit.hip)
 struct HmcGenArgs;
 int hmc_gen_available(const gjx_program* prog);
 int hmc_gen_launch(const gjx_program* prog, const HmcGenArgs& args, hipStream_t st);

@@ -357,7 +357,9 @@ static int scan_filter_peer_impl(gjx_peer_ctx* c, const gjx_program* steps, int3
   if (opts && opts->n_moves > 0) return gjx_fail(GJX_EUNSUPPORTED, "gjx_scan_filter_peer: the sharded filter kernel has no rejuvenation move (gjx_scan_filter on one GPU has)");
   if (fflags & ~(GJX_FILTER_MULTINOMIAL)) return gjx_fail(GJX_EUNSUPPORTED, "gjx_scan_filter_peer: of gjx_filter_opts.flags the sharded kernel takes GJX_FILTER_MULTINOMIAL only (it has one form)");
   const bool multinomial = (fflags & GJX_FILTER_MULTINOMIAL) != 0;
-  const int flavour = 256 | (multinomial ? 1024 : 0);
+  FilterVariant fv;
+  fv.sharded = true;
+  fv.multinomial = multinomial;
   if (!c || !steps || (!lse_steps && !prepare_only) || T < 2) return gjx_fail(GJX_EINVAL, "gjx_scan_filter_peer: bad argument (T >= 2)");
   if (!c->connected) return gjx_fail(GJX_EINVAL, "gjx_scan_filter_peer: the context is not connected (gjx_peer_ctx_connect)");
   auto input_rows = [](const gjx_program& p) {
@@ -384,7 +386,8 @@ static int scan_filter_peer_impl(gjx_peer_ctx* c, const gjx_program* steps, int3
   const int spls[5] = {1, 2, 4, 8, 16};
   for (int i = 0; i < 5 && !spl; ++i) {
     const int64_t g = ((int64_t)c->nt + spls[i] - 1) / spls[i];
-    int cap = gen_pf_resident_blocks(&steps[1], spls[i] | flavour, dyn);
+    fv.tiles = spls[i];
+    int cap = gen_pf_resident_blocks(&steps[1], encode(fv), dyn);
     if (cap <= 0) break;
     if (c->share > 1) cap /= c->share;               // ranks that share one device (dry runs): every rank's grid must be resident
     if (g <= cap && g * c->world <= kPfHostMaxTiles) { spl = spls[i]; grid = (int)g; }
@@ -445,7 +448,8 @@ static int scan_filter_peer_impl(gjx_peer_ctx* c, const gjx_program* steps, int3
   ga.rows_a = rows_a; ga.rows_b = rows_b; ga.rows_all = nullptr; ga.rows_step = 0;
   ga.in_row0_first = (int64_t)input_rows(steps[0]) * K;
   ga.in_row0 = (int64_t)input_rows(steps[1]) * K;
-  rc = gen_pf_launch(&steps[1], spl | flavour, ga, grid, dyn, st);
+  fv.tiles = spl;
+  rc = gen_pf_launch(&steps[1], encode(fv), ga, grid, dyn, st);
   if (rc) return rc;
   finfo.launches = 2; finfo.grid = grid; finfo.tiles_per_block = spl;
   if (info_out) *info_out = finfo;

@@ -135,8 +135,10 @@ static int scan_filter_impl(const gjx_program* steps, int32_t T, uint32_t key0, 
   const size_t wide_bytes = 256 + (16 * (size_t)kPfCorePad + 24) * (size_t)ntw + 8 * (size_t)ntw + 24 * (size_t)T + 64;
   if (room && T >= 2 && !(multinomial && n_moves > 0) && !(fflags & GJX_FILTER_NO_WIDE) && !no_fuse && ntw <= kPfHostMaxTiles && workspace_bytes >= wide_off + wide_bytes &&
       !gjx_plain_launches_forced() && steps[1].tab_dev && gen_pf_supported(&steps[1]) && (n_moves == 0 || gen_pf_moves_supported(&steps[1]))) {
-    // the kernel flavour: | 512 with the rejuvenation move, | 1024 multinomial resampling by sorted uniforms (pf_core's MULTI)
-    const int mv = (n_moves > 0 ? 512 : 0) | (multinomial ? 1024 : 0);
+    // the kernel flavour: with the rejuvenation move, or multinomial resampling by sorted uniforms (pf_core's MULTI)
+    FilterVariant fv;
+    fv.moves = n_moves > 0;
+    fv.multinomial = multinomial;
     bool same = true;
     for (int u = 2; u < T && same; ++u)
       same = steps[u].n_tab == steps[1].n_tab && steps[u].n_slots == steps[1].n_slots && input_rows(steps[u]) == input_rows(steps[1]) &&
@@ -149,7 +151,8 @@ static int scan_filter_impl(const gjx_program* steps, int32_t T, uint32_t key0, 
       const int64_t g = (ntw + spls[i] - 1) / spls[i];
       // (ask for the cheapest geometry first: a kernel is compiled — hipRTC, cached on disk — only for a geometry that could fit)
       if (g > 2 * 1024) continue;
-      const int cap = (opts && opts->coresident_blocks > 0) ? opts->coresident_blocks : gen_pf_resident_blocks(&steps[1], spls[i] | mv, dyn);
+      fv.tiles = spls[i];
+      const int cap = (opts && opts->coresident_blocks > 0) ? opts->coresident_blocks : gen_pf_resident_blocks(&steps[1], encode(fv), dyn);
       if (cap <= 0) break;                                   // no such kernel (compile failure: the reason is in gjx_last_error)
       if (g <= cap) { spl = spls[i]; grid = (int)g; }
     }
@@ -208,7 +211,8 @@ static int scan_filter_impl(const gjx_program* steps, int32_t T, uint32_t key0, 
         const hipError_t ez = hipMemsetAsync(ga.acc_total, 0, sizeof(unsigned long long), st0);
         if (ez != hipSuccess) return report(gjx_fail_hip(ez, "gjx_scan_filter(accept counter)"));
       }
-      rc = gen_pf_launch(&steps[1], spl | mv, ga, grid, dyn, st0);
+      fv.tiles = spl;
+      rc = gen_pf_launch(&steps[1], encode(fv), ga, grid, dyn, st0);
       if (rc == GJX_OK) {
         // the skeleton's status bits live in ITS control block: fold them into the word the caller reads
         hipLaunchKernelGGL(k_merge_status, dim3(1), dim3(64), 0, st0, (unsigned*)wa + 8, (unsigned*)ws_res + 8);

@@ -1,6 +1,7 @@
 """Manifest of the generated kernels a deployment precompiles.
 
-Generated kernels (csrc/gjx_codegen.hip) are compiled by hipRTC the first time a program structure is seen and cached
+Generated kernels (emitted by csrc/gjx_codegen.hip, compiled and launched by csrc/gjx_jit.hip) are compiled by hipRTC the
+first time a program structure is seen and cached
 on disk by the hash of their source (``csrc/jit_cache/`` next to the library).  A compile at run time costs 0.3 - 3 s and
 drops the GPU's clocks while it runs, so a build step walks THIS list — ``precompile_all()``, called by
 ``__graft_entry__.build()``; hipRTC cross-compiles for gfx950 without a GPU — and ``gjx_jit_stats`` (``kernels.jit_stats``)

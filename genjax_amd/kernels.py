@@ -106,15 +106,20 @@ def program_engine(prog: PackedProgram, device=None) -> int:
     return int(load().gjx_program_engine(C.byref(cp)))
 
 
+def _source(name: str, prog: PackedProgram, *code: int) -> str:
+    """a generated kernel's source from the export `name`: one call for the length, one for the text"""
+    fn, cp = getattr(load(), name), prog.c_program(None)
+    n = fn(C.byref(cp), *code, None, 0)
+    if n < 0:
+        check(int(n), name)
+    buf = C.create_string_buffer(int(n) + 1)
+    fn(C.byref(cp), *code, buf, int(n) + 1)
+    return buf.value.decode()
+
+
 def program_source(prog: PackedProgram, ppt: int = 0) -> str:
     """HIP source of the kernel gjx_codegen generates for this program (raises GjxError if the emitter does not cover it)."""
-    cp = prog.c_program(None)
-    n = load().gjx_program_source(C.byref(cp), int(ppt), None, 0)
-    if n < 0:
-        check(int(n), "gjx_program_source")
-    buf = C.create_string_buffer(int(n) + 1)
-    load().gjx_program_source(C.byref(cp), int(ppt), buf, int(n) + 1)
-    return buf.value.decode()
+    return _source("gjx_program_source", prog, int(ppt))
 
 
 def jit_stats() -> dict:
@@ -132,13 +137,7 @@ def program_precompile(prog: PackedProgram, ppt: int) -> None:
 
 def program_hmc_source(prog: PackedProgram) -> str:
     """HIP source of the HMC kernel gjx_codegen generates for this program (raises GjxError if the emitter does not cover it)."""
-    cp = prog.c_program(None)
-    n = load().gjx_program_hmc_source(C.byref(cp), None, 0)
-    if n < 0:
-        check(int(n), "gjx_program_hmc_source")
-    buf = C.create_string_buffer(int(n) + 1)
-    load().gjx_program_hmc_source(C.byref(cp), buf, int(n) + 1)
-    return buf.value.decode()
+    return _source("gjx_program_hmc_source", prog)
 
 
 def program_hmc_precompile(prog: PackedProgram) -> None:
@@ -150,13 +149,7 @@ def program_hmc_precompile(prog: PackedProgram) -> None:
 def program_filter_source(step: PackedProgram, tiles_per_block: int = 1) -> str:
     """HIP source of the FILTER kernel gjx_codegen generates for a step program (gjx_gen_pf: the step's sites as the model of the
     shared filter skeleton, csrc/gjx_pfcore.h); raises GjxError if the emitter does not cover it"""
-    cp = step.c_program(None)
-    n = load().gjx_program_filter_source(C.byref(cp), int(tiles_per_block), None, 0)
-    if n < 0:
-        check(int(n), "gjx_program_filter_source")
-    buf = C.create_string_buffer(int(n) + 1)
-    load().gjx_program_filter_source(C.byref(cp), int(tiles_per_block), buf, int(n) + 1)
-    return buf.value.decode()
+    return _source("gjx_program_filter_source", step, int(tiles_per_block))
 
 
 def program_filter_precompile(step: PackedProgram, tiles_per_block: int = 1) -> None:
