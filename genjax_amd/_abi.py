@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 # status
 OK, EINVAL, EUNSUPPORTED, EHIP, EWORKSPACE = 0, -1, -2, -3, -4
@@ -107,6 +107,11 @@ class GjxFilterOpts(C.Structure):
                 ("hmc_workspace", vp), ("hmc_workspace_bytes", C.c_size_t)]
 
 
+class GjxAdaptiveOpts(C.Structure):
+    """gjx_adaptive_opts (ABI 11): resampling only when ESS < ess_threshold * K"""
+    _fields_ = [("ess_threshold", f32), ("reserved", i32), ("logw_acc", vp), ("ess_steps", vp), ("resampled", vp)]
+
+
 class GjxFilterInfo(C.Structure):
     _fields_ = [("form", i32), ("launches", i32), ("grid", i32), ("tiles_per_block", i32)]
 
@@ -125,6 +130,7 @@ class GjxShardPlan(C.Structure):
                 ("seq", i64), ("reserved", i64), ("bounds", i64 * (MAX_RANKS + 1))]
 
 
+assert C.sizeof(GjxAdaptiveOpts) == 32 and C.sizeof(GjxFilterOpts) == 88
 assert C.sizeof(GjxParam) == 48 and C.sizeof(GjxSite) == 240 and C.sizeof(GjxShardPlan) == 8 * (12 + MAX_RANKS + 1)
 
 PP = C.POINTER(GjxProgram)
@@ -188,6 +194,9 @@ PROTOTYPES = {
                                       C.c_size_t, vp]),
     "gjx_scan_filter": (C.c_int, [vp, i32, u32, u32, i64, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]),
     "gjx_scan_filter_history": (C.c_int, [vp, i32, u32, u32, i64, vp, i32, vp, vp, vp, vp, C.c_size_t, vp, vp, vp]),
+    "gjx_scan_filter_adaptive": (C.c_int, [vp, i32, u32, u32, i64, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]),
+    "gjx_scan_filter_adaptive_history": (C.c_int, [vp, i32, u32, u32, i64, vp, i32, vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]),
+    "gjx_ess": (C.c_int, [vp, i64, vp, vp, C.c_size_t, vp]),
     "gjx_program_filter_source": (i64, [PP, i32, C.c_char_p, i64]),
     "gjx_program_filter_precompile": (C.c_int, [PP, i32]),
     "gjx_resample_indices_tiled": (C.c_int, [vp, i64, f64, i64, vp, vp, vp, vp, vp, C.c_size_t, vp]),

@@ -123,5 +123,18 @@ int launch_expand_planned(const uint64_t* cum, int64_t K, const gjx_shard_plan* 
                           int32_t* ancestors, int64_t anc_capacity, hipStream_t st);
 // maximum tile exponent, shifts and prefix of the shifted tile totals for the tile-scaled resampler (k_tiled_plan, gjx_ssm.hip):
 // P u64[nt + 1], sh i32[nt]
-int launch_tiled_plan(const uint64_t* S, const int32_t* E, int nt, uint64_t* P, int32_t* sh, unsigned* ctrl, hipStream_t st);
+// gate (or NULL): a device word; 0 means "the step does not resample" and the launch does nothing (gjx_scan_filter_adaptive)
+int launch_tiled_plan(const uint64_t* S, const int32_t* E, int nt, uint64_t* P, int32_t* sh, unsigned* ctrl, hipStream_t st,
+                      const int32_t* gate = nullptr);
+// gjx_resample_gather_tiled with every launch (tile totals, tile prefix, search) gated by the device word *gate: 0 -> identity ancestors,
+// the rows copied as they are, the log-weights, tile totals and status word untouched; gate == NULL: the ungated call (gjx_resample.hip)
+int resample_gather_tiled_gated(const float* logw, int64_t K, const uint64_t* tile_S, const int32_t* tile_E, int32_t lse_mode, const float* lse,
+                                int32_t n_partials, double u, const float* src, int64_t src_stride, int32_t rows, float* dst, int64_t dst_stride,
+                                int32_t* ancestors, float* lse_out, int64_t K_total, void* workspace, size_t workspace_bytes, void* stream,
+                                const int32_t* gate);
+// the fused launch of the adaptive filter (gjx_resample.hip, k_ess_tiles): W = fresh ? inc : W + inc in place (also stored to w_copy when
+// not NULL), {max, sum e, sum e^2} per 1024-particle tile, and the finishing block's record of the step: lse_rec[4] (lse_prev: the record
+// of the step before, read behind a skip), *ess_out, *decide_out = (ess < tau * K || tau >= 1).  fresh: a device word, or NULL = "yes"
+int launch_ess_accumulate(const float* inc, float* W, float* w_copy, int64_t K, const int32_t* fresh, float* lse_rec, const float* lse_prev,
+                          float* ess_out, int32_t* decide_out, float tau, void* workspace, size_t workspace_bytes, hipStream_t st);
 }  // namespace gjx

@@ -6,6 +6,9 @@
 // thresholds are one IEEE double multiply + truncation per output slot.  HBM traffic per
 // particle: pick 4 B read; cumsum 2x4 B read + 8 B write; search 4 B write (+ L2-resident
 // binary-search probes); gather 4 B read + 4 B write per row.
+#include <math.h>
+#include <string.h>
+
 #include "gjx_device.h"
 #include "gjx_host.h"
 #include "gjx_scan.h"
@@ -635,8 +638,11 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
 constexpr int kGatherTiledMaxTiles = 65536;
 
 // {S_b, E_b} of every tile from the log-weights (what k_tiled_quantise computes, without the cumulative array)
-__global__ __launch_bounds__(kTileQ) void k_tile_totals(const float* __restrict__ logw, int64_t K, uint64_t* S, int32_t* E) {
+// GATED (the adaptive filter, gjx_scan_filter_adaptive): *gate == 0 means "this step does not resample" — nothing is written
+template <bool GATED>
+__global__ __launch_bounds__(kTileQ) void k_tile_totals(const float* __restrict__ logw, int64_t K, uint64_t* S, int32_t* E, const int32_t* gate) {
   constexpr int NW = kTileQ / 64;
+  if (GATED && *gate == 0) return;
   __shared__ float fred[NW];
   __shared__ uint64_t wsum[NW];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -663,14 +669,15 @@ __global__ __launch_bounds__(kTileQ) void k_tile_totals(const float* __restrict_
 // PLANNED (more than 1024 tiles): the maximum exponent, the shifts and the prefix were computed ONCE by k_tiled_plan (one
 // small launch) and are read from memory — a block touches the nine prefix entries around its own index — instead of
 // every block reducing all nt granules again (O(nt^2) reads and 72 KB of LDS at nt = 4096).
-template <int ITEMS, bool PLANNED>
+// GATED: *gate == 0 -> identity ancestors (the rows, if any, are copied as they are); tile totals, plan and status word are not read
+template <int ITEMS, bool PLANNED, bool GATED>
 __global__ __launch_bounds__(256) void k_resample_gather_tiled(const float* __restrict__ x, int64_t K, const uint64_t* __restrict__ S,
                                                               const int32_t* __restrict__ E, const uint64_t* __restrict__ Pg,
                                                               const int32_t* __restrict__ shg, int lse_mode, const float* lse,
                                                               int n_partials, float* lse_out, float log_k_total, double u,
                                                               const float* __restrict__ src, int64_t src_stride, int rows,
                                                               float* __restrict__ dst, int64_t dst_stride, int32_t* ancestors,
-                                                              unsigned* ctrl, unsigned long long* timeline) {
+                                                              unsigned* ctrl, unsigned long long* timeline, const int32_t* gate) {
 #define GJX_STAMP(n) do { if (timeline && threadIdx.x == 0) timeline[blockIdx.x * 8 + (n)] = __builtin_amdgcn_s_memrealtime(); } while (0)
   GJX_STAMP(0);
   static_assert(ITEMS == 4, "a block consumes one quantisation tile: 256 lanes x 4 slots");
@@ -681,6 +688,10 @@ __global__ __launch_bounds__(256) void k_resample_gather_tiled(const float* __re
   __shared__ TiledSearchShared sh;
   const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * ITEMS;
   int32_t anc[ITEMS];
+  if (GATED && *gate == 0) {     // grid-uniform
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) anc[k] = (int32_t)((i0 + k < K) ? i0 + k : K - 1);
+  } else
   tiled_search_tile<PLANNED>(x, K, S, E, Pg, shg, nt, (int)blockIdx.x, Pl, Ebl, sh, lse_mode, lse, n_partials, lse_out, log_k_total, u, ctrl, timeline, anc);
   GJX_STAMP(4);
   // ---- children: rows of the ancestors, ITEMS consecutive slots per lane ----
@@ -752,6 +763,172 @@ int launch_expand_planned(const uint64_t* cum, int64_t K, const gjx_shard_plan* 
                      (int64_t)0, anc_capacity, ancestors, (const float*)nullptr, (int64_t)0, 0, (float*)nullptr, (int64_t)0,
                      range);
   GJX_CHECK_LAUNCH("gjx_shard_resample(expand)");
+  return GJX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Effective sample size, and the weight bookkeeping of the adaptive filter (gjx_scan_filter_adaptive) fused into it.
+// One block per 1024-particle tile (256 lanes x 4 particles): W = fresh ? inc : W + inc in place (ACC: 8 B read + 4 B written per
+// particle; !ACC, gjx_ess: 4 B read), tile maximum m_b, s1_b = sum exp(W - m_b), s2_b = sum exp(2 (W - m_b)) by the wave reductions
+// of this file.  A block publishes {m_b, s1_b} as one 8-byte and s2_b as one 4-byte agent-scope store, drains them and takes a
+// ticket — ONE atomic per block (k_count_flags, gjx_scanfilter.hip) —; the block that draws the last ticket combines the tiles:
+// M = max m_b, S1 = sum_b s1_b exp(m_b - M), S2 = sum_b s2_b exp(2 (m_b - M)), lane l summing tiles [l per, (l + 1) per) in order,
+// then the fixed-order wave sum and the four waves in order: a function of the weights and of K alone, never of a launch geometry.
+// It writes the LSE record of the step, ESS = S1^2 / S2 and the decision word the launches in front of the next step read.
+// Plain vector stores, no host in the loop.  NaN and -inf weights count as dead (fmaxf drops a NaN, its term is clamped to 0).
+// ------------------------------------------------------------------------------------------
+struct EssArgs {
+  const float* inc;            // ACC: the step's incremental log-weights
+  float* W;                    // the carried log-weights (!ACC: read only)
+  float* w_copy;               // ACC: W is stored here too when not NULL (the last step: the caller's logw)
+  int64_t K;
+  const int32_t* fresh;        // ACC: device word, != 0: the collection was resampled in front of this step (carried weights are 0); NULL: yes
+  unsigned long long* pm;      // [nt] {m_b, s1_b}
+  unsigned* p2;                // [nt] s2_b
+  unsigned* ticket;
+  float* out4;                 // !ACC: {M, S1, S2, ESS}
+  float* lse_rec;              // ACC: {M, S1, lse, lse - c}
+  const float* lse_prev;       // ACC: the record of the step before (c behind a skip), NULL at step 0
+  float log_k;
+  float* ess_out;
+  int32_t* decide_out;         // or NULL (the last step)
+  float tau_k;                 // ess_threshold * K
+  int always;                  // ess_threshold >= 1
+};
+
+template <bool ACC>
+__global__ __launch_bounds__(256) void k_ess_tiles(const EssArgs a) {
+  __shared__ float red[13];
+  __shared__ float fin[12];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int nt = (int)gridDim.x;
+  const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  // 16-byte accesses where the tile is whole and the buffers are aligned (kernel-uniform but for the last block)
+  const bool vec = i0 + 4 <= a.K && ((((uintptr_t)a.W) | (ACC ? ((uintptr_t)a.inc | (uintptr_t)a.w_copy) : 0)) & 15) == 0;
+  float w[4];
+  if (ACC) {
+    const bool fresh = a.fresh ? *a.fresh != 0 : true;     // grid-uniform
+    if (vec) {
+      const float4 q = *(const float4*)(a.inc + i0);
+      w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+      if (!fresh) {
+        const float4 c = *(const float4*)(a.W + i0);
+        w[0] += c.x; w[1] += c.y; w[2] += c.z; w[3] += c.w;
+      }
+      *(float4*)(a.W + i0) = make_float4(w[0], w[1], w[2], w[3]);
+      if (a.w_copy) *(float4*)(a.w_copy + i0) = make_float4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        w[k] = -INFINITY;
+        if (i0 + k < a.K) {
+          w[k] = a.inc[i0 + k];
+          if (!fresh) w[k] += a.W[i0 + k];
+          a.W[i0 + k] = w[k];
+          if (a.w_copy) a.w_copy[i0 + k] = w[k];
+        }
+      }
+    }
+  } else if (vec) {
+    const float4 c = *(const float4*)(a.W + i0);
+    w[0] = c.x; w[1] = c.y; w[2] = c.z; w[3] = c.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = (i0 + k < a.K) ? a.W[i0 + k] : -INFINITY;
+  }
+  const float wm = wave_max(fmaxf(fmaxf(w[0], w[1]), fmaxf(w[2], w[3])));
+  if (lane == 0) red[wid] = wm;
+  __syncthreads();
+  const float bm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float s1 = 0.0f, s2 = 0.0f;
+  if (bm > -INFINITY) {      // block-uniform
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float e = fast_exp(w[k] - bm);
+      e = e > 0.0f ? e : 0.0f;        // (a NaN weight: dead)
+      s1 += e;
+      s2 = fmaf(e, e, s2);
+    }
+  }
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
+  if (lane == 0) { red[4 + wid] = s1; red[8 + wid] = s2; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float b1 = (red[4] + red[5]) + (red[6] + red[7]), b2 = (red[8] + red[9]) + (red[10] + red[11]);
+    __hip_atomic_store(&a.pm[blockIdx.x], pack_f2(bm, b1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&a.p2[blockIdx.x], __float_as_uint(b2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    red[12] = (t == (unsigned)(nt - 1)) ? 1.0f : 0.0f;
+  }
+  __syncthreads();
+  if (red[12] == 0.0f) return;
+  // ---- the finishing block: every tile's partials with agent-scope loads ----
+  float M = -INFINITY;
+  for (int b = threadIdx.x; b < nt; b += 256)
+    M = fmaxf(M, __uint_as_float((unsigned)__hip_atomic_load(&a.pm[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+  M = wave_max(M);
+  if (lane == 0) fin[wid] = M;
+  __syncthreads();
+  M = fmaxf(fmaxf(fin[0], fin[1]), fmaxf(fin[2], fin[3]));
+  float S1 = 0.0f, S2 = 0.0f;
+  if (M > -INFINITY) {
+    const int per = (nt + 255) >> 8;
+    const int b0 = threadIdx.x * per, b1 = b0 + per < nt ? b0 + per : nt;
+    for (int b = b0; b < b1; ++b) {
+      const unsigned long long v = __hip_atomic_load(&a.pm[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const float t2 = __uint_as_float(__hip_atomic_load(&a.p2[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+      const float f = fast_exp(__uint_as_float((unsigned)v) - M);      // (a dead tile: exp(-inf) = 0 against sums that are 0)
+      S1 = fmaf(__uint_as_float((unsigned)(v >> 32)), f, S1);
+      S2 = fmaf(t2, f * f, S2);
+    }
+  }
+  S1 = wave_sum(S1);
+  S2 = wave_sum(S2);
+  if (lane == 0) { fin[4 + wid] = S1; fin[8 + wid] = S2; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    S1 = (fin[4] + fin[5]) + (fin[6] + fin[7]);
+    S2 = (fin[8] + fin[9]) + (fin[10] + fin[11]);
+    const bool live = M > -INFINITY && S2 > 0.0f;
+    const float ess = live ? S1 * S1 / S2 : 0.0f;
+    if (!ACC) { a.out4[0] = M; a.out4[1] = S1; a.out4[2] = S2; a.out4[3] = ess; }
+    if (ACC) {
+      const bool fresh = a.fresh ? *a.fresh != 0 : true;
+      const float ls = logf(S1);
+      const float l = live ? M + ls : -INFINITY;
+      // lse(W_t) - c_t: behind a skip c_t = lse(W_{t-1}); the difference is formed from the maxima and the sums separately (two
+      // numbers of the size of log-ML would cancel to a step's increment otherwise)
+      float d = l - a.log_k;
+      if (!fresh && a.lse_prev) d = live ? (M - a.lse_prev[0]) + (ls - logf(a.lse_prev[1])) : -INFINITY;
+      a.lse_rec[0] = M; a.lse_rec[1] = S1; a.lse_rec[2] = l; a.lse_rec[3] = d;
+      a.ess_out[0] = ess;
+      if (a.decide_out) a.decide_out[0] = (a.always || ess < a.tau_k) ? 1 : 0;
+    }
+    __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// workspace: [256 B control: word 0 the ticket][pm u64 nt][p2 u32 nt]
+static int ess_workspace(void* workspace, size_t workspace_bytes, int64_t nt, EssArgs& a) {
+  if (!workspace || workspace_bytes < kWsHeaderBytes + 12 * (size_t)nt) return -1;
+  a.ticket = (unsigned*)workspace;
+  a.pm = (unsigned long long*)((char*)workspace + kWsHeaderBytes);
+  a.p2 = (unsigned*)(a.pm + nt);
+  return 0;
+}
+
+int launch_ess_accumulate(const float* inc, float* W, float* w_copy, int64_t K, const int32_t* fresh, float* lse_rec, const float* lse_prev,
+                          float* ess_out, int32_t* decide_out, float tau, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  const int64_t nt = (K + kTileQ - 1) / kTileQ;
+  EssArgs a;
+  memset(&a, 0, sizeof(a));
+  if (ess_workspace(workspace, workspace_bytes, nt, a)) return gjx_fail(GJX_EWORKSPACE, "gjx_scan_filter_adaptive: workspace too small");
+  a.inc = inc; a.W = W; a.w_copy = w_copy; a.K = K; a.fresh = fresh; a.lse_rec = lse_rec; a.lse_prev = lse_prev;
+  a.log_k = (float)log((double)K); a.ess_out = ess_out; a.decide_out = decide_out; a.tau_k = tau * (float)K; a.always = tau >= 1.0f;
+  hipLaunchKernelGGL(k_ess_tiles<true>, dim3((unsigned)nt), dim3(256), 0, st, a);
+  GJX_CHECK_LAUNCH("gjx_scan_filter_adaptive(weights + ESS)");
   return GJX_OK;
 }
 
@@ -905,10 +1082,11 @@ extern "C" int gjx_resample_gather(const float* x, int64_t K, int32_t is_log, co
   return GJX_OK;
 }
 
-extern "C" int gjx_resample_gather_tiled(const float* logw, int64_t K, const uint64_t* tile_S, const int32_t* tile_E, int32_t lse_mode,
-                                         const float* lse, int32_t n_partials, double u, const float* src, int64_t src_stride,
-                                         int32_t rows, float* dst, int64_t dst_stride, int32_t* ancestors, float* lse_out,
-                                         int64_t K_total, void* workspace, size_t workspace_bytes, void* stream) {
+// gjx_resample_gather_tiled, and (gate != NULL) its gated form: every launch reads the device word *gate first (gjx_host.h)
+int gjx::resample_gather_tiled_gated(const float* logw, int64_t K, const uint64_t* tile_S, const int32_t* tile_E, int32_t lse_mode,
+                                     const float* lse, int32_t n_partials, double u, const float* src, int64_t src_stride,
+                                     int32_t rows, float* dst, int64_t dst_stride, int32_t* ancestors, float* lse_out,
+                                     int64_t K_total, void* workspace, size_t workspace_bytes, void* stream, const int32_t* gate) {
   if (!logw || K <= 0 || !(u >= 0.0 && u < 1.0) || rows < 0 || (rows > 0 && (!src || !dst)) || K > 0x7fffffffLL ||
       (lse_mode != 0 && lse_mode != 2) || (lse_mode == 2 && (!lse || n_partials <= 0)) || ((tile_S == nullptr) != (tile_E == nullptr)))
     return gjx_fail(GJX_EINVAL, "gjx_resample_gather_tiled: bad argument");
@@ -921,7 +1099,8 @@ extern "C" int gjx_resample_gather_tiled(const float* logw, int64_t K, const uin
   if (!tile_S) {   // the producer left no tile totals: one small launch over the log-weights
     uint64_t* S = (uint64_t*)((char*)workspace + kWsHeaderBytes);
     int32_t* E = (int32_t*)(S + nt);
-    hipLaunchKernelGGL(k_tile_totals, dim3((unsigned)nt), dim3(kTileQ), 0, st, logw, K, S, E);
+    if (gate) hipLaunchKernelGGL(k_tile_totals<true>, dim3((unsigned)nt), dim3(kTileQ), 0, st, logw, K, S, E, gate);
+    else hipLaunchKernelGGL(k_tile_totals<false>, dim3((unsigned)nt), dim3(kTileQ), 0, st, logw, K, S, E, (const int32_t*)nullptr);
     GJX_CHECK_LAUNCH("gjx_resample_gather_tiled/totals");
     tile_S = S; tile_E = E;
   }
@@ -933,19 +1112,31 @@ extern "C" int gjx_resample_gather_tiled(const float* logw, int64_t K, const uin
     Pg = (uint64_t*)(((uintptr_t)Pg + 15) & ~(uintptr_t)15);
     int32_t* shg = (int32_t*)(Pg + nt + 1);
     if ((char*)(shg + nt) > (char*)workspace + workspace_bytes) return gjx_fail(GJX_EWORKSPACE, "gjx_resample_gather_tiled: workspace too small");
-    const int rc = gjx::launch_tiled_plan(tile_S, tile_E, (int)nt, Pg, shg, ctrl, st);
+    const int rc = gjx::launch_tiled_plan(tile_S, tile_E, (int)nt, Pg, shg, ctrl, st, gate);
     if (rc) return rc;
-    hipLaunchKernelGGL((k_resample_gather_tiled<4, true>), dim3((unsigned)nt), dim3(256), 0, st, logw, K, tile_S, tile_E, (const uint64_t*)Pg,
-                       (const int32_t*)shg, (int)lse_mode, lse, (int)n_partials, lse_out, log_k, u, src, src_stride, (int)rows, dst, dst_stride,
-                       ancestors, ctrl, timeline);
+#define GJX_GT(GATED) hipLaunchKernelGGL((k_resample_gather_tiled<4, true, GATED>), dim3((unsigned)nt), dim3(256), 0, st, logw, K, tile_S, tile_E, \
+                       (const uint64_t*)Pg, (const int32_t*)shg, (int)lse_mode, lse, (int)n_partials, lse_out, log_k, u, src, src_stride, (int)rows, \
+                       dst, dst_stride, ancestors, ctrl, timeline, gate)
+    if (gate) GJX_GT(true); else GJX_GT(false);
+#undef GJX_GT
   } else {
     const size_t lds = 8 * (size_t)((nt + 2) & ~1) + 4 * (size_t)nt;
-    hipLaunchKernelGGL((k_resample_gather_tiled<4, false>), dim3((unsigned)nt), dim3(256), lds, st, logw, K, tile_S, tile_E, (const uint64_t*)nullptr,
-                       (const int32_t*)nullptr, (int)lse_mode, lse, (int)n_partials, lse_out, log_k, u, src, src_stride, (int)rows, dst, dst_stride,
-                       ancestors, ctrl, timeline);
+#define GJX_GT(GATED) hipLaunchKernelGGL((k_resample_gather_tiled<4, false, GATED>), dim3((unsigned)nt), dim3(256), lds, st, logw, K, tile_S, tile_E, \
+                       (const uint64_t*)nullptr, (const int32_t*)nullptr, (int)lse_mode, lse, (int)n_partials, lse_out, log_k, u, src, src_stride, \
+                       (int)rows, dst, dst_stride, ancestors, ctrl, timeline, gate)
+    if (gate) GJX_GT(true); else GJX_GT(false);
+#undef GJX_GT
   }
   GJX_CHECK_LAUNCH("gjx_resample_gather_tiled");
   return GJX_OK;
+}
+
+extern "C" int gjx_resample_gather_tiled(const float* logw, int64_t K, const uint64_t* tile_S, const int32_t* tile_E, int32_t lse_mode,
+                                         const float* lse, int32_t n_partials, double u, const float* src, int64_t src_stride,
+                                         int32_t rows, float* dst, int64_t dst_stride, int32_t* ancestors, float* lse_out,
+                                         int64_t K_total, void* workspace, size_t workspace_bytes, void* stream) {
+  return gjx::resample_gather_tiled_gated(logw, K, tile_S, tile_E, lse_mode, lse, n_partials, u, src, src_stride, rows, dst, dst_stride, ancestors,
+                                          lse_out, K_total, workspace, workspace_bytes, stream, nullptr);
 }
 
 extern "C" int gjx_resample_gather_systematic(const uint64_t* cum, int64_t K, const uint64_t* base_total_dev, double u,
@@ -984,3 +1175,16 @@ extern "C" int gjx_gather_rows(const float* src, int64_t src_stride, const int32
   return GJX_OK;
 }
 
+
+extern "C" int gjx_ess(const float* logw, int64_t K, float* out4, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!logw || !out4 || K <= 0 || K > (int64_t)1 << 31) return gjx_fail(GJX_EINVAL, "gjx_ess: bad argument");
+  const int64_t nt = (K + kTileQ - 1) / kTileQ;
+  EssArgs a;
+  memset(&a, 0, sizeof(a));
+  if (workspace_bytes < gjx_workspace_bytes(GJX_OP_RESAMPLE, K) || ess_workspace(workspace, workspace_bytes, nt, a))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_ess: workspace too small");
+  a.W = const_cast<float*>(logw); a.K = K; a.out4 = out4;
+  hipLaunchKernelGGL(k_ess_tiles<false>, dim3((unsigned)nt), dim3(256), 0, (hipStream_t)stream, a);
+  GJX_CHECK_LAUNCH("gjx_ess");
+  return GJX_OK;
+}

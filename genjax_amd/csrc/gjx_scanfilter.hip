@@ -56,10 +56,13 @@ __global__ void k_tiles_to_granules(const uint64_t* __restrict__ S, const int32_
 }
 
 // rows_of(t): the buffer step t writes its choices into (two alternating buffers, or one per step when the run is recorded)
+// ad (gjx_scan_filter_adaptive, checked by adaptive_check): accumulated weights in ad->logw_acc and a resampling in front of step t only
+// where the device word ad->resampled[t] says so — the plain-launch loop with the search gated and one fused launch behind the step's kernel
 template <class RowsOf>
 static int scan_filter_impl(const gjx_program* steps, int32_t T, uint32_t key0, uint32_t key1, int64_t K, RowsOf&& rows_of,
                             float* logw, int32_t* ancestors, int32_t* ancestors_all, float* lse_steps, void* workspace,
-                            size_t workspace_bytes, void* stream, const gjx_filter_opts* opts, gjx_filter_info* info_out) {
+                            size_t workspace_bytes, void* stream, const gjx_filter_opts* opts, gjx_filter_info* info_out,
+                            const gjx_adaptive_opts* ad = nullptr) {
   const int32_t fflags = opts ? opts->flags : 0;
   const int n_moves = opts ? opts->n_moves : 0;
   if (n_moves < 0) return gjx_fail(GJX_EINVAL, "gjx_scan_filter: n_moves < 0");
@@ -90,12 +93,16 @@ static int scan_filter_impl(const gjx_program* steps, int32_t T, uint32_t key0, 
       if (hmc_t[t].n_slots != steps[t].n_slots || opts->hmc_workspace_bytes < gjx_hmc_workspace_bytes(&hmc_t[t], K))
         return gjx_fail(GJX_EINVAL, "gjx_scan_filter: hmc_targets[t] must have the rows of step t, and hmc_workspace must hold gjx_hmc_workspace_bytes of every target");
   }
-  const bool no_fuse = (fflags & GJX_FILTER_TWO_LAUNCH) != 0 || hmc_t != nullptr;
+  const bool no_fuse = (fflags & GJX_FILTER_TWO_LAUNCH) != 0 || hmc_t != nullptr || ad != nullptr;
   bool fused = room && !no_fuse && K % 1024 == 0 && K <= (1 << 20);
   hipStream_t st0 = (hipStream_t)stream;
   // the status word describes THIS call (a stale time-out bit would end a one-launch form at its first step)
   hipLaunchKernelGGL(k_clear_status, dim3(1), dim3(64), 0, st0, (unsigned*)ws_res + 8);
   GJX_CHECK_LAUNCH("gjx_scan_filter(status word)");
+  if (ad) {
+    const hipError_t e = hipMemsetAsync(ad->resampled, 0, sizeof(int32_t), st0);      // nothing is resampled in front of step 0
+    if (e != hipSuccess) return gjx_fail_hip(e, "gjx_scan_filter_adaptive(resampled[0])");
+  }
   if (fused && T > 1) {
     // the second run workspace's control block must be zero like the first one's (the caller zero-fills the workspace once; be safe)
     const hipError_t e = hipMemsetAsync(ws_run2, 0, kWsHeaderBytes, (hipStream_t)stream);
@@ -274,6 +281,12 @@ static int scan_filter_impl(const gjx_program* steps, int32_t T, uint32_t key0, 
           // (the call above: the finished LSE record of step t - 1 from the run's block pairs; its prefix sums are overwritten)
           rc = gjx_resample_sorted_multinomial_tiled(lw_prev, K, res_keys[2 * t], res_keys[2 * t + 1], K, anc_t, mn_cum, nullptr, nullptr, ws_res, need_res, stream);
           finfo.launches += 5;
+        } else if (ad) {
+          // the gated search on the ACCUMULATED weights: their tile totals are recomputed (the producing kernel's describe inc_{t-1}),
+          // the record of step t - 1 is already written; resampled[t] == 0: identity ancestors, nothing else touched
+          rc = gjx::resample_gather_tiled_gated(ad->logw_acc, K, nullptr, nullptr, 0, nullptr, 0, us[t], nullptr, 0, 0, nullptr, 0, anc_t, nullptr, K,
+                                                ws_res, need_res, stream, ad->resampled + t);
+          finfo.launches += K > 1024 * 1024 ? 2 : 1;
         } else
         rc = gjx_resample_gather_tiled(lw_prev, K, tS, tE, 2, (const float*)(pws + kWsHeaderBytes), prev.n_partials, us[t], nullptr, 0, 0, nullptr, 0,
                                        anc_t, lse_steps + 4 * (size_t)(t - 1), K, ws_res, need_res, stream);
@@ -306,6 +319,15 @@ static int scan_filter_impl(const gjx_program* steps, int32_t T, uint32_t key0, 
       rc = gjx_run_program_ex(&pr, keys[2 * t], keys[2 * t + 1], K, 0, out, nullptr, nullptr, lw_of(t), nullptr, nullptr, nullptr, nullptr, K,
                               ws_of(t), need_run, stream, &o, &info);
       if (rc) return rc;
+    }
+    if (ad) {
+      // W_t = (resampled in front of step t ? 0 : W_{t-1}) + inc_t in place, the record of step t, ESS_t and the decision for step t + 1
+      // (the search's tile totals in ws_res are dead by now: the tile partials of this launch take their place)
+      rc = gjx::launch_ess_accumulate(lw_of(t), ad->logw_acc, t == T - 1 ? logw : nullptr, K, t > 0 ? ad->resampled + t : nullptr,
+                                      lse_steps + 4 * (size_t)t, t > 0 ? lse_steps + 4 * (size_t)(t - 1) : nullptr, ad->ess_steps + t,
+                                      t + 1 < T ? ad->resampled + t + 1 : nullptr, ad->ess_threshold, ws_res, need_res, st0);
+      if (rc) return rc;
+      finfo.launches += 1;
     }
     prev = info;
     // ---- steps 2 .. T-1 in ONE launch (gjx_gen_steps) when step 1 ran with the search in its prologue, the remaining step programs are
@@ -366,6 +388,7 @@ static int scan_filter_impl(const gjx_program* steps, int32_t T, uint32_t key0, 
       }
     }
   }
+  if (ad) return report(GJX_OK);          // (every record was written by its step's fused launch)
   // the record of the last step: its block pairs are still in its run workspace
   finfo.launches += 1;
   return report(gjx_launch_lse_finish(ws_of(T - 1) + kWsHeaderBytes, prev.n_partials, K, lse_steps + 4 * (size_t)(T - 1), (hipStream_t)stream));
@@ -394,4 +417,41 @@ extern "C" int gjx_scan_filter_history(const gjx_program* steps, int32_t T, uint
   const gjx_plain_launch_scope plain_scope(opts && (opts->flags & GJX_FILTER_NO_ONE_LAUNCH) == GJX_FILTER_NO_ONE_LAUNCH);
   return scan_filter_impl(steps, T, key0, key1, K, [&](int t) { return rows_all + (size_t)t * (size_t)rows_per_step * (size_t)K; }, logw, anc,
                           ancestors_all, lse_steps, workspace, workspace_bytes, stream, opts, info_out);
+}
+
+// ---- adaptive resampling (include/gjx.h, gjx_adaptive_opts) ----
+static int adaptive_check(const char* who, const gjx_filter_opts* opts, const gjx_adaptive_opts* ad) {
+  char msg[224];
+  auto fail = [&](int rc, const char* what) { snprintf(msg, sizeof(msg), "%s: %s", who, what); return gjx_fail(rc, msg); };
+  if (!ad || !ad->logw_acc || !ad->ess_steps || !ad->resampled) return fail(GJX_EINVAL, "adapt and its logw_acc, ess_steps, resampled must not be NULL");
+  if (!(ad->ess_threshold >= 0.0f && ad->ess_threshold <= 1.0f)) return fail(GJX_EINVAL, "ess_threshold must be in [0, 1]");
+  if (opts && opts->n_moves > 0) return fail(GJX_EUNSUPPORTED, "the rejuvenation move (n_moves > 0) runs inside the one-launch filter kernel, which resamples in front of every step");
+  if (opts && opts->hmc_targets) return fail(GJX_EUNSUPPORTED, "the HMC move (hmc_targets) runs behind a resampling in front of EVERY step");
+  if (opts && (opts->flags & GJX_FILTER_MULTINOMIAL)) return fail(GJX_EUNSUPPORTED, "adaptive resampling is systematic (no GJX_FILTER_MULTINOMIAL)");
+  return GJX_OK;
+}
+
+extern "C" int gjx_scan_filter_adaptive(const gjx_program* steps, int32_t T, uint32_t key0, uint32_t key1, int64_t K, float* rows_a, float* rows_b,
+                                        float* logw, int32_t* ancestors, int32_t* ancestors_all, float* lse_steps, void* workspace,
+                                        size_t workspace_bytes, void* stream, const gjx_filter_opts* opts, gjx_filter_info* info_out,
+                                        const gjx_adaptive_opts* adapt) {
+  if (!steps || T < 1 || K <= 0 || !rows_a || !rows_b || !logw || !ancestors || !lse_steps)
+    return gjx_fail(GJX_EINVAL, "gjx_scan_filter_adaptive: bad argument");
+  if (const int rc = adaptive_check("gjx_scan_filter_adaptive", opts, adapt)) return rc;
+  return scan_filter_impl(steps, T, key0, key1, K, [&](int t) { return (t & 1) ? rows_b : rows_a; }, logw, ancestors, ancestors_all, lse_steps,
+                          workspace, workspace_bytes, stream, opts, info_out, adapt);
+}
+
+extern "C" int gjx_scan_filter_adaptive_history(const gjx_program* steps, int32_t T, uint32_t key0, uint32_t key1, int64_t K, float* rows_all,
+                                                int32_t rows_per_step, float* logw, int32_t* ancestors_all, float* lse_steps, void* workspace,
+                                                size_t workspace_bytes, void* stream, const gjx_filter_opts* opts, gjx_filter_info* info_out,
+                                                const gjx_adaptive_opts* adapt) {
+  if (!steps || T < 1 || K <= 0 || !rows_all || rows_per_step < 1 || !logw || (T > 1 && !ancestors_all) || !lse_steps)
+    return gjx_fail(GJX_EINVAL, "gjx_scan_filter_adaptive_history: bad argument");
+  for (int t = 0; t < T; ++t)
+    if (steps[t].n_slots > rows_per_step) return gjx_fail(GJX_EINVAL, "gjx_scan_filter_adaptive_history: a step has more rows than rows_per_step");
+  if (const int rc = adaptive_check("gjx_scan_filter_adaptive_history", opts, adapt)) return rc;
+  int32_t* anc = ancestors_all ? ancestors_all : (int32_t*)rows_all;     // (T == 1: never written)
+  return scan_filter_impl(steps, T, key0, key1, K, [&](int t) { return rows_all + (size_t)t * (size_t)rows_per_step * (size_t)K; }, logw, anc,
+                          ancestors_all, lse_steps, workspace, workspace_bytes, stream, opts, info_out, adapt);
 }

@@ -805,8 +805,12 @@ __global__ __launch_bounds__(kTileQ) void k_tiled_quantise(const float* logw, in
   }
 }
 
-__global__ __launch_bounds__(1024) void k_tiled_plan(const uint64_t* S, const int32_t* E, int nt, uint64_t* P, int32_t* sh, unsigned* ctrl) {
+// GATED (the adaptive filter): *gate == 0 means "this step does not resample" — nothing is read or written
+template <bool GATED = false>
+__global__ __launch_bounds__(1024) void k_tiled_plan(const uint64_t* S, const int32_t* E, int nt, uint64_t* P, int32_t* sh, unsigned* ctrl,
+                                                     const int32_t* gate = nullptr) {
   __shared__ float fred[16];
+  if (GATED && *gate == 0) return;
   __shared__ uint64_t wsum[16];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   float em = (float)kTileDead;
@@ -933,8 +937,9 @@ __global__ __launch_bounds__(kTileQ) void k_sorted_ancestors(const uint64_t* P, 
   anc[j] = (int32_t)((int64_t)lo * kTileQ + l2);
 }
 
-int launch_tiled_plan(const uint64_t* S, const int32_t* E, int nt, uint64_t* P, int32_t* sh, unsigned* ctrl, hipStream_t st) {
-  hipLaunchKernelGGL(k_tiled_plan, dim3(1), dim3(1024), 0, st, S, E, nt, P, sh, ctrl);
+int launch_tiled_plan(const uint64_t* S, const int32_t* E, int nt, uint64_t* P, int32_t* sh, unsigned* ctrl, hipStream_t st, const int32_t* gate) {
+  if (gate) hipLaunchKernelGGL(k_tiled_plan<true>, dim3(1), dim3(1024), 0, st, S, E, nt, P, sh, ctrl, gate);
+  else hipLaunchKernelGGL(k_tiled_plan<false>, dim3(1), dim3(1024), 0, st, S, E, nt, P, sh, ctrl, (const int32_t*)nullptr);
   GJX_CHECK_LAUNCH("k_tiled_plan");
   return GJX_OK;
 }
@@ -1052,7 +1057,7 @@ extern "C" int gjx_resample_indices_tiled(const float* logw, int64_t K, double u
   int32_t* E = (int32_t*)(P + nt + 1);
   int32_t* sh = E + nt;
   hipLaunchKernelGGL(k_tiled_quantise, dim3((unsigned)nt), dim3(kTileQ), 0, st, logw, K, cum, S, E, q_out, e_out);
-  hipLaunchKernelGGL(k_tiled_plan, dim3(1), dim3(1024), 0, st, (const uint64_t*)S, (const int32_t*)E, (int)nt, P, sh, (unsigned*)workspace + 8);
+  hipLaunchKernelGGL(k_tiled_plan<false>, dim3(1), dim3(1024), 0, st, (const uint64_t*)S, (const int32_t*)E, (int)nt, P, sh, (unsigned*)workspace + 8, (const int32_t*)nullptr);
   hipLaunchKernelGGL(k_tiled_ancestors, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (const uint64_t*)P, (const int32_t*)sh,
                      (const uint64_t*)cum, (int)nt, K, u, N, ancestors);
   GJX_CHECK_LAUNCH("gjx_resample_indices_tiled");
@@ -1079,7 +1084,7 @@ extern "C" int gjx_resample_sorted_multinomial_tiled(const float* logw, int64_t 
   uint64_t* SP = SS + nb;
   const key2 key{key0, key1};
   hipLaunchKernelGGL(k_tiled_quantise, dim3((unsigned)nt), dim3(kTileQ), 0, st, logw, K, cum, S, E, q_out, e_out);
-  hipLaunchKernelGGL(k_tiled_plan, dim3(1), dim3(1024), 0, st, (const uint64_t*)S, (const int32_t*)E, (int)nt, P, sh, (unsigned*)workspace + 8);
+  hipLaunchKernelGGL(k_tiled_plan<false>, dim3(1), dim3(1024), 0, st, (const uint64_t*)S, (const int32_t*)E, (int)nt, P, sh, (unsigned*)workspace + 8, (const int32_t*)nullptr);
   hipLaunchKernelGGL(k_spacing_totals, dim3((unsigned)nb), dim3(kTileQ), 0, st, key, N, SS);
   hipLaunchKernelGGL(k_spacing_plan, dim3(1), dim3(1024), 0, st, (const uint64_t*)SS, (int)nb, SP);
   hipLaunchKernelGGL(k_sorted_ancestors, dim3((unsigned)((N + kTileQ - 1) / kTileQ)), dim3(kTileQ), 0, st, (const uint64_t*)P, (const int32_t*)sh,

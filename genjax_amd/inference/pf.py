@@ -201,7 +201,7 @@ class BootstrapFilter:
         return super().__new__(cls)
 
     def __init__(self, ssm: LinearGaussianSSM, k_particles: int, rng_mode: int | None = None, rejuvenate: dict | None = None,
-                 weights: str | None = None):
+                 weights: str | None = None, ess_threshold: float | None = None):
         """``rejuvenate=dict(n_moves=.., scale=..)``: resample-move — after every resampling each particle takes n_moves
         random-walk Metropolis steps (proposal scale ``scale``) that leave p(x_{t-1} | parent, y_{t-1}) invariant, fused
         into the propagate kernel (gjx_ssm_step_move).
@@ -211,6 +211,9 @@ class BootstrapFilter:
         peer-mapped exchange when sharded.  Default (None): tile-scaled wherever that path exists, i.e. everywhere except a
         sharded run that cannot use the peer-mapped exchange (keep_means / step_by_step, ranks that are not peers, shards that
         are not whole tiles), which runs the global-maximum scheme over the collective transport."""
+        if ess_threshold is not None:
+            raise ValueError("ess_threshold (adaptive resampling) belongs to the generic filter: the hand-written linear-Gaussian kernels "
+                             "resample in front of every step — write the model as a @gen step and pass kernel.scan(n=T)")
         if weights not in (None, "global_max", "tile_scaled"):
             raise ValueError("weights must be 'global_max' or 'tile_scaled'")
         self._auto_weights = weights is None

@@ -35,7 +35,8 @@ class ScanBootstrapFilter:
     step), the others are propagated."""
 
     def __init__(self, scan: ScanCombinator, k_particles: int, rng_mode: int | None = None, proposal: ScanCombinator | None = None,
-                 proposal_args=None, rejuvenate: dict | None = None, resampler: str = "systematic", moves=None):
+                 proposal_args=None, rejuvenate: dict | None = None, resampler: str = "systematic", moves=None,
+                 ess_threshold: float | None = None):
         """``proposal``: ``q_step.scan(n=T)`` — a kernel ``(carry, x) -> (carry, out)`` like the model's whose sites PROPOSE the model's
         latent choices of the same names (the importance step with a custom proposal, inference/smc.py:302-313, applied per Scan step:
         scan.py:325-416 extends a trace by one step): step t draws from q_t(. | carry, x_t) and weights by
@@ -48,7 +49,12 @@ class ScanBootstrapFilter:
         ``moves=[...]``: ANY of the library's move requests behind every resampling — ``HMC(S["x"], eps, L)`` over the step's continuous
         latents (hmc.py:138-211), ``{"x": Rejuvenate(dist, argument_mapping)}`` with an arbitrary proposal (rejuvenate.py:70-94) — each
         with the caller-side accept (test_requests.py:131-137) on the step-local target; the filter then runs step by step as device
-        calls (inference/filter_moves.py) instead of in the one-launch kernel; ``out["accepted"]`` counts per move."""
+        calls (inference/filter_moves.py) instead of in the one-launch kernel; ``out["accepted"]`` counts per move.
+        ``ess_threshold=tau`` (in [0, 1]): ADAPTIVE resampling — the weights are carried over the steps and the collection is resampled
+        in front of a step only when its effective sample size has fallen under tau K (Gen's maybe_resample!; 1: in front of every step,
+        0: never).  The decision is taken on the device (gjx_scan_filter_adaptive: plain launches per step); ``out["ess"]`` f32[T],
+        ``out["resampled"]`` bool[T], ``out["logw"]`` the ACCUMULATED log-weights; a skipped step's ancestors are the identity.  Not
+        with moves (they rejuvenate behind a resampling in front of every step) nor with the multinomial resampler."""
         from ..gen import StaticGenerativeFunction
         if not isinstance(scan, (ScanCombinator, StaticGenerativeFunction)):
             raise TypeError("ScanBootstrapFilter needs kernel.scan(n=T), or a @gen model whose body is sites in front of one kernel.scan(n=T)(...) call")
@@ -66,6 +72,15 @@ class ScanBootstrapFilter:
         if resampler not in ("systematic", "multinomial"):
             raise ValueError("resampler must be 'systematic' or 'multinomial'")
         self.resampler = resampler            # multinomial: every slot draws its own uniform (GJX_FILTER_MULTINOMIAL; three plain launches per step)
+        self.ess_threshold = None if ess_threshold is None else float(ess_threshold)
+        if self.ess_threshold is not None:
+            if not 0.0 <= self.ess_threshold <= 1.0:       # (NaN fails too)
+                raise ValueError("ess_threshold must be in [0, 1] (1: resample in front of every step, 0: never)")
+            if self.rejuvenate or self.moves:
+                raise ValueError("ess_threshold (adaptive resampling) does not run with rejuvenate=... / moves=[...]: a move rejuvenates "
+                                 "behind the resampling in front of EVERY step")
+            if resampler == "multinomial":
+                raise ValueError("ess_threshold (adaptive resampling) runs with the systematic resampler")
         self.rng_mode = config.rng_mode() if rng_mode is None else rng_mode
         self._cache: dict = {}
 
@@ -299,12 +314,23 @@ class ScanBootstrapFilter:
         lse = torch.empty((T, 4), dtype=f32, device=dev)
         ws_bytes = b["ws"].numel() if T <= 4096 else min(b["ws"].numel(), self._ws_one_launch_per_step)
         opts, info = self._opts(dev), A.GjxFilterInfo()
+        # adaptive resampling: the same calls with the accumulated weights, the ESS record and the decisions (gjx_adaptive_opts) behind them
+        adapt, tail = None, ()
+        scan_filter, scan_filter_history = load().gjx_scan_filter, load().gjx_scan_filter_history
+        if self.ess_threshold is not None:
+            if b.get("logw_acc") is None:
+                b["logw_acc"] = torch.empty(K, dtype=f32, device=dev)
+            ess, resampled = torch.empty(T, dtype=f32, device=dev), torch.empty(T, dtype=torch.int32, device=dev)
+            adapt = A.GjxAdaptiveOpts(self.ess_threshold, 0, b["logw_acc"].data_ptr(), ess.data_ptr(), resampled.data_ptr())
+            tail = (C.byref(adapt),)
+            scan_filter, scan_filter_history = load().gjx_scan_filter_adaptive, load().gjx_scan_filter_adaptive_history
+        extra = (lambda: dict(ess=ess, resampled=resampled.bool())) if adapt is not None else dict
         if keep_history:
             rows_all = torch.empty((T, n_rows, K), dtype=f32, device=dev)
             anc_all = torch.empty((max(T - 1, 1), K), dtype=torch.int32, device=dev)
-            check(load().gjx_scan_filter_history(C.cast(cps, C.c_void_p), T, key[0], key[1], K, kernels._ptr(rows_all), n_rows, kernels._ptr(b["logw"]),
-                                                 kernels._ptr(anc_all), kernels._ptr(lse), kernels._ptr(b["ws"]), ws_bytes, kernels._stream(),
-                                                 C.byref(opts), C.byref(info)), "gjx_scan_filter_history")
+            check(scan_filter_history(C.cast(cps, C.c_void_p), T, key[0], key[1], K, kernels._ptr(rows_all), n_rows, kernels._ptr(b["logw"]),
+                                      kernels._ptr(anc_all), kernels._ptr(lse), kernels._ptr(b["ws"]), ws_bytes, kernels._stream(),
+                                      C.byref(opts), C.byref(info), *tail), "gjx_scan_filter_history")
             self.last_info = dict(form=int(info.form), form_name=A.FILTER_FORM_NAMES[int(info.form)], launches=int(info.launches), grid=int(info.grid),
                                   tiles_per_block=int(info.tiles_per_block))
             st = self._status(b)
@@ -316,11 +342,11 @@ class ScanBootstrapFilter:
             hist = ScanHistory(progs, rows_all, anc_all[: T - 1], logw, moved=moved)
             return dict(log_ml=incs.sum(), increments=incs, lse_steps=lse, choices=rows_all[T - 1][: max(progs[-1].n_slots, 1)], logw=logw,
                         programs=progs, ancestors=anc_all[: T - 1], history=hist, degenerate=bool(st & 2), info=self.last_info,
-                        accepted_total=(int(self._acc.item()) if moved and getattr(self, "_acc", None) is not None else None))
+                        accepted_total=(int(self._acc.item()) if moved and getattr(self, "_acc", None) is not None else None), **extra())
         anc_all = torch.empty((max(T - 1, 1), K), dtype=torch.int32, device=dev) if keep_ancestors else None
-        check(load().gjx_scan_filter(C.cast(cps, C.c_void_p), T, key[0], key[1], K, kernels._ptr(b["rows_a"]), kernels._ptr(b["rows_b"]),
-                                     kernels._ptr(b["logw"]), kernels._ptr(b["anc"]), kernels._ptr(anc_all), kernels._ptr(lse),
-                                     kernels._ptr(b["ws"]), ws_bytes, kernels._stream(), C.byref(opts), C.byref(info)), "gjx_scan_filter")
+        check(scan_filter(C.cast(cps, C.c_void_p), T, key[0], key[1], K, kernels._ptr(b["rows_a"]), kernels._ptr(b["rows_b"]),
+                          kernels._ptr(b["logw"]), kernels._ptr(b["anc"]), kernels._ptr(anc_all), kernels._ptr(lse),
+                          kernels._ptr(b["ws"]), ws_bytes, kernels._stream(), C.byref(opts), C.byref(info), *tail), "gjx_scan_filter")
         self.last_info = dict(form=int(info.form), form_name=A.FILTER_FORM_NAMES[int(info.form)], launches=int(info.launches), grid=int(info.grid),
                               tiles_per_block=int(info.tiles_per_block))
         st = self._status(b)
@@ -332,7 +358,7 @@ class ScanBootstrapFilter:
         return dict(log_ml=incs.sum(), increments=incs, lse_steps=lse, choices=self._out(ch), logw=self._out(b["logw"]), programs=progs,
                     ancestors=anc_all if keep_ancestors else self._out(b["anc"]), degenerate=bool(st & 2), info=self.last_info,
                     accepted_total=(int(self._acc.item()) if (self.rejuvenate or self._hmc_state) and getattr(self, "_acc", None) is not None else None),
-                    accepted=([int(self._acc.item())] if self._hmc_state else None))
+                    accepted=([int(self._acc.item())] if self._hmc_state else None), **extra())
 
     def _repeat_after_timeout(self, key, constraint, args, device, keep_ancestors, keep_history):
         """GJX_STATUS_POLL_TIMEOUT: the one-launch kernel needs its whole grid resident and something else held compute units.  The
@@ -369,6 +395,8 @@ class ScanBootstrapFilter:
         choices (this rank's part of the last step: a view of the window), logw, ancestors? (global indices), programs, info)"""
         if ctx.K != self.K:
             raise ValueError("run_peer: the filter's particle count must be the context's K_local")
+        if self.ess_threshold is not None:
+            raise NotImplementedError("run_peer: the sharded filter kernel resamples in front of every step (ess_threshold runs on one GPU)")
         if self.moves or (self.rejuvenate and int(self.rejuvenate.get("n_moves", 0)) > 0):
             raise NotImplementedError("run_peer: the sharded filter kernel has no resample-move yet (rejuvenate=..., moves=...); run() on one GPU has")
         if getattr(self, "_has_statics", False):

@@ -88,6 +88,11 @@ class ParticleCollection:
                 self._lse = kernels.logsumexp(self.log_weights, self.K_total)
         return self._lse
 
+    def effective_sample_size(self):
+        """ESS = (sum w)^2 / sum w^2 of the collection's weights: a 0-d device tensor (gjx_ess, one launch; Gen's effective_sample_size)"""
+        from .. import kernels
+        return kernels.ess(self.log_weights)[3]
+
     def lse_partials(self):
         """kernels.RunPartials of the producing run if still valid (for ``inference.pf.resample(..., collection=)``)"""
         p = self._partials

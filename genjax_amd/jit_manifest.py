@@ -29,6 +29,10 @@ MANIFEST: List[Entry] = [
     ("hier_logreg_importance", lambda: workloads.logreg_importance_program()[0], "run", (1, 2, 4, 1 | 256)),
     # config 3's model written as @gen + .scan: the filter kernel on the shared skeleton, one tile per block (K = 2^18) and four (2^20)
     ("lgssm_scan_step", lambda: workloads.lgssm_scan_step_program(), "filter", (1, 4)),
+    # the same model at dx = 2 (tests/test_gpu_adaptive_filter.py): the plain-launch loop of the adaptive filter (ess_threshold=...) runs
+    # the step programs' own kernels, step 0 and the periodic step, at whatever particles-per-lane the picker chooses
+    ("lgssm_scan_dx2_step0", lambda: workloads.lgssm_scan_step_program(2, step=0), "run", (1, 2, 4)),
+    ("lgssm_scan_dx2_step", lambda: workloads.lgssm_scan_step_program(2), "run", (1, 2, 4)),
     # config 5: the generated HMC kernel
     ("hier_logreg_hmc", lambda: workloads.logreg_program()[0], "hmc", (None,)),
 ]

@@ -381,6 +381,17 @@ def resample_indices_tiled(logw: torch.Tensor, u: float, N: int | None = None, a
     return (anc, q, e) if want_q else anc
 
 
+def ess(logw: torch.Tensor, ws=None) -> torch.Tensor:
+    """gjx_ess: log-weights f32[K] -> device f32[4] = {max, sum e, sum e^2, ESS = (sum e)^2 / sum e^2}, e_i = exp(logw_i - max); the sums
+    are taken per 1024-particle tile and combined in a fixed order (one launch, no synchronisation)"""
+    K = logw.numel()
+    out = torch.empty(4, dtype=torch.float32, device=logw.device)
+    if ws is None:
+        ws = shared_workspace(A.OP_RESAMPLE, K, logw.device)
+    check(load().gjx_ess(_ptr(logw), K, _ptr(out), _ptr(ws), ws.numel(), _stream()), "gjx_ess")
+    return out
+
+
 def resample_sorted_multinomial_tiled(logw: torch.Tensor, key, N: int | None = None, anc=None, cum=None, ws=None, want_q=False):
     """gjx_resample_sorted_multinomial_tiled: log-weights -> MULTINOMIAL ancestors (sorted uniforms from exponential spacings under
     `key`, tile-scaled fixed point), non-decreasing.  -> ancestors int32[N], or (ancestors, q, e) with want_q"""

@@ -114,10 +114,11 @@ def lgssm_scan(dx: int = 8, T: int = 256):
     return step.scan(n=T), np.zeros(dx, np.float32), s
 
 
-def lgssm_scan_step_program(dx: int = 8):
-    """the one-step program (step 1 of 4) the generic filter generates its kernels from: build steps pre-compile it"""
+def lgssm_scan_step_program(dx: int = 8, step: int = 1):
+    """the one-step program (step 1 of 4; ``step=0``: the first step, which reads no carry) the generic filter generates its kernels
+    from: build steps pre-compile it"""
     from . import C
     from .inference.scan_filter import ScanBootstrapFilter
     scan, carry0, s = lgssm_scan(dx, 4)
     bf = ScanBootstrapFilter(scan, 1024)
-    return bf.step_programs(C["y"].set(np.asarray(s["y"], np.float32)[:4]), (carry0, None))[1]
+    return bf.step_programs(C["y"].set(np.asarray(s["y"], np.float32)[:4]), (carry0, None))[step]

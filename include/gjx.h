@@ -44,7 +44,7 @@ typedef unsigned long size_t;
 extern "C" {
 #endif
 
-#define GJX_ABI_VERSION 10
+#define GJX_ABI_VERSION 11
 
 typedef enum gjx_status {
   GJX_OK = 0,
@@ -852,6 +852,45 @@ int gjx_scan_filter(const gjx_program* steps, int32_t T, uint32_t key0, uint32_t
 int gjx_scan_filter_history(const gjx_program* steps, int32_t T, uint32_t key0, uint32_t key1, int64_t K, float* rows_all,
                             int32_t rows_per_step, float* logw, int32_t* ancestors_all, float* lse_steps, void* workspace,
                             size_t workspace_bytes, void* stream, const gjx_filter_opts* opts, gjx_filter_info* info_out);
+/* ---- (ABI 11) ADAPTIVE resampling: the filter above carries ACCUMULATED log-weights W f32[K] and resamples in front of a step only
+ * when the effective sample size of the collection has fallen under a fraction of K (Gen's maybe_resample!(state, ess_threshold)).
+ *   step 0: W_0 = inc_0 (the step's incremental log-weights).  In front of step t >= 1: e_i = exp(W_i - max W),
+ *   ESS_{t-1} = (sum e)^2 / sum e^2 (0 for a dead collection); resample iff ESS_{t-1} < ess_threshold * K or ess_threshold >= 1.
+ *   resampled: ancestors = gjx_resample_indices_tiled(W, K, us[t], K) bit for bit (comb offset and keys as gjx_scan_filter; the tile
+ *     totals are recomputed from W), the carry is read through them, W_t = inc_t.
+ *   skipped: ancestors = identity, written to the same buffers (ancestors, ancestors_all[t-1]); W_t = W_{t-1} + inc_t; the step's
+ *     resampling key is not used.
+ *   lse_steps[t] = {max W_t, sum exp(W_t - max), lse(W_t), lse(W_t) - c_t}, c_t the log-sum-exp of the carried weights before inc_t was
+ *     added: log K at step 0 and behind a resampling, lse(W_{t-1}) behind a skip — so log-ML = sum_t lse_steps[t][3] as before, and
+ *     with ess_threshold >= 1 the record is gjx_scan_filter's (to float summation order).
+ * The sums are taken per 1024-particle tile and the tiles combined in a fixed order: ESS is a function of W alone.  The decision is
+ * taken on the DEVICE (resampled[t] is the word the launches in front of step t read): the call issues no stream synchronisation.
+ * Per step: the gated search of the tile-scaled resampler (tile totals, the tile prefix beyond 1024 tiles, the search — on "skip"
+ * each writes nothing but identity ancestors), the step's kernel, and ONE fused launch that adds inc_t to W in place (8 B read + 4 B
+ * written per particle), reduces {max, sum e, sum e^2} and writes the record, ess_steps[t] and resampled[t + 1].
+ * info_out->form is GJX_FILTER_FORM_TWO_LAUNCH: the one-launch forms (WIDE, STEPS) and the prologue search (PER_STEP) assume
+ * incremental weights and the producing kernel's tile totals and are NOT extended here.  Any K <= 2^26, any program an engine runs;
+ * GJX_FILTER_ABSOLUTE_INPUTS and proposal sites work as in gjx_scan_filter.  GJX_EUNSUPPORTED: n_moves > 0, hmc_targets,
+ * GJX_FILTER_MULTINOMIAL.  GJX_EINVAL: ess_threshold outside [0, 1] or NaN, a NULL field.  logw receives W_{T-1}. */
+typedef struct gjx_adaptive_opts {
+  float ess_threshold;           /* [0, 1]; >= 1: always resample; 0: never (importance sampling along the Scan) */
+  int32_t reserved;              /* 0 */
+  float* logw_acc;               /* f32[K] device scratch: the carried W */
+  float* ess_steps;              /* f32[T] out: ESS of W_t */
+  int32_t* resampled;            /* i32[T] out: 1 if the collection was resampled in FRONT of step t ([0] = 0) */
+} gjx_adaptive_opts;
+int gjx_scan_filter_adaptive(const gjx_program* steps, int32_t T, uint32_t key0, uint32_t key1, int64_t K, float* rows_a, float* rows_b,
+                             float* logw, int32_t* ancestors, int32_t* ancestors_all, float* lse_steps, void* workspace,
+                             size_t workspace_bytes, void* stream, const gjx_filter_opts* opts, gjx_filter_info* info_out,
+                             const gjx_adaptive_opts* adapt);
+int gjx_scan_filter_adaptive_history(const gjx_program* steps, int32_t T, uint32_t key0, uint32_t key1, int64_t K, float* rows_all,
+                                     int32_t rows_per_step, float* logw, int32_t* ancestors_all, float* lse_steps, void* workspace,
+                                     size_t workspace_bytes, void* stream, const gjx_filter_opts* opts, gjx_filter_info* info_out,
+                                     const gjx_adaptive_opts* adapt);
+/* Effective sample size of log-weights f32[K]: out4 (device) = {max, sum e, sum e^2, (sum e)^2 / sum e^2} with e_i = exp(logw_i -
+ * max); NaN and -inf weights count as dead, a dead collection gives {-inf, 0, 0, 0}.  The reduction of the filter above (one launch,
+ * 4 B read per particle).  workspace: gjx_workspace_bytes(GJX_OP_RESAMPLE, K), zero-filled once. */
+int gjx_ess(const float* logw, int64_t K, float* out4, void* workspace, size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
