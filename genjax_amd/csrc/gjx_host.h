@@ -90,6 +90,13 @@ inline bool decode(int code, FilterVariant* v) {
   return true;
 }
 
+// rows of a program's INPUT sites (they come first and in order)
+inline int input_rows(const gjx_program& p) {
+  int n = 0;
+  for (int j = 0; j < p.n_sites; ++j) if (p.sites[j].mode == GJX_MODE_INPUT) n += p.sites[j].dim;
+  return n;
+}
+
 // phase-stamp buffer of the profiling scripts (gjx_debug_timeline): the registered device buffer if it holds `need` bytes
 unsigned long long* debug_timeline(size_t need);
 struct GenArgs;
@@ -111,6 +118,16 @@ bool gen_pf_same_kernel(const gjx_program* p, const gjx_program* q);
 int gen_pf_precompile(const gjx_program* prog, int spl);
 int gen_pf_resident_blocks(const gjx_program* prog, int spl, size_t dyn_lds);
 int gen_pf_launch(const gjx_program* prog, int spl, const GenPfArgs& args, int grid, size_t dyn_lds, hipStream_t st);
+// steps 2 .. T-1 are the kernel of step 1 (a periodic Scan: they differ in tables, keys, comb offsets); same_kernel(&steps[1], &steps[u])
+// compares the generated code (gen_pf_same_kernel, or gen_same_kernel at one ppt)
+template <class SameKernel>
+bool periodic_steps(const gjx_program* steps, int T, SameKernel&& same_kernel) {
+  for (int u = 2; u < T; ++u)
+    if (steps[u].n_tab != steps[1].n_tab || steps[u].n_slots != steps[1].n_slots || input_rows(steps[u]) != input_rows(steps[1]) ||
+        !steps[u].tab_dev || !same_kernel(&steps[1], &steps[u]))
+      return false;
+  return true;
+}
 // n 8-byte words from HOST memory to device memory through kernel arguments (small per-run argument arrays: step keys, comb
 // offsets, table pointers): no host buffer has to outlive the call, unlike an asynchronous copy from pageable memory
 int upload_words(void* dst_dev, const void* src_host, size_t n_words, hipStream_t st);

@@ -30,31 +30,6 @@ constexpr size_t kAlign = 256;
 size_t align_up(size_t v) { return (v + kAlign - 1) / kAlign * kAlign; }
 }  // namespace
 
-struct gjx_peer_ctx {
-  int world = 0, rank = 0, rows = 0, share = 1;
-  int64_t K = 0;                       // particles per rank
-  int nt = 0, NT = 0;                  // quantisation tiles per rank / in total
-  char* data = nullptr;                // this rank's DATA window
-  char* flag = nullptr;                // this rank's FLAG window
-  size_t data_bytes = 0, flag_bytes = 0;
-  size_t off_rows[2] = {0, 0}, off_lw[2] = {0, 0}, off_m[2] = {0, 0};   // off_m: transition means of the resample-move filter
-  size_t off_chk[2] = {0, 0};          // verify mode: one check word per particle row (u32[K], ping-pong like the rows)
-  bool verify = false;                 // GJX_PEER_VERIFY=1 when the context was created
-  bool verify_fault = false;           // GJX_PEER_VERIFY_FAULT=<this rank>: publish wrong check words (test hook)
-  bool data_fine = false;              // DATA window in fine-grained memory (GJX_PEER_DATA=fine)
-  size_t off_region[2] = {0, 0}, region_bytes = 0;
-  // inside a flag region
-  size_t r_aggA = 0, r_aggB = 0, r_bsum = 0, r_bmax = 0, r_ready = 0, r_gmm = 0;
-  char* peer_data[GJX_MAX_RANKS];
-  char* peer_flag[GJX_MAX_RANKS];
-  long long* delta_dev = nullptr;      // [2][world]: byte distance to rank g's data window, then to its flag window
-  bool connected = false;
-  uint64_t n_filter = 0, n_gmm = 0;    // launches so far (select the flag region / the tags)
-  double* us_dev = nullptr;
-  uint32_t* keys_dev = nullptr;
-  int t_cap = 0;
-};
-
 #define GJX_HIP(call, where)                                   \
   do {                                                         \
     hipError_t e__ = (call);                                   \
@@ -122,8 +97,8 @@ static int peer_ctx_create(int32_t n_ranks, int32_t rank, int64_t K_local, int32
   // the words of the one-launch resampling step (twice, for alternating calls: 4 x [MAX_RANKS] u64 + this rank's tile granules [nt])
   const size_t NT = (size_t)c->NT;
   size_t r = 0;
-  c->r_aggA = r; r = align_up(r + 8 * NT * kPfGranulePad);   // (one granule per 64-byte line)
-  c->r_aggB = r; r = align_up(r + 8 * NT * kPfGranulePad);
+  c->r_aggA = r; r = align_up(r + 8 * NT * kPfCorePad);   // (one granule per 64-byte line)
+  c->r_aggB = r; r = align_up(r + 8 * NT * kPfCorePad);
   c->r_bsum = r; r = align_up(r + 12 * NT);
   c->r_bmax = r; r = align_up(r + 12 * NT);
   c->r_ready = r; r = align_up(r + 4 * (size_t)kPfHostMaxTiles);
@@ -271,38 +246,18 @@ static int filter_peer(const gjx_ssm* m, uint32_t key0, uint32_t key1, int32_t r
   std::vector<uint32_t> h_keys;        // per-call staging; the words travel as kernel arguments (upload_words): nothing of it is read later
   std::vector<double> h_us;
   pf_step_keys(key0, key1, T, h_keys, h_us);
-  if (int rcu = upload_words(c->us_dev, h_us.data(), (size_t)T, st)) return rcu;
-  if (int rck = upload_words(c->keys_dev, h_keys.data(), (size_t)T, st)) return rck;      // (T pairs of 32-bit words)
+  if (int rcu = pf_upload_steps(c->us_dev, h_us, c->keys_dev, h_keys, nullptr, nullptr, T, st)) return rcu;
   float* x_a = (float*)(c->data + c->off_rows[0]);
   float* x_b = (float*)(c->data + c->off_rows[1]);
-  float* lw_even = (float*)(c->data + c->off_lw[0]);
-  float* lw_odd = (float*)(c->data + c->off_lw[1]);
-  float* lw0 = ((T - 1) & 1) ? lw_odd : lw_even;     // log-weights of step 0
+  float* lw0 = (float*)(c->data + c->off_lw[(T - 1) & 1]);     // log-weights of step 0
   // step 0 from the prior; its global LSE record comes out of the ring like every other step's (T > 1)
   int rc = gjx_ssm_step(m, h_keys[0], h_keys[1], rng_mode, 0, K, (int64_t)c->rank * K, nullptr, K, nullptr, ys_dev, x_a, lw0,
                         nullptr, K_total, nullptr, 0, stream);
   if (rc) return rc;
-  const int region = (int)(c->n_filter & 1), other = region ^ 1;
-  c->n_filter += 1;
-  char* rg = c->flag + c->off_region[region];
   PfArgs f;
   memset(&f, 0, sizeof(f));
-  f.A = m->A_dev; f.H = m->H_dev; f.ys = ys_dev; f.q = m->q; f.r = m->r; f.dy = m->dy; f.T = T;
-  f.K = K; f.K_total = K_total; f.offset = (int64_t)c->rank * K; f.G = c->world; f.rank = c->rank; f.nt = c->nt; f.NT = c->NT;
-  f.x_a = x_a; f.x_b = x_b; f.lw_even = lw_even; f.lw_odd = lw_odd;
-  f.aggA = (unsigned long long*)(rg + c->r_aggA); f.aggB = (unsigned long long*)(rg + c->r_aggB);
-  f.bsum = (float*)(rg + c->r_bsum); f.bmax = (float*)(rg + c->r_bmax); f.ready = (unsigned*)(rg + c->r_ready);
-  f.peer_data = c->world > 1 ? c->delta_dev : nullptr;
-  f.peer_flag = c->world > 1 ? c->delta_dev + c->world : nullptr;
-  f.keys = c->keys_dev; f.us = c->us_dev; f.lse_steps = lse_steps; f.ancestors = ancestors;
-  f.ctrl = (unsigned*)c->flag + 8; f.log_k = (float)log((double)K_total);
-  // the other ranks' launches may be queued behind host work of their own: the first rendezvous waits for seconds, later ones ~0.1 s
-  f.first_budget = c->world > 1 ? (1u << 24) : (1u << 16);
-  f.zero_ptr = (unsigned long long*)(c->flag + c->off_region[other] + c->r_aggA);
-  f.zero_n = (int)((c->r_bsum - c->r_aggA) / 8);
-  f.q0 = m->q0;
-  f.verify = c->verify ? (c->verify_fault ? 2 : 1) : 0;
-  f.chk_a = (unsigned*)(c->data + c->off_chk[0]); f.chk_b = (unsigned*)(c->data + c->off_chk[1]);
+  f.core = pf_core_peer(T, c, lse_steps, ancestors);
+  f.A = m->A_dev; f.H = m->H_dev; f.ys = ys_dev; f.q = m->q; f.r = m->r; f.dy = m->dy; f.x_a = x_a; f.x_b = x_b; f.q0 = m->q0;
   if (move) {
     f.m_a = (float*)(c->data + c->off_m[0]); f.m_b = (float*)(c->data + c->off_m[1]);
     f.n_moves = n_moves; f.move_scale = move_scale; f.acc_total = acc_total;
@@ -362,19 +317,12 @@ static int scan_filter_peer_impl(gjx_peer_ctx* c, const gjx_program* steps, int3
   fv.multinomial = multinomial;
   if (!c || !steps || (!lse_steps && !prepare_only) || T < 2) return gjx_fail(GJX_EINVAL, "gjx_scan_filter_peer: bad argument (T >= 2)");
   if (!c->connected) return gjx_fail(GJX_EINVAL, "gjx_scan_filter_peer: the context is not connected (gjx_peer_ctx_connect)");
-  auto input_rows = [](const gjx_program& p) {
-    int n = 0;
-    for (int j = 0; j < p.n_sites; ++j) if (p.sites[j].mode == GJX_MODE_INPUT) n += p.sites[j].dim;
-    return n;
-  };
   for (int t = 0; t < T; ++t)
     if (steps[t].n_slots > c->rows) return gjx_fail(GJX_EINVAL, "gjx_scan_filter_peer: a step program has more rows than the context (rows >= n_slots of every step)");
   if (!steps[1].tab_dev || !gen_pf_supported(&steps[1]))
     return gjx_fail(GJX_EUNSUPPORTED, "gjx_scan_filter_peer: the step program is outside the filter emitter's coverage (sites SAMPLE / OBS_TAB / INPUT)");
-  for (int u = 2; u < T; ++u)
-    if (steps[u].n_tab != steps[1].n_tab || steps[u].n_slots != steps[1].n_slots || input_rows(steps[u]) != input_rows(steps[1]) || !steps[u].tab_dev ||
-        !gen_pf_same_kernel(&steps[1], &steps[u]))
-      return gjx_fail(GJX_EUNSUPPORTED, "gjx_scan_filter_peer: the step programs 1 .. T-1 must be one kernel (a periodic Scan)");
+  if (!periodic_steps(steps, T, gen_pf_same_kernel))
+    return gjx_fail(GJX_EUNSUPPORTED, "gjx_scan_filter_peer: the step programs 1 .. T-1 must be one kernel (a periodic Scan)");
   if (input_rows(steps[1]) > steps[0].n_slots - input_rows(steps[0])) return gjx_fail(GJX_EINVAL, "gjx_scan_filter_peer: step 1 reads more carry rows than step 0 produced");
   if (c->NT > kPfHostMaxTiles) return gjx_fail(GJX_EUNSUPPORTED, "gjx_scan_filter_peer: K_total <= 2^22");
   const size_t need_run = gjx_workspace_bytes(GJX_OP_RUN, c->K);
@@ -382,21 +330,15 @@ static int scan_filter_peer_impl(gjx_peer_ctx* c, const gjx_program* steps, int3
   hipStream_t st = (hipStream_t)stream;
   const int64_t K = c->K, K_total = K * c->world;
   const size_t dyn = pf_core_dyn_lds(c->NT, multinomial);
-  int spl = 0, grid = 0;
-  const int spls[5] = {1, 2, 4, 8, 16};
-  for (int i = 0; i < 5 && !spl; ++i) {
-    const int64_t g = ((int64_t)c->nt + spls[i] - 1) / spls[i];
-    fv.tiles = spls[i];
-    int cap = gen_pf_resident_blocks(&steps[1], encode(fv), dyn);
-    if (cap <= 0) break;
-    if (c->share > 1) cap /= c->share;               // ranks that share one device (dry runs): every rank's grid must be resident
-    if (g <= cap && g * c->world <= kPfHostMaxTiles) { spl = spls[i]; grid = (int)g; }
-  }
-  if (!spl) return gjx_fail(GJX_EUNSUPPORTED, "gjx_scan_filter_peer: no co-resident grid for this size (or the kernel could not be generated)");
+  const PfGeometry geo = pf_pick_tiles(c->nt, c->world, c->share, kPfHostMaxTiles, [&](int tiles) {
+    fv.tiles = tiles;
+    return gen_pf_resident_blocks(&steps[1], encode(fv), dyn);
+  });
+  if (!geo.spl) return gjx_fail(GJX_EUNSUPPORTED, "gjx_scan_filter_peer: no co-resident grid for this size (or the kernel could not be generated)");
   if (T > c->t_cap) return gjx_fail(GJX_EUNSUPPORTED, "gjx_scan_filter_peer: more steps than a peer context holds (GJX_PEER_MAX_STEPS = 4096 per call)");
   if (prepare_only) {
     // step 0's own kernel (gjx_run_program_ex picks and compiles it on first use), then nothing is launched
-    finfo.launches = 0; finfo.grid = grid; finfo.tiles_per_block = spl;
+    finfo.launches = 0; finfo.grid = geo.grid; finfo.tiles_per_block = geo.spl;
     if (info_out) *info_out = finfo;
     (void)gjx_program_precompile(&steps[0], gen_pick_ppt(&steps[0], c->K, false));     // (step 0 may run on another engine: not an error)
     return GJX_OK;
@@ -404,19 +346,11 @@ static int scan_filter_peer_impl(gjx_peer_ctx* c, const gjx_program* steps, int3
   std::vector<uint32_t> h_keys, h_res;
   std::vector<double> h_us;
   pf_step_keys_res(key0, key1, T, h_keys, h_us, h_res);
-  if (multinomial)      // (the sorted-uniform resampler takes the resampling KEY of a step where the comb takes its offset: two words as one 64-bit pattern)
-    for (int u = 0; u < T; ++u) { const uint64_t w = (uint64_t)h_res[2 * u] | ((uint64_t)h_res[2 * u + 1] << 32); memcpy(&h_us[u], &w, 8); }
-  if (int rcu = upload_words(c->us_dev, h_us.data(), (size_t)T, st)) return rcu;
-  if (int rcu = upload_words(c->keys_dev, h_keys.data(), (size_t)T, st)) return rcu;
   const float** tabs_dev = (const float**)((char*)workspace + ((need_run + 255) & ~(size_t)255));
-  std::vector<const float*> h_tabs((size_t)T, nullptr);
-  for (int u = 0; u < T; ++u) h_tabs[u] = steps[u].tab_dev;
-  if (int rcu = upload_words(tabs_dev, h_tabs.data(), (size_t)T, st)) return rcu;
+  if (int rcu = pf_upload_steps(c->us_dev, pf_us_words(h_us, h_res, multinomial), c->keys_dev, h_keys, tabs_dev, steps, T, st)) return rcu;
   float* rows_a = (float*)(c->data + c->off_rows[0]);
   float* rows_b = (float*)(c->data + c->off_rows[1]);
-  float* lw_even = (float*)(c->data + c->off_lw[0]);
-  float* lw_odd = (float*)(c->data + c->off_lw[1]);
-  float* lw0 = ((T - 1) & 1) ? lw_odd : lw_even;     // log-weights of step 0
+  float* lw0 = (float*)(c->data + c->off_lw[(T - 1) & 1]);     // log-weights of step 0
   // step 0 (no carry to read) on this rank's particle range; its global LSE record comes out of the ring like every other step's
   gjx_run_opts o;
   memset(&o, 0, sizeof(o));
@@ -424,34 +358,17 @@ static int scan_filter_peer_impl(gjx_peer_ctx* c, const gjx_program* steps, int3
   int rc = gjx_run_program_ex(&steps[0], h_keys[0], h_keys[1], K, (int64_t)c->rank * K, rows_a, nullptr, nullptr, lw0, nullptr, nullptr, nullptr, nullptr,
                               K_total, workspace, need_run, stream, &o, &info);
   if (rc) return rc;
-  const int region = (int)(c->n_filter & 1), other = region ^ 1;
-  c->n_filter += 1;
-  char* rg = c->flag + c->off_region[region];
   GenPfArgs ga;
   memset(&ga, 0, sizeof(ga));
-  PfCoreArgs& f = ga.core;
-  f.T = T; f.K = K; f.K_total = K_total; f.offset = (int64_t)c->rank * K; f.G = c->world; f.rank = c->rank; f.nt = c->nt; f.NT = c->NT;
-  f.lw_even = lw_even; f.lw_odd = lw_odd;
-  f.aggA = (unsigned long long*)(rg + c->r_aggA); f.aggB = (unsigned long long*)(rg + c->r_aggB);
-  f.bsum = (float*)(rg + c->r_bsum); f.bmax = (float*)(rg + c->r_bmax); f.ready = (unsigned*)(rg + c->r_ready);
-  f.peer_data = c->world > 1 ? c->delta_dev : nullptr;
-  f.peer_flag = c->world > 1 ? c->delta_dev + c->world : nullptr;
-  f.keys = c->keys_dev; f.us = c->us_dev; f.lse_steps = lse_steps; f.ancestors = ancestors; f.ancestors_all = nullptr;
-  f.ctrl = (unsigned*)c->flag + 8; f.log_k = (float)log((double)K_total);
-  f.first_budget = c->world > 1 ? (1u << 24) : (1u << 16);
-  f.zero_ptr = (unsigned long long*)(c->flag + c->off_region[other] + c->r_aggA);
-  f.zero_n = (int)((c->r_bsum - c->r_aggA) / 8);
-  f.verify = c->verify ? (c->verify_fault ? 2 : 1) : 0;
-  f.chk_a = (unsigned*)(c->data + c->off_chk[0]); f.chk_b = (unsigned*)(c->data + c->off_chk[1]);
-  f.timeline = nullptr;
+  ga.core = pf_core_peer(T, c, lse_steps, ancestors);
   ga.tabs = tabs_dev;
-  ga.rows_a = rows_a; ga.rows_b = rows_b; ga.rows_all = nullptr; ga.rows_step = 0;
+  ga.rows_a = rows_a; ga.rows_b = rows_b;
   ga.in_row0_first = (int64_t)input_rows(steps[0]) * K;
   ga.in_row0 = (int64_t)input_rows(steps[1]) * K;
-  fv.tiles = spl;
-  rc = gen_pf_launch(&steps[1], encode(fv), ga, grid, dyn, st);
+  fv.tiles = geo.spl;
+  rc = gen_pf_launch(&steps[1], encode(fv), ga, geo.grid, dyn, st);
   if (rc) return rc;
-  finfo.launches = 2; finfo.grid = grid; finfo.tiles_per_block = spl;
+  finfo.launches = 2; finfo.grid = geo.grid; finfo.tiles_per_block = geo.spl;
   if (info_out) *info_out = finfo;
   return GJX_OK;
 }

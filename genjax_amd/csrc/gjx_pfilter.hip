@@ -1,5 +1,6 @@
-// gjx_pfilter.hip — host side of k_pf_persistent (gjx_pfilter.inl): grid / tiles-per-block plan and the step keys of a
-// filter run (the single-GPU launch is in gjx_ssm.hip, the sharded one in gjx_peer.hip).
+// gjx_pfilter.hip — host side shared by the launchers of the one-launch particle filters (declared in gjx_pfilter_host.h): the kernel /
+// grid plan of k_pf_persistent, the step keys of a run, the skeleton's workspace area, the ONE place PfCoreArgs is filled (one GPU, or a
+// rank of a peer context) and the upload of the per-step arrays.  The launchers themselves are in gjx_ssm.hip, gjx_peer.hip, gjx_scanfilter.hip.
 #include <math.h>
 #include <string.h>
 
@@ -19,22 +20,16 @@ int pf_plan(int rng_mode, int dx, int dy, int64_t K_local, int n_ranks, int shar
   if (n_ranks > 1 && K_local % kPfHostThreads) return GJX_EUNSUPPORTED;   // sharded: whole tiles per rank
   if (nt * n_ranks > kPfHostMaxTiles) return GJX_EUNSUPPORTED;
   const size_t lds = pf_host_dyn_lds((int)(nt * n_ranks));
-  const int spls[5] = {1, 2, 4, 8, 16};
-  for (int i = 0; i < 5; ++i) {
-    const int spl = spls[i];
-    const void* fn = rng_mode == GJX_RNG_JAX32 ? pf_kernel_jax(dx, spl, move) : pf_kernel_flat(dx, spl, move);
-    if (!fn) continue;
+  auto kernel = [&](int spl) { return rng_mode == GJX_RNG_JAX32 ? pf_kernel_jax(dx, spl, move) : pf_kernel_flat(dx, spl, move); };
+  const PfGeometry geo = pf_pick_tiles(nt, n_ranks, share, kPfHostMaxTiles, [&](int spl) {
+    const void* fn = kernel(spl);
     // (static + dynamic LDS is above the 64 KB default once NT > 2048)
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); }
-    int cap = gjx_coresident_blocks(fn, kPfHostThreads, lds);
-    if (share > 1) cap /= share;                 // ranks that share one device (dry runs): every rank's grid must be resident
-    const int64_t grid = (nt + spl - 1) / spl;
-    if (grid <= cap && grid * n_ranks <= kPfHostMaxTiles) {
-      out->fn = fn; out->spl = spl; out->grid = (int)grid; out->lds = lds; out->nt = (int)nt;
-      return GJX_OK;
-    }
-  }
-  return GJX_EUNSUPPORTED;
+    if (fn && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); }
+    return fn ? gjx_coresident_blocks(fn, kPfHostThreads, lds) : 0;
+  });
+  if (!geo.spl) return GJX_EUNSUPPORTED;
+  out->fn = kernel(geo.spl); out->spl = geo.spl; out->grid = geo.grid; out->lds = lds; out->nt = (int)nt;
+  return GJX_OK;
 }
 
 // ---- small per-run argument arrays (step keys, comb offsets, table pointers) reach the device as KERNEL ARGUMENTS: the runtime
@@ -95,6 +90,74 @@ void pf_step_keys_res(uint32_t key0, uint32_t key1, int T, std::vector<uint32_t>
     res_keys[2 * t] = kr[0]; res_keys[2 * t + 1] = kr[1];
     us[t] = (double)((b[0] ^ b[1]) >> 9) / 8388608.0;
   }
+}
+
+PfRegion pf_region(char* base, int64_t nt, int64_t grid, int T, bool with_tabs) {
+  PfRegion r;
+  const size_t tile_bytes = (16 * (size_t)kPfCorePad + 24) * (size_t)nt, ready_bytes = 8 * (((size_t)grid + 1) / 2);
+  r.nt = (int)nt; r.ctrl = (unsigned*)base + 8;
+  r.aggA = (unsigned long long*)(base + kWsHeaderBytes); r.aggB = r.aggA + (size_t)nt * kPfCorePad;
+  r.bsum = (float*)(r.aggB + (size_t)nt * kPfCorePad); r.bmax = r.bsum + 3 * (size_t)nt;
+  r.ready = (unsigned*)(r.bmax + 3 * (size_t)nt);
+  r.us = (double*)((char*)r.ready + ready_bytes); r.keys = (uint32_t*)(r.us + T);
+  r.tabs = with_tabs ? (const float**)(r.keys + 2 * (size_t)T) : nullptr;
+  r.clear_bytes = tile_bytes + ready_bytes;
+  r.bytes = kWsHeaderBytes + tile_bytes + 8 * (size_t)grid + (with_tabs ? 24 : 16) * (size_t)T + 64;
+  return r;
+}
+
+PfCoreArgs pf_core_single(int T, int64_t K, const PfRegion& rg, float* lw_even, float* lw_odd, float* lse_steps, int32_t* ancestors) {
+  PfCoreArgs c;
+  memset(&c, 0, sizeof(c));               // one rank: offset, rank 0; no peers, nothing to clear for a next launch, no verify mode
+  c.T = T; c.K = K; c.K_total = K; c.G = 1; c.nt = rg.nt; c.NT = rg.nt;
+  c.lw_even = lw_even; c.lw_odd = lw_odd;
+  c.aggA = rg.aggA; c.aggB = rg.aggB; c.bsum = rg.bsum; c.bmax = rg.bmax; c.ready = rg.ready;
+  c.keys = rg.keys; c.us = rg.us; c.lse_steps = lse_steps; c.ancestors = ancestors;
+  c.ctrl = rg.ctrl; c.log_k = (float)log((double)K); c.first_budget = kPollBudget;
+  return c;
+}
+
+PfCoreArgs pf_core_peer(int T, gjx_peer_ctx* c, float* lse_steps, int32_t* ancestors) {
+  const int region = (int)(c->n_filter & 1), other = region ^ 1;
+  c->n_filter += 1;
+  char* rg = c->flag + c->off_region[region];
+  PfCoreArgs f;
+  memset(&f, 0, sizeof(f));
+  f.T = T; f.K = c->K; f.K_total = c->K * c->world; f.offset = (int64_t)c->rank * c->K; f.G = c->world; f.rank = c->rank; f.nt = c->nt; f.NT = c->NT;
+  f.lw_even = (float*)(c->data + c->off_lw[0]); f.lw_odd = (float*)(c->data + c->off_lw[1]);
+  f.aggA = (unsigned long long*)(rg + c->r_aggA); f.aggB = (unsigned long long*)(rg + c->r_aggB);
+  f.bsum = (float*)(rg + c->r_bsum); f.bmax = (float*)(rg + c->r_bmax); f.ready = (unsigned*)(rg + c->r_ready);
+  f.peer_data = c->world > 1 ? c->delta_dev : nullptr;
+  f.peer_flag = c->world > 1 ? c->delta_dev + c->world : nullptr;
+  f.keys = c->keys_dev; f.us = c->us_dev; f.lse_steps = lse_steps; f.ancestors = ancestors;
+  f.ctrl = (unsigned*)c->flag + 8; f.log_k = (float)log((double)f.K_total);
+  // the other ranks' launches may be queued behind host work of their own: the first rendezvous waits for seconds, later ones ~0.1 s
+  f.first_budget = c->world > 1 ? (1u << 24) : kPollBudget;
+  f.zero_ptr = (unsigned long long*)(c->flag + c->off_region[other] + c->r_aggA);
+  f.zero_n = (int)((c->r_bsum - c->r_aggA) / 8);
+  f.verify = c->verify ? (c->verify_fault ? 2 : 1) : 0;
+  f.chk_a = (unsigned*)(c->data + c->off_chk[0]); f.chk_b = (unsigned*)(c->data + c->off_chk[1]);
+  return f;
+}
+
+std::vector<double> pf_us_words(const std::vector<double>& us, const std::vector<uint32_t>& res_keys, bool multinomial) {
+  std::vector<double> w(us);
+  if (multinomial)
+    for (size_t u = 0; u < w.size(); ++u) { const uint64_t b = (uint64_t)res_keys[2 * u] | ((uint64_t)res_keys[2 * u + 1] << 32); memcpy(&w[u], &b, 8); }
+  return w;
+}
+
+int pf_upload_tabs(const float** tabs_dev, const gjx_program* steps, int T, hipStream_t st) {
+  std::vector<const float*> h_tabs((size_t)T, nullptr);
+  for (int u = 0; u < T; ++u) h_tabs[u] = steps[u].tab_dev;
+  return upload_words(tabs_dev, h_tabs.data(), (size_t)T, st);
+}
+
+int pf_upload_steps(double* us_dev, const std::vector<double>& us, uint32_t* keys_dev, const std::vector<uint32_t>& keys, const float** tabs_dev,
+                    const gjx_program* steps, int T, hipStream_t st) {
+  if (int rc = upload_words(us_dev, us.data(), (size_t)T, st)) return rc;
+  if (int rc = upload_words(keys_dev, keys.data(), (size_t)T, st)) return rc;      // (T pairs of 32-bit words)
+  return tabs_dev ? pf_upload_tabs(tabs_dev, steps, T, st) : GJX_OK;
 }
 
 }  // namespace gjx

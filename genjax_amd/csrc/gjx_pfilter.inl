@@ -16,8 +16,6 @@
 
 namespace gjx {
 
-static_assert(kPfThreads == kPfCoreThreads && kPfGranulePad == kPfCorePad, "k_pf_persistent runs on pf_core's geometry");
-
 template <int RNG, int DX, bool MOVE>
 struct LgssmModel {
   const PfArgs& f;
@@ -34,8 +32,8 @@ struct LgssmModel {
   GJX_DEV float* m_buf(int t) const { return (t & 1) ? f.m_b : f.m_a; }   // MOVE: A x'_{t-1} of step t (step 0: the prior mean, zero — never read)
 
   GJX_DEV void prologue(int tid) {
-    for (int e = tid; e < DX * DX; e += kPfThreads) sA[e] = f.A[e];
-    if (f.H) for (int e = tid; e < f.dy * DX; e += kPfThreads) sH[e] = f.H[e];
+    for (int e = tid; e < DX * DX; e += kPfCoreThreads) sA[e] = f.A[e];
+    if (f.H) for (int e = tid; e < f.dy * DX; e += kPfCoreThreads) sH[e] = f.H[e];
   }
   GJX_DEV void stage(int t, int tid) {             // y_t (and y_{t-1}) by lanes of the second wave, while the granules travel
     const int lane = tid & 63;
@@ -163,26 +161,15 @@ struct LgssmModel {
   }
 };
 
-GJX_DEV PfCoreArgs pf_core_args(const PfArgs& f) {
-  PfCoreArgs c;
-  c.T = f.T; c.K = f.K; c.K_total = f.K_total; c.offset = f.offset; c.G = f.G; c.rank = f.rank; c.nt = f.nt; c.NT = f.NT;
-  c.lw_even = f.lw_even; c.lw_odd = f.lw_odd; c.aggA = f.aggA; c.aggB = f.aggB; c.bsum = f.bsum; c.bmax = f.bmax; c.ready = f.ready;
-  c.peer_data = f.peer_data; c.peer_flag = f.peer_flag; c.keys = f.keys; c.us = f.us; c.lse_steps = f.lse_steps;
-  c.ancestors = f.ancestors; c.ancestors_all = nullptr; c.ctrl = f.ctrl; c.log_k = f.log_k; c.first_budget = f.first_budget;
-  c.zero_ptr = f.zero_ptr; c.zero_n = f.zero_n; c.verify = f.verify; c.chk_a = f.chk_a; c.chk_b = f.chk_b; c.timeline = f.timeline;
-  return c;
-}
-
 template <int RNG, int DX, int SPL, bool MOVE = false>
-__global__ __launch_bounds__(kPfThreads) void k_pf_persistent(PfArgs f) {
+__global__ __launch_bounds__(kPfCoreThreads) void k_pf_persistent(PfArgs f) {
   extern __shared__ __align__(16) unsigned char pf_dyn[];
   // model constants in LDS: inside the step loop the compiler must assume the kernel's own stores may alias A, H, ys and
   // re-reads them with VECTOR loads every step
   __shared__ float sA[DX * DX], sH[kSsmPersistMaxDy * DX], sY[kSsmPersistMaxDy];
   __shared__ float sYp[MOVE ? kSsmPersistMaxDy : 1];       // MOVE: y_{t-1}, the observation the moved particle is conditioned on
   LgssmModel<RNG, DX, MOVE> m(f, sA, sH, sY, sYp);
-  const PfCoreArgs c = pf_core_args(f);
-  pf_core<LgssmModel<RNG, DX, MOVE>, SPL>(c, m, pf_dyn);
+  pf_core<LgssmModel<RNG, DX, MOVE>, SPL>(f.core, m, pf_dyn);
 }
 
 // kernel of one (dx, spl) for this translation unit's RNG; NULL when the combination is not instantiated

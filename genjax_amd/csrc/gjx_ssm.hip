@@ -1121,41 +1121,23 @@ static int pf_filter_launch(const gjx_ssm* m, uint32_t key0, uint32_t key1, int3
                             float* x_a, float* x_b, float* logw, float* lw_alt, int32_t* ancestors, float* lse_steps, char* ws2,
                             size_t need, void* stream, const PfMove* mv) {
   PfPlan pf;
-  if (pf_plan(rng_mode, m->dx, m->dy, K, 1, 1, &pf, mv != nullptr) != GJX_OK ||
-      256 + (16 * (size_t)kPfGranulePad + 24) * (size_t)pf.nt + 8 * (size_t)pf.grid + 16 * (size_t)T + 64 > need)
-    return GJX_EUNSUPPORTED;
+  if (pf_plan(rng_mode, m->dx, m->dy, K, 1, 1, &pf, mv != nullptr) != GJX_OK) return GJX_EUNSUPPORTED;
+  const PfRegion rg = pf_region(ws2, pf.nt, pf.grid, T, false);
+  if (rg.bytes > need) return GJX_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  auto lw_of = [&](int t) { return ((T - 1 - t) & 1) ? lw_alt : logw; };
   std::vector<uint32_t> h_keys;
   std::vector<double> h_us;
   pf_step_keys(key0, key1, T, h_keys, h_us);
-  const size_t NT = (size_t)pf.nt;
-  // ws2: [256 B control][aggA 64 NT][aggB 64 NT][bsum 12 NT][bmax 12 NT][ready 4 grid, padded to 8][us 8 T][keys 8 T]
-  unsigned long long* aggA = (unsigned long long*)(ws2 + kWsHeaderBytes);
-  unsigned long long* aggB = aggA + NT * kPfGranulePad;
-  float* bsum = (float*)(aggB + NT * kPfGranulePad);
-  float* bmax = bsum + 3 * NT;
-  unsigned* ready = (unsigned*)(bmax + 3 * NT);
-  double* us_dev = (double*)(ready + 2 * (((size_t)pf.grid + 1) / 2));
-  uint32_t* keys_dev = (uint32_t*)(us_dev + T);
-  hipError_t e = hipMemsetAsync(aggA, 0, (16 * kPfGranulePad + 24) * NT + 8 * (((size_t)pf.grid + 1) / 2), st);   // no stale granule of another kernel may pass
+  hipError_t e = hipMemsetAsync(rg.aggA, 0, rg.clear_bytes, st);   // no stale granule of another kernel may pass
   if (e == hipSuccess && mv && mv->acc_total) e = hipMemsetAsync(mv->acc_total, 0, sizeof(unsigned long long), st);
   if (e != hipSuccess) return gjx_fail_hip(e, "gjx_ssm_filter(workspace)");
-  // (step keys and comb offsets travel as kernel arguments: no host buffer outlives this call, no per-thread staging state)
-  if (int rcu = upload_words(us_dev, h_us.data(), (size_t)T, st)) return rcu;
-  if (int rcu = upload_words(keys_dev, h_keys.data(), (size_t)T, st)) return rcu;
-  if (int rc0 = ssm_step0(m, h_keys, rng_mode, K, ys_dev, x_a, lw_of(0), st)) return rc0;   // (no move: there is nothing to rejuvenate yet)
+  if (int rcu = pf_upload_steps(rg.us, h_us, rg.keys, h_keys, nullptr, nullptr, T, st)) return rcu;
+  if (int rc0 = ssm_step0(m, h_keys, rng_mode, K, ys_dev, x_a, ((T - 1) & 1) ? lw_alt : logw, st)) return rc0;   // (step 0's log-weights; no move: there is nothing to rejuvenate yet)
   PfArgs f;
   memset(&f, 0, sizeof(f));
-  f.A = m->A_dev; f.H = m->H_dev; f.ys = ys_dev; f.q = m->q; f.r = m->r; f.dy = m->dy; f.T = T;
-  f.K = K; f.K_total = K; f.offset = 0; f.G = 1; f.rank = 0; f.nt = pf.nt; f.NT = pf.nt;
-  f.x_a = x_a; f.x_b = x_b; f.lw_even = logw; f.lw_odd = lw_alt;
-  f.aggA = aggA; f.aggB = aggB; f.bsum = bsum; f.bmax = bmax; f.ready = ready;
-  f.peer_data = nullptr; f.peer_flag = nullptr; f.keys = keys_dev; f.us = us_dev;
-  f.lse_steps = lse_steps; f.ancestors = ancestors; f.ctrl = (unsigned*)ws2 + 8; f.log_k = (float)log((double)K);
-  f.first_budget = 1u << 16; f.zero_ptr = nullptr; f.zero_n = 0;
-  f.q0 = m->q0;
-  f.timeline = gjx::debug_timeline(128 * (size_t)pf.grid);     // (profiling scripts only: gjx_debug_timeline registers the buffer)
+  f.core = pf_core_single(T, K, rg, logw, lw_alt, lse_steps, ancestors);
+  f.core.timeline = gjx::debug_timeline(128 * (size_t)pf.grid);     // (profiling scripts only: gjx_debug_timeline registers the buffer)
+  f.A = m->A_dev; f.H = m->H_dev; f.ys = ys_dev; f.q = m->q; f.r = m->r; f.dy = m->dy; f.x_a = x_a; f.x_b = x_b; f.q0 = m->q0;
   if (mv) { f.m_a = mv->m_a; f.m_b = mv->m_b; f.n_moves = mv->n_moves; f.move_scale = mv->move_scale; f.acc_total = mv->acc_total; }
   void* args[] = {&f};
   e = hipLaunchKernel(pf.fn, dim3((unsigned)pf.grid), dim3(kPfHostThreads), args, pf.lds, st);
