@@ -365,9 +365,15 @@ GJX_DEV float lbeta_f(float a, float b) {
 // leaves O(1): in float32 the closed form is piecewise constant from a ~ 1e5 (steps of 0.25 at a = 1e7).  From a >= 8 the same
 // value in the deviance form  1/2 log a - 1/2 log 2 pi - S(a) + a (log1p(d) - d),  d = (z - a) / a,  S = Stirling's correction:
 // nothing large is subtracted — the caller forms z - a with ONE rounding (fma), log1p(d) - d comes from a series.
-// log1p(t) - t: below |t| = 1/4, log1p(t) = 2 atanh(s) with s = t / (2 + t), and 2 s - t = -s t exactly
-GJX_DEV float log1p_minus(float t) {
-  if (!(fabsf(t) < 0.25f)) return log1p_acc(t) - t;
+// log1p(t) - t: below |t| = 1/4, log1p(t) = 2 atanh(s) with s = t / (2 + t), and 2 s - t = -s t exactly.  Outside, log(1 + t) - t: nothing
+// large cancels there any more — but towards t = -1 (z << a: the far lower tail) the sum 1 + t is formed from a t that was already
+// rounded next to -1, and log(1 + t) carries 2^-24 / (1 + t), times a in the caller (gamma(30, 1/4) at x = 1e-3 off by 0.17,
+// poisson(1e-4) at x = 1000 off by 583: tests/test_gpu_density_grid.py).  Below t = -3/4 the caller's `far_log()` gives log(1 + t)
+// from the UN-cancelled quantities (log z - log a), whose rounding is relative to the result; it is evaluated on that path only, so
+// the bulk path |t| < 1/4 is the instructions it was.  Both forms are accurate around -3/4: the switch is continuous.
+template <class FarLog>
+GJX_DEV float log1p_minus(float t, FarLog&& far_log) {
+  if (!(fabsf(t) < 0.25f)) return (t < -0.75f ? far_log() : log1p_acc(t)) - t;
   const float s = t * fast_rcp(2.0f + t), s2 = s * s;
   return fmaf(-s, t, 2.0f * s * s2 * (0.333333333f + s2 * (0.2f + s2 * (0.142857143f + s2 * (0.111111111f + s2 * 0.0909090909f)))));
 }
@@ -375,9 +381,10 @@ GJX_DEV float stirling_corr(float a) {      // lgamma(a) - ((a - 1/2) log a - a 
   const float r = fast_rcp(a), r2 = r * r;
   return r * (0.0833333333f - r2 * (2.7777778e-3f - r2 * 7.9365079e-4f));
 }
-// a log z - z - lgamma(a) for a >= 8; num = z - a
-GJX_DEV float gamma_kernel_big(float a, float num) {
-  return fmaf(a, log1p_minus(num * fast_rcp(a)), 0.5f * fast_log(a) - kHalfLog2Pi - stirling_corr(a));
+// a log z - z - lgamma(a) for a >= 8; num = z - a (ONE rounding), z itself for the far lower tail (log1p_minus)
+GJX_DEV float gamma_kernel_big(float a, float num, float z) {
+  const float la = fast_log(a);
+  return fmaf(a, log1p_minus(num * fast_rcp(a), [&]() { return fast_log(z) - la; }), 0.5f * la - kHalfLog2Pi - stirling_corr(a));
 }
 
 // digamma: recurrence up to x >= 6, then the asymptotic series (|error| < 1e-6 for x > 1e-3)
@@ -390,6 +397,11 @@ GJX_DEV float digamma_f(float x) {
   return acc + fast_log(x) - 0.5f * r - r2 * (0.0833333333f - r2 * (0.00833333333f - r2 * 0.00396825397f));
 }
 
+// 1 - exp(u), u <= 0, accurate near 0 (series above -2^-6, as log1p_acc)
+GJX_DEV float one_minus_exp(float u) {
+  if (u > -0.015625f) return -u * (1.0f + u * (0.5f + u * (0.166666667f + u * (0.0416666667f + u * 0.00833333333f))));
+  return 1.0f - fast_exp(u);
+}
 GJX_DEV float softplus(float x) { return fmaxf(x, 0.0f) + log1p_acc(fast_exp(-fabsf(x))); }
 GJX_DEV float sigmoid(float x) { return fast_rcp(1.0f + fast_exp(-x)); }
 
@@ -564,6 +576,13 @@ GJX_DEV float normal_interval_mass(float lo, float hi) {
   return normal_cdf(hi) - normal_cdf(lo);
 }
 
+// atan(hi) - atan(lo), lo <= hi (the truncated Cauchy's interval mass): with lo hi > -1 it is atan((hi - lo) / (1 + lo hi)), which
+// has no cancellation — a window [1000, 1050] scale units out leaves 5e-5 of two values of 1.57, 2e-3 of the mass in float32
+GJX_DEV float atan_diff(float lo, float hi) {
+  const float p = fmaf(lo, hi, 1.0f);
+  return p > 0.0f ? atanf((hi - lo) * fast_rcp(p)) : atanf(hi) - atanf(lo);
+}
+
 // exp(-x) I0(x) and I1(x) / I0(x), x >= 0: Abramowitz & Stegun 9.8.1 - 9.8.4 (|relative error| < 2e-7)
 GJX_DEV float bessel_i0e(float x) {
   if (x < 3.75f) {
@@ -624,7 +643,7 @@ GJX_DEV float elem_logpdf(int kind, float x, float a, float b, float c = 0.0f, f
       if (x < c || x > d) return -INFINITY;
       const float rs = fast_rcp(b);
       const float z = (x - a) * rs;
-      return -fast_log(b) - log1p_acc(z * z) - fast_log(atanf((d - a) * rs) - atanf((c - a) * rs));
+      return -fast_log(b) - log1p_acc(z * z) - fast_log(atan_diff((c - a) * rs, (d - a) * rs));
     }
     case GJX_NEGATIVE_BINOMIAL: {  // a = total_count r, b = logits l of the success probability: C(x + r - 1, x) p^x (1 - p)^r
       if (x < 0.0f || x != floorf(x)) return -INFINITY;
@@ -638,17 +657,17 @@ GJX_DEV float elem_logpdf(int kind, float x, float a, float b, float c = 0.0f, f
     case GJX_CHI: {  // a = df: sqrt of a chi2(df) variate
       if (x <= 0.0f) return -INFINITY;
       const float h = 0.5f * a;
-      if (h >= 8.0f) return gamma_kernel_big(h, 0.5f * fmaf(x, x, -a)) + kLn2 - fast_log(x);      // chi2's density at x^2, times 2 x
+      if (h >= 8.0f) return gamma_kernel_big(h, 0.5f * fmaf(x, x, -a), 0.5f * x * x) + kLn2 - fast_log(x);      // chi2's density at x^2, times 2 x
       return (1.0f - h) * kLn2 + ((a - 1.0f) == 0.0f ? 0.0f : (a - 1.0f) * fast_log(x)) - 0.5f * x * x - lgammaf(h);
     }
     case GJX_EXP_GAMMA: {  // a = concentration, b = rate: y = log of a gamma variate; with z = b e^y: a log z - z - lgamma(a)
       const float z = b * fast_exp(x);
-      if (a >= 8.0f) return gamma_kernel_big(a, z - a);
+      if (a >= 8.0f) return gamma_kernel_big(a, z - a, z);
       return a * (fast_log(b) + x) - z - lgammaf(a);
     }
     case GJX_EXP_INVERSE_GAMMA: {  // a = concentration, b = scale: y = log of an inverse-gamma variate; z = b e^-y
       const float z = b * fast_exp(-x);
-      if (a >= 8.0f) return gamma_kernel_big(a, z - a);
+      if (a >= 8.0f) return gamma_kernel_big(a, z - a, z);
       return a * (fast_log(b) - x) - z - lgammaf(a);
     }
     case GJX_KUMARASWAMY: {  // a = concentration1, b = concentration0
@@ -676,7 +695,7 @@ GJX_DEV float elem_logpdf(int kind, float x, float a, float b, float c = 0.0f, f
     }
     case GJX_POISSON:
       if (x < 0.0f || x != floorf(x)) return -INFINITY;
-      if (x >= 7.0f) return gamma_kernel_big(x + 1.0f, a - (x + 1.0f)) - fast_log(a);     // (x + 1) log a - a - lgamma(x + 1) - log a
+      if (x >= 7.0f) return gamma_kernel_big(x + 1.0f, a - (x + 1.0f), a) - fast_log(a);     // (x + 1) log a - a - lgamma(x + 1) - log a
       return (x == 0.0f ? 0.0f : x * fast_log(a)) - a - lgammaf(x + 1.0f);
     case GJX_GEOMETRIC: return (x < 0.0f || x != floorf(x)) ? -INFINITY : ((x == 0.0f ? 0.0f : x * log1p_acc(-a)) + fast_log(a));
     case GJX_GUMBEL: {
@@ -689,11 +708,11 @@ GJX_DEV float elem_logpdf(int kind, float x, float a, float b, float c = 0.0f, f
     }
     case GJX_INVERSE_GAMMA:  // a = concentration, b = scale
       if (x <= 0.0f) return -INFINITY;
-      if (a >= 8.0f) return gamma_kernel_big(a, fmaf(-a, x, b) * fast_rcp(x)) - fast_log(x);   // z = b / x: a log z - z - lgamma(a) - log x
+      if (a >= 8.0f) return gamma_kernel_big(a, fmaf(-a, x, b) * fast_rcp(x), b * fast_rcp(x)) - fast_log(x);   // z = b / x: a log z - z - lgamma(a) - log x
       return a * fast_log(b) - lgammaf(a) - (a + 1.0f) * fast_log(x) - b * fast_rcp(x);
     case GJX_WEIBULL: {  // a = concentration k, b = scale
       if (x < 0.0f) return -INFINITY;
-      const float lr = fast_log(x * fast_rcp(b));
+      const float lr = safe_log(x * fast_rcp(b));      // (x / b can be denormal-small one step inside the edge at 0)
       return fast_log(a * fast_rcp(b)) + ((a - 1.0f) == 0.0f ? 0.0f : (a - 1.0f) * lr) - fast_exp(a * lr);
     }
     case GJX_LOGIT_NORMAL: {
@@ -704,7 +723,7 @@ GJX_DEV float elem_logpdf(int kind, float x, float a, float b, float c = 0.0f, f
     case GJX_CHI2: {  // a = df
       const float h = 0.5f * a;
       if (x <= 0.0f) return -INFINITY;
-      if (h >= 8.0f) return gamma_kernel_big(h, 0.5f * (x - a)) - fast_log(x);                  // gamma(h, rate 1/2): z = x / 2
+      if (h >= 8.0f) return gamma_kernel_big(h, 0.5f * (x - a), 0.5f * x) - fast_log(x);                  // gamma(h, rate 1/2): z = x / 2
       return ((h - 1.0f) == 0.0f ? 0.0f : (h - 1.0f) * fast_log(x)) - 0.5f * x - h * kLn2 - lgammaf(h);
     }
     case GJX_NORMAL:
@@ -720,9 +739,12 @@ GJX_DEV float elem_logpdf(int kind, float x, float a, float b, float c = 0.0f, f
         // w = -t_ / b,  t_ = n x - a (the linear terms a u + b w cancel identically), and the rest of Stirling is O(log n).
         // t_ = b x - a (1 - x) from two fused multiply-adds: the rounding of n = a + b (up to 16 at n = 3e8) never enters it
         const float n = a + b, t_ = fmaf(b, x, fmaf(a, x, -a));
-        const float dev = fmaf(a, log1p_minus(t_ * fast_rcp(a)), b * log1p_minus(-t_ * fast_rcp(b)));
-        return dev + 0.5f * (fast_log(a) + fast_log(b) - fast_log(n)) - kHalfLog2Pi - stirling_corr(a) - stirling_corr(b) + stirling_corr(n)
-               - fast_log(x) - log1p_acc(-x);
+        // far from the mode (x << p or 1 - x << 1 - p) log1p(u) = log x - log(a / n) and log1p(w) = log(1 - x) - log(b / n), from the
+        // logarithms this branch takes anyway (log1p_minus)
+        const float la = fast_log(a), lb = fast_log(b), ln = fast_log(n), lx = fast_log(x), l1x = log1p_acc(-x);
+        const float dev = fmaf(a, log1p_minus(t_ * fast_rcp(a), [&]() { return lx - la + ln; }),
+                               b * log1p_minus(-t_ * fast_rcp(b), [&]() { return l1x - lb + ln; }));
+        return dev + 0.5f * (la + lb - ln) - kHalfLog2Pi - stirling_corr(a) - stirling_corr(b) + stirling_corr(n) - lx - l1x;
       }
       const float t1 = (a - 1.0f) == 0.0f ? 0.0f : (a - 1.0f) * fast_log(x);
       const float t2 = (b - 1.0f) == 0.0f ? 0.0f : (b - 1.0f) * log1p_acc(-x);
@@ -744,7 +766,7 @@ GJX_DEV float elem_logpdf(int kind, float x, float a, float b, float c = 0.0f, f
       return -(kLogPi + fast_log(b)) - log1p_acc(z * z);
     }
     case GJX_GAMMA: {
-      if (a >= 8.0f && x > 0.0f) return gamma_kernel_big(a, fmaf(b, x, -a)) - fast_log(x);     // z = b x: a log z - z - lgamma(a) - log x
+      if (a >= 8.0f && x > 0.0f) return gamma_kernel_big(a, fmaf(b, x, -a), b * x) - fast_log(x);     // z = b x: a log z - z - lgamma(a) - log x
       const float t0 = a == 0.0f ? 0.0f : a * fast_log(b);
       const float t1 = (a - 1.0f) == 0.0f ? 0.0f : (a - 1.0f) * fast_log(x);
       return t0 + t1 - b * x - lgammaf(a);
@@ -1125,10 +1147,11 @@ GJX_DEV void dlogpdf(int kind, float x, float a, float b, float c, float d, floa
   dx = 0.0f;
   auto done = [&]() { gpar[0] = da; gpar[1] = db; gpar[2] = dc; gpar[3] = dd; };
   switch (kind) {
-    case GJX_TRUNCATED_CAUCHY: {  // a = loc, b = scale, c = low, d = high
+    case GJX_TRUNCATED_CAUCHY: {  // a = loc, b = scale, c = low, d = high.  (Limit: db is a sum of terms of size 1 / b; in a window a few float32
+      // steps of x wide it cancels to ~0 and keeps 1e-5 / b of absolute error — tests/golden/make_density_grid.py leaves that window out.)
       const float rb = fast_rcp(b);
       const float z = (x - a) * rb, lo = (c - a) * rb, hi = (d - a) * rb;
-      const float rA = fast_rcp(atanf(hi) - atanf(lo)) * rb;
+      const float rA = fast_rcp(atan_diff(lo, hi)) * rb;
       const float wl = fast_rcp(fmaf(lo, lo, 1.0f)) * rA, wh = fast_rcp(fmaf(hi, hi, 1.0f)) * rA;
       const float w = 2.0f * z * fast_rcp(fmaf(z, z, 1.0f)) * rb;
       dx = -w; da = w + (wh - wl); db = fmaf(w, z, -rb) + (hi * wh - lo * wl); dc = wl; dd = -wh;
@@ -1157,7 +1180,9 @@ GJX_DEV void dlogpdf(int kind, float x, float a, float b, float c, float d, floa
     }
     case GJX_KUMARASWAMY: {
       const float lx = fast_log(x), xa = fast_exp(a * lx);
-      const float r = xa * fast_rcp(1.0f - xa);                                  // x^a / (1 - x^a)
+      // x^a / (1 - x^a); towards x = 1 the difference 1 - x^a keeps 2^-24 of 1 (d/da = 70.6 where it is 71.4 at 1 - x^a = 1e-6:
+      // tests/test_gpu_density_grid.py), 1 - exp(a log x) from the series does not
+      const float r = xa * fast_rcp(one_minus_exp(a * lx));
       dx = ((a - 1.0f) - (b - 1.0f) * a * r) * fast_rcp(x);
       da = fast_rcp(a) + lx * (1.0f - (b - 1.0f) * r);
       db = fast_rcp(b) + log1p_acc(-xa);
@@ -1197,7 +1222,9 @@ GJX_DEV void dlogpdf(int kind, float x, float a, float b, float c, float d, floa
       const float wy = big ? a + 1.0f : w * y;
       dx = -w * rc; db = w * rc; dc = (wy - 1.0f) * rc;
       const float l1p = big ? 2.0f * fast_log(fabsf(y)) - fast_log(a) : log1p_acc(yy * fast_rcp(a));
-      const float t2 = big ? 0.5f * (a + 1.0f) * fast_rcp(a) : 0.5f * (a + 1.0f) * yy * fast_rcp(a * (a + yy));
+      // (df + 1) y^2 / (2 df (df + y^2)) = w y / (2 df): the product df (df + y^2) leaves float32 from |y| ~ 1e16 at df = 1e7 (inf * 0: a NaN,
+      // tests/test_gpu_density_grid.py), w y never does
+      const float t2 = 0.5f * wy * fast_rcp(a);
       da = -0.5f * l1p + t2 - 0.5f * fast_rcp(a) + 0.5f * digamma_half_step(0.5f * a);
       done(); return;
     }
@@ -1234,7 +1261,7 @@ GJX_DEV void dlogpdf(int kind, float x, float a, float b, float c, float d, floa
       done(); return;
     }
     case GJX_WEIBULL: {
-      const float lr = fast_log(x * fast_rcp(b));
+      const float lr = safe_log(x * fast_rcp(b));
       const float t = fast_exp(a * lr);
       dx = ((a - 1.0f) - a * t) * fast_rcp(x); db = a * (t - 1.0f) * fast_rcp(b); da = fast_rcp(a) + lr * (1.0f - t);
       done(); return;

@@ -1,4 +1,9 @@
 """Program builders shared by the CPU and GPU tests."""
+import functools
+import gzip
+import json
+import os
+
 import numpy as np
 
 from genjax_amd import _abi as A
@@ -27,6 +32,69 @@ def one_site(kind: str, a, b=None, obs=None, rng=A.RNG_FLAT, c=None, d=None):
     if obs is None:
         return PackedProgram(sl, rng_mode=rng)
     return PackedProgram(sl, {"v": A.MODE_OBS_TAB}, {"v": obs}, rng_mode=rng)
+
+
+VECTOR_KINDS = ("dirichlet",)          # (with the categoricals: their own tables, not tests/golden/density_grid.json.gz)
+
+
+@functools.lru_cache(maxsize=None)
+def density_grid():
+    """tests/golden/density_grid.json.gz (tests/golden/make_density_grid.py): {kind: record of arrays}, read once and left unchanged"""
+    with gzip.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "density_grid.json.gz"), "rt") as f:
+        return json.load(f)
+
+
+def density_grid_program(kind: str):
+    """One row of density_grid() per particle: a carrier site p_i ~ uniform(-1e37, 1e37) per parameter (its own
+    gradient is 0, so its gradient row holds d/d(parameter) alone) and x ~ KIND(p0, ...), every site MODE_OBS_SLOT.  Selected for
+    gradients: every site but a discrete x.  -> (program, slot of x, slots of the parameters, index of x's site)"""
+    n = NPAR[kind]
+    sl = SiteList()
+    for j in range(n):
+        sl.add(f"p{j}", A.UNIFORM, [-1e37, 1e37])
+    sl.add("x", KIND[kind], [Param.value(f"p{j}") for j in range(n)])
+    addrs = [f"p{j}" for j in range(n)] + ["x"]
+    sel = tuple(a for a in addrs if a != "x" or KIND[kind] not in A.NO_GRADIENT_KINDS)
+    prog = PackedProgram(sl, {a: A.MODE_OBS_SLOT for a in addrs}, selected=sel)
+    return prog, prog.slot_of["x"], [prog.slot_of[f"p{j}"] for j in range(n)], n
+
+
+def density_grid_choices(rec, prog, x_slot, p_slots):
+    """the rows of one kind's record as particles: choices[slot][row]"""
+    ch = np.zeros((max(prog.n_slots, 1), len(rec["x"])), np.float32)
+    ch[x_slot] = np.asarray(rec["x"], np.float64)
+    for j, s in enumerate(p_slots):
+        ch[s] = np.asarray(rec["p"][j], np.float64)
+    return ch
+
+
+def density_grid_truth(rec):
+    """-> dict(lp [rows] (-inf outside the support), k_lp, grads {name: (truth with NaN where not asserted, kappa)}); "x" first, then
+    "p0".. in parameter order"""
+    f = lambda a: np.array([np.nan if v is None else v for v in a], np.float64)
+    lp = np.where(np.asarray(rec["neg_inf"], bool), -np.inf, f(rec["lp"]))
+    grads = {"x": (f(rec["dx"]), f(rec["k_dx"]))}
+    for j in range(len(rec["p"])):
+        grads[f"p{j}"] = (f(rec["dp"][j]), f(rec["k_dp"][j]))
+    return dict(lp=lp, k_lp=f(rec["k_lp"]), grads=grads)
+
+
+def density_grid_excess(got, want, kappa, at, rt):
+    """|got - want| / (at + rt |want| + 2 kappa) per row: the float tolerance plus the conditioning term (a kernel that forms (x - mu) / sd
+    or b x - a with one or two roundings answers for inputs a float32 step away; 2 = one step in each of two inputs).  Rows where
+    `want` is -inf must be -inf exactly (excess 0 or inf); rows where `want` is NaN are not asserted (excess 0); a NaN in `got`
+    anywhere else is inf."""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    with np.errstate(invalid="ignore"):
+        r = np.abs(got - want) / (at + rt * np.abs(want) + 2.0 * np.asarray(kappa, np.float64))
+    r = np.where(np.isneginf(want), np.where(np.isneginf(got), 0.0, np.inf), r)
+    r = np.where(np.isnan(want), 0.0, r)
+    return np.where(np.isnan(r), np.inf, r)
+
+
+def density_grid_rows(rec, rows, got=None):
+    """readable list of rows (for assertion messages): x, parameters[, what the code gave]"""
+    return [(i, rec["x"][i], tuple(c[i] for c in rec["p"])) + (() if got is None else (float(got[i]),)) for i in rows]
 
 
 def gmm(D=16, C=8, rng=A.RNG_FLAT, seed=0):
