@@ -234,7 +234,8 @@ bool expr_block_ok(const gjx_program* p, const gjx_param& q, int n_slots, int di
       case GJX_E_WHERE: if (!nodeok(e.a) || !nodeok(e.b) || !nodeok(e.c)) return false; break;
       case GJX_E_LINV: if (e.c < 1 || e.c > 64 || e.a < 0 || e.a + 1 + e.c > p->n_tab || e.b < 0 || (!plate && (e.b + e.c > n_slots || e.da || e.db))) return false; break;
       case GJX_E_LINN: if (e.c < 1 || e.c > 64 || e.a < 0 || e.a + 1 + e.c > p->n_tab || e.b < 0 || e.b + e.c > i || (e.da && !plate)) return false; break;
-      default: if (e.op < GJX_E_NEG || e.op > GJX_E_RECIP || !nodeok(e.a)) return false; break;
+      case GJX_E_LSEN: if (e.c < 1 || e.c > 64 || e.b < 0 || e.b + e.c > i || e.da || e.db) return false; break;
+      default: if (!((e.op >= GJX_E_NEG && e.op <= GJX_E_RECIP) || (e.op >= GJX_E_ERF && e.op <= GJX_E_EXPM1)) || !nodeok(e.a)) return false; break;
     }
   }
   return true;
@@ -359,6 +360,7 @@ Roll detect_roll(const gjx_program* p, bool any_stream = false) {     // any_str
               case GJX_E_VALUE: if (!moves_ok(ea.a, eb.a, 1)) return r; break;
               case GJX_E_LINV: if (eb.a != ea.a + (t - 1) * st[l].enode_dtab[k][i] || !moves_ok(ea.b, eb.b, ea.c)) return r; break;
               case GJX_E_LINN: if (eb.a != ea.a + (t - 1) * st[l].enode_dtab[k][i] || eb.b != ea.b) return r; break;
+              case GJX_E_LSEN: if (eb.b != ea.b) return r; break;       // (no table entries: nothing strides; c was compared above)
               default: if (eb.a != ea.a || eb.b != ea.b) return r; break;
             }
           }
@@ -708,7 +710,7 @@ std::vector<char> emit_expr_nodes(Emit& o, const gjx_program* prog, const gjx_pa
       case GJX_E_CONST: case GJX_E_VALUE: case GJX_E_LINV: break;
       case GJX_E_ADD: case GJX_E_SUB: case GJX_E_MUL: case GJX_E_DIV: case GJX_E_MAX: case GJX_E_MIN: case GJX_E_GT: need[e.a] = need[e.b] = 1; break;
       case GJX_E_WHERE: need[e.a] = need[e.b] = need[e.c] = 1; break;
-      case GJX_E_LINN: for (int t = 0; t < e.c; ++t) need[e.b + t] = 1; break;
+      case GJX_E_LINN: case GJX_E_LSEN: for (int t = 0; t < e.c; ++t) need[e.b + t] = 1; break;
       default: need[e.a] = 1; break;
     }
   }
@@ -720,7 +722,7 @@ std::vector<char> emit_expr_nodes(Emit& o, const gjx_program* prog, const gjx_pa
     ExprNode e = expr_node(prog, q, i);
     if (dtab && !dtab->empty()) e.da = (*dtab)[i];
     std::string r;
-    const std::string A = e.op >= GJX_E_ADD && e.op != GJX_E_LINV && e.op != GJX_E_LINN ? N(e.a) : "", B = N(e.b);
+    const std::string A = e.op >= GJX_E_ADD && e.op != GJX_E_LINV && e.op != GJX_E_LINN && e.op != GJX_E_LSEN ? N(e.a) : "", B = N(e.b);
     switch (e.op) {
       case GJX_E_CONST: r = T(e.a, e.da, 0); break;
       case GJX_E_VALUE: r = val(i, 0); break;
@@ -740,6 +742,15 @@ std::vector<char> emit_expr_nodes(Emit& o, const gjx_program* prog, const gjx_pa
       case GJX_E_LINN: {
         r = T(e.a, e.da, 0);
         for (int t = 0; t < e.c; ++t) r = "fmaf(" + T(e.a, e.da, 1 + t) + ", " + N(e.b + t) + ", " + r + ")";
+        break;
+      }
+      case GJX_E_LSEN: {      // the maximum (an fmaxf chain), the sum of exp(x - m), m + log(sum); every operand -inf: -inf
+        const std::string m = N(i) + "_m";
+        std::string mx = N(e.b), sum;
+        for (int t = 1; t < e.c; ++t) mx = "fmaxf(" + mx + ", " + N(e.b + t) + ")";
+        for (int t = 0; t < e.c; ++t) sum += (t ? " + " : "") + ("fast_exp(" + N(e.b + t) + " - " + m + ")");
+        o.f("%sconst float %s = %s;\n", ind, m.c_str(), mx.c_str());
+        r = m + " == -INFINITY ? " + m + " : " + m + " + fast_log(" + sum + ")";
         break;
       }
       default: r = "expr_unary(" + std::to_string(e.op) + ", " + A + ")"; break;
@@ -2158,7 +2169,7 @@ void hmc_emit_element(Emit& o, const gjx_program* prog, const HmcPlan& hp, int j
           case GJX_E_CONST: case GJX_E_VALUE: case GJX_E_LINV: break;
           case GJX_E_ADD: case GJX_E_SUB: case GJX_E_MUL: case GJX_E_DIV: case GJX_E_MAX: case GJX_E_MIN: case GJX_E_GT: need[e.a] = need[e.b] = 1; break;
           case GJX_E_WHERE: need[e.a] = need[e.b] = need[e.c] = 1; break;
-          case GJX_E_LINN: for (int t = 0; t < e.c; ++t) need[e.b + t] = 1; break;
+          case GJX_E_LINN: case GJX_E_LSEN: for (int t = 0; t < e.c; ++t) need[e.b + t] = 1; break;
           default: need[e.a] = 1; break;
         }
       }
@@ -2171,7 +2182,7 @@ void hmc_emit_element(Emit& o, const gjx_program* prog, const HmcPlan& hp, int j
           case GJX_E_LINV: for (int t = 0; t < e.c; ++t) live[i] = live[i] || hp.sel_of_slot[expr_leaf_reg(g_expr_prog, q, ri, k, i, t)] >= 0; break;
           case GJX_E_ADD: case GJX_E_SUB: case GJX_E_MUL: case GJX_E_DIV: case GJX_E_MAX: case GJX_E_MIN: live[i] = live[e.a] || live[e.b]; break;
           case GJX_E_WHERE: live[i] = live[e.b] || live[e.c]; break;
-          case GJX_E_LINN: for (int t = 0; t < e.c; ++t) live[i] = live[i] || live[e.b + t]; break;
+          case GJX_E_LINN: case GJX_E_LSEN: for (int t = 0; t < e.c; ++t) live[i] = live[i] || live[e.b + t]; break;
           default: live[i] = live[e.a]; break;
         }
       }
@@ -2202,6 +2213,9 @@ void hmc_emit_element(Emit& o, const gjx_program* prog, const HmcPlan& hp, int j
           case GJX_E_MIN: add(e.a, N(e.a) + " <= " + N(e.b) + " ? " + gi + " : 0.0f"); add(e.b, N(e.a) + " <= " + N(e.b) + " ? 0.0f : " + gi); break;
           case GJX_E_WHERE: add(e.b, N(e.a) + " != 0.0f ? " + gi + " : 0.0f"); add(e.c, N(e.a) + " != 0.0f ? 0.0f : " + gi); break;
           case GJX_E_LINN: for (int t = 0; t < e.c; ++t) add(e.b + t, gi + " * TAB(" + toff(e.a, e.da) + " + " + std::to_string(1 + t) + ")"); break;
+          case GJX_E_LSEN:
+            for (int t = 0; t < e.c; ++t) add(e.b + t, N(i) + " == -INFINITY ? 0.0f : " + gi + " * fast_exp(" + N(e.b + t) + " - " + N(i) + ")");
+            break;
           case GJX_E_CONST: case GJX_E_GT: break;
           default: add(e.a, gi + " * expr_unary_deriv(" + std::to_string(e.op) + ", " + N(e.a) + ", " + N(i) + ")"); break;
         }

@@ -402,6 +402,12 @@ GJX_DEV float one_minus_exp(float u) {
   if (u > -0.015625f) return -u * (1.0f + u * (0.5f + u * (0.166666667f + u * (0.0416666667f + u * 0.00833333333f))));
   return 1.0f - fast_exp(u);
 }
+// digamma on the whole line: below 0 by reflection, psi(x) = psi(1 - x) - pi / tan(pi x) (the argument of tan reduced to
+// [-1/2, 1/2]: tan has period pi); the poles at 0, -1, -2, ... give +-inf or NaN, never a finite wrong number
+GJX_DEV float digamma_real(float x) {
+  if (x > 0.0f) return digamma_f(x);
+  return digamma_f(1.0f - x) - 3.14159265f * fast_rcp(tanf(3.14159265f * (x - rintf(x))));
+}
 GJX_DEV float softplus(float x) { return fmaxf(x, 0.0f) + log1p_acc(fast_exp(-fabsf(x))); }
 GJX_DEV float sigmoid(float x) { return fast_rcp(1.0f + fast_exp(-x)); }
 
@@ -438,6 +444,10 @@ GJX_DEV float expr_unary(int op, float x) {
     case GJX_E_SIN: return sinf(x);
     case GJX_E_COS: return cosf(x);
     case GJX_E_LOG1P: return log1p_acc(x);
+    case GJX_E_ERF: return erff(x);
+    case GJX_E_ERFC: return erfcf(x);
+    case GJX_E_LGAMMA: return lgammaf(x);      // log |Gamma(x)|
+    case GJX_E_EXPM1: return expm1f(x);
     default: return fast_rcp(x);   // GJX_E_RECIP
   }
 }
@@ -456,6 +466,10 @@ GJX_DEV float expr_unary_deriv(int op, float x, float y) {
     case GJX_E_SIN: return cosf(x);
     case GJX_E_COS: return -sinf(x);
     case GJX_E_LOG1P: return fast_rcp(1.0f + x);
+    case GJX_E_ERF: return 1.12837917f * fast_exp(-x * x);         // 2 / sqrt(pi)
+    case GJX_E_ERFC: return -1.12837917f * fast_exp(-x * x);
+    case GJX_E_LGAMMA: return digamma_real(x);
+    case GJX_E_EXPM1: return y + 1.0f;
     default: return -y * y;        // GJX_E_RECIP
   }
 }
@@ -481,6 +495,14 @@ GJX_DEV void expr_forward(const gjx_param& p, const float* __restrict__ tab, Val
       case GJX_E_WHERE: r = ev[a] != 0.0f ? ev[b] : ev[c]; break;
       case GJX_E_LINV: { r = tab[a]; for (int e = 0; e < c; ++e) r = fmaf(tab[a + 1 + e], val(b + e), r); break; }
       case GJX_E_LINN: { r = tab[a]; for (int e = 0; e < c; ++e) r = fmaf(tab[a + 1 + e], ev[b + e], r); break; }
+      case GJX_E_LSEN: {      // the maximum first; every operand -inf: -inf, not NaN
+        float m = ev[b];
+        for (int e = 1; e < c; ++e) m = fmaxf(m, ev[b + e]);
+        float s = 0.0f;
+        for (int e = 0; e < c; ++e) s += fast_exp(ev[b + e] - m);
+        r = m == -INFINITY ? m : m + fast_log(s);
+        break;
+      }
       default: r = expr_unary(op, ev[a]); break;
     }
     ev[i] = r;
@@ -521,6 +543,7 @@ GJX_DEV void expr_backward(const gjx_param& p, int d, float g, const float* __re
       case GJX_E_WHERE: if (ev[a] != 0.0f) ad[b] += gi; else ad[c] += gi; break;
       case GJX_E_LINV: for (int e = 0; e < c; ++e) G.at(b + e) += gi * tab[a + 1 + e]; break;
       case GJX_E_LINN: for (int e = 0; e < c; ++e) ad[b + e] = fmaf(gi, tab[a + 1 + e], ad[b + e]); break;
+      case GJX_E_LSEN: if (ev[i] != -INFINITY) for (int e = 0; e < c; ++e) ad[b + e] = fmaf(gi, fast_exp(ev[b + e] - ev[i]), ad[b + e]); break;
       default: ad[a] = fmaf(gi, expr_unary_deriv(op, ev[a], ev[i]), ad[a]); break;
     }
   }

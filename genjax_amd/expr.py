@@ -14,6 +14,7 @@ A node is a hashable tuple:
     (op, a) / (op, a, b)                 unary / binary elementwise op, op in UNARY / BINARY
     ("where", cond, a, b)                cond != 0 ? a : b
     ("lin", bias, ((node, weight), ...)) bias + sum_k weight_k * node_k     (rows of W @ x: one device node per run of sources)
+    ("lse", (node, ...))                 log sum_k exp(node_k)                  (one device node per 64 operands: GJX_E_LSEN)
 """
 from __future__ import annotations
 
@@ -26,13 +27,29 @@ from . import _abi as A
 
 UNARY = {"neg": A.E_NEG, "exp": A.E_EXP, "log": A.E_LOG, "sqrt": A.E_SQRT, "square": A.E_SQUARE, "tanh": A.E_TANH,
          "sigmoid": A.E_SIGMOID, "softplus": A.E_SOFTPLUS, "abs": A.E_ABS, "sin": A.E_SIN, "cos": A.E_COS, "log1p": A.E_LOG1P,
-         "recip": A.E_RECIP}
+         "recip": A.E_RECIP, "erf": A.E_ERF, "erfc": A.E_ERFC, "lgamma": A.E_LGAMMA, "expm1": A.E_EXPM1}
 BINARY = {"add": A.E_ADD, "sub": A.E_SUB, "mul": A.E_MUL, "div": A.E_DIV, "max": A.E_MAX, "min": A.E_MIN, "gt": A.E_GT}
+
+
+
+def _lgamma1(x: float) -> float:
+    try:
+        return math.lgamma(x)
+    except ValueError:              # a pole (0, -1, -2, ...): log |Gamma| = +inf
+        return math.inf
+
+
+def _np_special(f: Callable) -> Callable:
+    """the standard library's float64 erf / erfc / lgamma, elementwise over arrays (NumPy itself has none of them)"""
+    uf = np.frompyfunc(lambda v: f(v) if v == v else v, 1, 1)
+    return lambda x: np.asarray(uf(np.asarray(x, np.float64)), np.float64)[()]
+
 
 _NP_UNARY = {
     "neg": lambda x: -x, "exp": np.exp, "log": np.log, "sqrt": np.sqrt, "square": lambda x: x * x, "tanh": np.tanh,
     "sigmoid": lambda x: 1.0 / (1.0 + np.exp(-x)), "softplus": lambda x: np.logaddexp(0.0, x), "abs": np.abs, "sin": np.sin,
     "cos": np.cos, "log1p": np.log1p, "recip": lambda x: 1.0 / x,
+    "erf": _np_special(math.erf), "erfc": _np_special(math.erfc), "lgamma": _np_special(_lgamma1), "expm1": np.expm1,
 }
 
 
@@ -136,6 +153,33 @@ def lin(bias: float, terms: Sequence) -> tuple:
     return ("lin", b, ts)
 
 
+def _np_logsumexp(rows):
+    """log sum exp over axis 0, float64: the maximum taken out first; every operand -inf gives -inf (not NaN)"""
+    a = np.stack(np.broadcast_arrays(*[np.asarray(r, np.float64) for r in rows]))
+    with np.errstate(all="ignore"):
+        m = a.max(axis=0)
+        m0 = np.where(np.isfinite(m), m, 0.0)
+        return (m0 + np.log(np.exp(a - m0).sum(axis=0)))[()]
+
+
+def lse(nodes: Sequence[tuple]) -> tuple:
+    """log sum exp of the nodes: an lse of lse's stays one node, constant operands fold into one, one operand is itself"""
+    ops: list = []
+    consts: list = []
+    for n in nodes:
+        for m in (n[1] if n[0] == "lse" else (n,)):
+            (consts if is_const(m) else ops).append(m)
+    if consts:
+        c = float(_np_logsumexp([m[1] for m in consts]))
+        if not ops:
+            return const(c)
+        if c != -math.inf:
+            ops.append(const(c))
+    if not ops:
+        raise ValueError("lse of no operands")
+    return ops[0] if len(ops) == 1 else ("lse", tuple(ops))
+
+
 def add(a, b):
     # sums of (scaled) nodes stay ONE linear form: a + b + 2 c is one device node over three sources
     if a[0] in ("lin", "c") or b[0] in ("lin", "c"):
@@ -158,6 +202,8 @@ def _children(n):
         return ()
     if k == "lin":
         return tuple(m for m, _ in n[2])
+    if k == "lse":
+        return n[1]
     return n[1:]
 
 
@@ -193,6 +239,8 @@ def rewrite_leaves(outs: Sequence[tuple], fn: Callable) -> list:
             r = n if r is None else r
         elif k == "lin":
             r = lin(n[1], [(go(m), w) for m, w in n[2]])
+        elif k == "lse":
+            r = lse([go(m) for m in n[1]])
         elif k == "where":
             r = where(go(n[1]), go(n[2]), go(n[3]))
         elif k in UNARY:
@@ -217,7 +265,8 @@ def evaluate(outs: Sequence[tuple], leaf: Callable, xp=np):
         import torch
         return {"neg": lambda v: -v, "exp": torch.exp, "log": torch.log, "sqrt": torch.sqrt, "square": lambda v: v * v, "tanh": torch.tanh,
                 "sigmoid": torch.sigmoid, "softplus": torch.nn.functional.softplus, "abs": torch.abs, "sin": torch.sin, "cos": torch.cos,
-                "log1p": torch.log1p, "recip": lambda v: 1.0 / v}[op](x)
+                "log1p": torch.log1p, "recip": lambda v: 1.0 / v, "erf": torch.erf, "erfc": torch.erfc, "lgamma": torch.lgamma,
+                "expm1": torch.expm1}[op](x)
 
     def go(n):
         if n in memo:
@@ -231,6 +280,14 @@ def evaluate(outs: Sequence[tuple], leaf: Callable, xp=np):
             r = n[1]
             for m, w in n[2]:
                 r = r + w * go(m)
+        elif k == "lse":
+            rows = [go(m) for m in n[1]]
+            if not is_t:
+                r = _np_logsumexp(rows)
+            else:
+                import torch
+                like = next((x for x in rows if isinstance(x, torch.Tensor)), None)
+                r = torch.logsumexp(torch.stack(torch.broadcast_tensors(*[_as_arr(x, xp, like) for x in rows])), 0)
         elif k == "where":
             c, a, b = go(n[1]), go(n[2]), go(n[3])
             r = xp.where(_as_arr(c, xp) != 0, _as_arr(a, xp, c), _as_arr(b, xp, c))
@@ -303,32 +360,57 @@ def lower(outs: Sequence[tuple], leaf_place: Callable, push: Callable) -> tuple[
             const_off[k] = push(np.asarray([x], np.float32))
         return const_off[k]
 
-    def top(n, fresh: bool = False) -> int:
-        """device node of host node n (its children are lowered first); fresh: emit the top node again even if it exists —
-        what puts the operands of a LINN node, and the outputs of the block, at consecutive indices"""
-        if not fresh and n in index:
-            return index[n]
+    def prepare(n) -> tuple:
+        """everything host node n needs below its top node is emitted; -> the top node (op, a, b, c), not yet emitted"""
         k = n[0]
         if k == "c":
-            i = emit(A.E_CONST, const_at(n[1]))
-        elif k == "v":
+            return (A.E_CONST, const_at(n[1]), 0, 0)
+        if k == "v":
             where_, at = leaf_place(n[1], n[2])
-            i = emit(A.E_VALUE if where_ == "slot" else A.E_CONST, at)
-        elif k == "lin":
-            i = lower_lin(n)
-        elif k == "where":
-            c_, a_, b_ = top(n[1]), top(n[2]), top(n[3])
-            i = emit(A.E_WHERE, c_, a_, b_)
-        elif k in UNARY:
-            a_ = top(n[1])
-            i = emit(UNARY[k], a_)
-        else:
-            a_, b_ = top(n[1]), top(n[2])
-            i = emit(BINARY[k], a_, b_)
+            return (A.E_VALUE if where_ == "slot" else A.E_CONST, at, 0, 0)
+        if k == "lin":
+            return prepare_lin(n)
+        if k == "lse":
+            return prepare_lse(n[1])
+        if k == "where":
+            return (A.E_WHERE, top(n[1]), top(n[2]), top(n[3]))
+        if k in UNARY:
+            return (UNARY[k], top(n[1]), 0, 0)
+        a_, b_ = top(n[1]), top(n[2])
+        return (BINARY[k], a_, b_, 0)
+
+    def top(n, fresh: bool = False) -> int:
+        """device node of host node n (its children are lowered first); fresh: emit the top node again even if it exists —
+        what puts the operands of a LINN / LSEN node, and the outputs of the block, at consecutive indices"""
+        if not fresh and n in index:
+            return index[n]
+        i = emit(*prepare(n))
         index.setdefault(n, i)
         return i
 
-    def lower_lin(n) -> int:
+    def run_of(ms) -> int:
+        """the host nodes ms at consecutive device nodes (what LINN and LSEN range over): everything below their top nodes first,
+        then the top nodes, each emitted afresh; -> the first index"""
+        tops = [prepare(m) for m in ms]
+        first = len(nodes)
+        for m, t_ in zip(ms, tops):
+            index.setdefault(m, emit(*t_))
+        return first
+
+    def prepare_lse(ops) -> tuple:
+        if len(ops) <= 64:
+            return (A.E_LSEN, 0, run_of(ops), len(ops))
+        # more than 64 operands: an LSEN per chunk of 64 (log sum exp is associative), then one over the chunks' results
+        chunks = [ops[c0:c0 + 64] for c0 in range(0, len(ops), 64)]
+        if len(chunks) > 64:
+            raise ExprTooLarge(f"a log-sum-exp over {len(ops)} operands")
+        tops = [(A.E_LSEN, 0, run_of(ch), len(ch)) for ch in chunks]
+        first = len(nodes)
+        for t_ in tops:
+            emit(*t_)
+        return (A.E_LSEN, 0, first, len(tops))
+
+    def prepare_lin(n) -> tuple:
         bias, terms = n[1], n[2]
         lat, rest = [], []
         for m, w in terms:
@@ -338,9 +420,9 @@ def lower(outs: Sequence[tuple], leaf_place: Callable, push: Callable) -> tuple[
                     lat.append((at, w))
                     continue
             rest.append((m, w))
-        parts: list[int] = []
         lat.sort()
         # runs of consecutive slots -> LINV (choices read straight from registers / rows); small gaps are bridged with zero weights
+        runs: list = []
         j = 0
         while j < len(lat):
             run = [lat[j]]
@@ -350,42 +432,45 @@ def lower(outs: Sequence[tuple], leaf_place: Callable, push: Callable) -> tuple[
                 run.append(lat[j + 1])
                 j += 1
             j += 1
+            runs.append(run)
+        parts: list[tuple] = []              # the top nodes of the parts; all but the last are emitted as they come
+        for run in runs:
             b_here = bias if not parts else 0.0
             off = push(np.asarray([b_here] + [w for _, w in run], np.float32))
-            parts.append(emit(A.E_LINV, off, run[0][0], len(run)))
+            parts.append((A.E_LINV, off, run[0][0], len(run)))
         # everything else -> LINN over operands emitted at consecutive indices (chunks of 64)
+        done = [emit(*t_) for t_ in parts[:-1]]
         for c0 in range(0, len(rest), 64):
             chunk = rest[c0:c0 + 64]
-            for m, _ in chunk:                     # children first, so that the fresh tops below are consecutive
-                if m[0] not in ("c", "v"):
-                    for ch in _children(m):
-                        top(ch)
-            first = None
-            for m, _ in chunk:
-                i = top(m, fresh=True)
-                first = i if first is None else first
+            if len(done) < len(parts):
+                done.append(emit(*parts[-1]))
+            first = run_of([m for m, _ in chunk])
             b_here = bias if not parts else 0.0
             off = push(np.asarray([b_here] + [w for _, w in chunk], np.float32))
-            parts.append(emit(A.E_LINN, off, first, len(chunk)))
-        acc = parts[0]
-        for p_ in parts[1:]:
+            parts.append((A.E_LINN, off, first, len(chunk)))
+        if len(parts) == 1:
+            return parts[0]
+        if len(done) < len(parts):
+            done.append(emit(*parts[-1]))
+        acc = done[0]
+        for p_ in done[1:-1]:
             acc = emit(A.E_ADD, acc, p_)
-        return acc
+        return (A.E_ADD, acc, done[-1], 0)
 
     outs = list(outs)
     for n in outs:                                  # everything below the outputs
-        if n[0] == "lin":
-            continue                                # (a linear output is emitted whole, below)
+        if n[0] in ("lin", "lse"):
+            continue                                # (a linear or log-sum-exp output is emitted whole, below)
         for ch in _children(n):
             top(ch)
     first_out = None
     if len(outs) == 1:
         i = top(outs[0])
         if i != len(nodes) - 1:
-            i = top(outs[0], fresh=True) if outs[0][0] != "lin" else emit(A.E_MAX, i, i)
+            i = top(outs[0], fresh=True) if outs[0][0] not in ("lin", "lse") else emit(A.E_MAX, i, i)
     else:
         # outputs are the LAST len nodes, in order: linear outputs may need several nodes each, so they go first and are copied
-        pre = [top(n) if n[0] == "lin" else None for n in outs]
+        pre = [top(n) if n[0] in ("lin", "lse") else None for n in outs]
         for n, p_ in zip(outs, pre):
             i = emit(A.E_MAX, p_, p_) if p_ is not None else top(n, fresh=True)     # max(x, x): the identity, gradient to x
             first_out = i if first_out is None else first_out

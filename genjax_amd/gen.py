@@ -28,7 +28,8 @@ from .program import MissingAddress, PackedProgram, Param, SiteList
 
 __all__ = [
     "gen", "StaticGenerativeFunction", "Trace", "Distribution", "take", "where", "cond", "const", "exp",
-    "softplus", "sigmoid", "tanh", "log", "sqrt", "square", "sin", "cos", "log1p", "maximum", "minimum", "dot", "normal", "flip", "bernoulli", "beta", "categorical", "uniform", "mv_normal_diag",
+    "softplus", "sigmoid", "tanh", "log", "sqrt", "square", "sin", "cos", "log1p", "maximum", "minimum", "dot",
+    "erf", "erfc", "lgamma", "expm1", "logsumexp", "abs", "normal", "flip", "bernoulli", "beta", "categorical", "uniform", "mv_normal_diag",
     "exponential", "half_normal", "laplace", "log_normal", "cauchy", "gamma", "Marginal", "ScanCombinator",
 ]
 
@@ -41,8 +42,61 @@ class NotSupportedInModelBody(TypeError):
 
 
 class Sym:
-    __array_ufunc__ = None  # numpy binary operators defer to our reflected methods
     __array_priority__ = 1000
+
+    # NumPy calls on symbolic values take the same code paths as the operators and the genjax.* functions: np.exp(site) is the closed
+    # GJX_XF_EXP form, ndarray * sym is sym.__rmul__(ndarray) (what the binary operators deferred to while __array_ufunc__ was None).
+    # Ufuncs are mapped by NAME, so that scipy.special.erf / erfc / gammaln / expit work without this module importing scipy.
+    def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
+        name = ufunc.__name__
+        if method == "reduce" and name == "add" and len(inputs) == 1:
+            return _np_reduce("sum", inputs, dict({"axis": 0}, **kwargs))      # (np.add.reduce: axis defaults to 0)
+        if method != "__call__" or name not in _UFUNCS or any(v is not None for v in kwargs.values()):
+            what = f"np.{name}" + ("" if method == "__call__" else f".{method}") + (f" with {sorted(kwargs)}" if method == "__call__" and name in _UFUNCS else "")
+            raise NotSupportedInModelBody(f"{what} of an expression of choices is not supported in a model body")
+        return _UFUNCS[name](*inputs)
+
+    def __array_function__(self, func, types, args, kwargs):
+        name = func.__name__
+        if name in ("sum", "mean", "prod", "max", "amax", "min", "amin", "cumsum"):
+            return _np_reduce({"amax": "max", "amin": "min"}.get(name, name), args, kwargs)
+        if name in ("where", "dot") and not kwargs:
+            return {"where": where, "dot": dot}[name](*args)
+        if name in ("abs", "absolute") and not kwargs:
+            return abs_(*args)
+        raise NotSupportedInModelBody(f"np.{name} of an expression of choices is not supported in a model body")
+
+    # reductions over the elements of a vector (axis None, 0 or -1: there is one axis).  Sums of affine forms stay affine (a ones-row
+    # matrix product: the closed forms); of general expressions they are linear forms (one device node per output); prod / max / min are
+    # chains of the binary ops
+    def _reduce_dim(self, axis, keepdims) -> int:
+        if keepdims or axis not in (None, 0, -1):
+            raise NotSupportedInModelBody("reductions in a model body take axis None, 0 or -1 and no keepdims")
+        if not hasattr(self, "dim"):
+            raise NotSupportedInModelBody(f"a reduction of {type(self).__name__} is not supported in a model body")
+        return self.dim
+
+    def sum(self, axis=None, keepdims=False): return self.__rmatmul__(np.ones((1, self._reduce_dim(axis, keepdims))))
+
+    def mean(self, axis=None, keepdims=False):
+        d = self._reduce_dim(axis, keepdims)
+        return self.__rmatmul__(np.full((1, d), 1.0 / d))
+
+    def cumsum(self, axis=None):
+        d = self._reduce_dim(axis, False)
+        return self.__rmatmul__(np.tril(np.ones((d, d))))
+
+    def _fold(self, op: str, axis, keepdims) -> "Expr":
+        self._reduce_dim(axis, keepdims)
+        es = self._expr().elems
+        acc = es[0]
+        for e in es[1:]:
+            acc = E.binary(op, acc, e)
+        return Expr([acc])
+
+    def prod(self, axis=None, keepdims=False): return self._fold("mul", axis, keepdims)
+    def max(self, axis=None, keepdims=False): return self._fold("max", axis, keepdims)
+    def min(self, axis=None, keepdims=False): return self._fold("min", axis, keepdims)
 
     def as_param(self) -> Param:  # pragma: no cover - abstract
         raise NotImplementedError
@@ -81,7 +135,14 @@ class Sym:
         o = np.asarray(o, np.float64)
         return self.__rmatmul__(o if o.ndim == 1 else o.T)
 
+    def __abs__(self): return _eun("abs", self)
+
+    def __rpow__(self, base):               # 2.0 ** x = exp(x ln 2): on an affine x the closed GJX_XF_EXP form
+        return exp(self * np.log(np.asarray(base, np.float64)))
+
     def __pow__(self, k):
+        if isinstance(k, Sym):              # a ** b = exp(b log a)
+            return _eun("exp", _ebin("mul", k, _eun("log", self)))
         k = float(k)
         if k == 1.0:
             return self
@@ -454,6 +515,31 @@ sin = _fn("sin", np.sin)
 cos = _fn("cos", np.cos)
 log1p = _fn("log1p", np.log1p)
 abs_ = _fn("abs", np.abs)
+abs = abs_                  # the public name (it shadows the builtin inside this module only, which does not use it)
+erf = _fn("erf", E._NP_UNARY["erf"])
+erfc = _fn("erfc", E._NP_UNARY["erfc"])
+lgamma = _fn("lgamma", E._NP_UNARY["lgamma"])
+expm1 = _fn("expm1", np.expm1)
+
+
+def logsumexp(x, axis=None, keepdims=False):
+    """``jax.nn.logsumexp`` over a vector of numbers or of expressions of earlier choices: ONE device node (GJX_E_LSEN) per 64 operands"""
+    if isinstance(x, (list, tuple)) and any(isinstance(it, Sym) for it in x):
+        x = array(x)
+    if isinstance(x, Sym):
+        x._reduce_dim(axis, keepdims)
+        return Expr([E.lse(x._expr().elems)])
+    a = np.asarray(x, np.float64)
+    r = E._np_logsumexp(list(a.ravel()) if axis is None else list(np.moveaxis(a, axis, 0)))
+    return np.expand_dims(r, tuple(range(a.ndim)) if axis is None else axis) if keepdims else r
+
+
+def _logaddexp(a, b):
+    a, b = _to_expr(a), _to_expr(b)
+    n = max(a.dim, b.dim)
+    if a.dim not in (1, n) or b.dim not in (1, n):
+        raise NotSupportedInModelBody(f"cannot broadcast expressions of {a.dim} and {b.dim} elements")
+    return Expr([E.lse([a.elems[i % a.dim], b.elems[i % b.dim]]) for i in range(n)])
 
 
 def maximum(a, b):
@@ -479,6 +565,36 @@ def dot(a, b):
     if isinstance(a, Sym):
         return a @ np.asarray(b, np.float64)
     return np.dot(a, b)
+
+
+def _np_reduce(name: str, args, kwargs):
+    """np.sum(x) / np.add.reduce(x) / ...: the method of the same name; arguments NumPy adds that change nothing are accepted"""
+    kw = {k: v for k, v in kwargs.items() if v is not None and not (k == "keepdims" and v is False) and v is not np._NoValue}
+    x, rest = args[0], list(args[1:])
+    if rest:
+        kw["axis"] = rest.pop(0)
+    if rest or set(kw) - {"axis", "keepdims"} or not isinstance(x, Sym):
+        raise NotSupportedInModelBody(f"np.{name} of an expression of choices takes axis (None, 0, -1) only")
+    return getattr(x, name)(**kw)
+
+
+def _op2(fwd: str, rev: str) -> Callable:
+    """a binary ufunc as the operator it stands for: the Sym operand's own method — the reflected one when the array is on the left"""
+    def f(a, b):
+        return getattr(a, fwd)(b) if isinstance(a, Sym) else getattr(b, rev)(a)
+    return f
+
+
+_UFUNCS = {
+    "add": _op2("__add__", "__radd__"), "subtract": _op2("__sub__", "__rsub__"), "multiply": _op2("__mul__", "__rmul__"),
+    "divide": _op2("__truediv__", "__rtruediv__"), "true_divide": _op2("__truediv__", "__rtruediv__"),
+    "power": _op2("__pow__", "__rpow__"), "float_power": _op2("__pow__", "__rpow__"), "matmul": _op2("__matmul__", "__rmatmul__"),
+    "greater": _op2("__gt__", "__lt__"), "less": _op2("__lt__", "__gt__"), "greater_equal": _op2("__ge__", "__le__"),
+    "less_equal": _op2("__le__", "__ge__"), "negative": lambda x: -x, "reciprocal": lambda x: x ** -1.0,
+    "exp": exp, "log": log, "sqrt": sqrt, "square": square, "tanh": tanh, "sin": sin, "cos": cos, "log1p": log1p, "expm1": expm1,
+    "absolute": abs_, "fabs": abs_, "maximum": maximum, "minimum": minimum, "logaddexp": _logaddexp,
+    "erf": erf, "erfc": erfc, "gammaln": lgamma, "expit": sigmoid,
+}
 
 
 # ---------------------------------------------------------------------------------------------

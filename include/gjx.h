@@ -147,7 +147,13 @@ enum {
   GJX_E_WHERE = 22,   /* node a != 0 ? node b : node c                                                  */
   GJX_E_LINV = 23,    /* tab[a] + sum_{e < c} tab[a + 1 + e] * choices[b + e][i]: bias and weights contiguous in the table */
   GJX_E_LINN = 24,    /* tab[a] + sum_{e < c} tab[a + 1 + e] * node (b + e)                              */
-  GJX_E_OP_MAX = 25
+  GJX_E_ERF = 25,     /* erf(node a)          gradient 2/sqrt(pi) exp(-a^2); any real a                  */
+  GJX_E_ERFC = 26,    /* 1 - erf(node a)      gradient -2/sqrt(pi) exp(-a^2); any real a                 */
+  GJX_E_LGAMMA = 27,  /* log|Gamma(node a)|   gradient digamma(a) (a < 0: by reflection); a not 0, -1, -2, ... */
+  GJX_E_EXPM1 = 28,   /* exp(node a) - 1      gradient exp(a), accurate near 0; any real a               */
+  GJX_E_LSEN = 29,    /* log sum_{e < c} exp(node (b + e)), 1 <= c <= 64, a unused; -inf if every operand is -inf;
+                         gradient to node (b + e): exp(node (b + e) - result), 0 where the result is -inf */
+  GJX_E_OP_MAX = 30
 };
 #define GJX_EXPR_MAX_NODES 96
 #define GJX_EXPR_NODE_FLOATS 6
