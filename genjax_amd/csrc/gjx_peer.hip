@@ -97,8 +97,8 @@ static int peer_ctx_create(int32_t n_ranks, int32_t rank, int64_t K_local, int32
   // the words of the one-launch resampling step (twice, for alternating calls: 4 x [MAX_RANKS] u64 + this rank's tile granules [nt])
   const size_t NT = (size_t)c->NT;
   size_t r = 0;
-  c->r_aggA = r; r = align_up(r + 8 * NT * kPfCorePad);   // (one granule per 64-byte line)
-  c->r_aggB = r; r = align_up(r + 8 * NT * kPfCorePad);
+  c->r_aggA = r; r = align_up(r + 8 * NT * kGranulePad);   // (one granule per 64-byte line)
+  c->r_aggB = r; r = align_up(r + 8 * NT * kGranulePad);
   c->r_bsum = r; r = align_up(r + 12 * NT);
   c->r_bmax = r; r = align_up(r + 12 * NT);
   c->r_ready = r; r = align_up(r + 4 * (size_t)kPfHostMaxTiles);
@@ -462,23 +462,8 @@ __global__ __launch_bounds__(256) void k_peer_resample_gather(PrgArgs a) {
   if (a.mode == 2) mx_r = block_ref_max(2, a.lse, a.n_partials, fred, &sm_sum);      // this rank's {max, sumexp} (ends with a barrier)
   else __syncthreads();                                                             // (sPF / s_dead visible)
   // ---- own tile: exponent, fixed-point weights, total -> local granule ----
-  {
-    float m = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k) m = fmaxf(m, xv[k]);
-    const float wm = wave_max_dpp(m);
-    if (lane == 0) s_tm[wid] = wm;
-  }
-  __syncthreads();
-  const int eb = tile_exponent(fmaxf(fmaxf(s_tm[0], s_tm[1]), fmaxf(s_tm[2], s_tm[3])));
-  {
-    uint64_t qs = 0;
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k) qs += (i0 + k < K) ? tile_q(xv[k], eb) : 0;
-    const uint64_t wt = wave_sum_u64(qs);
-    if (lane == 0) wsum[wid] = wt;
-  }
-  __syncthreads();
+  uint64_t qown[ITEMS], incown;
+  const int eb = tile_quantise<256, ITEMS>(xv, s_tm, wsum, qown, incown);
   const bool verify = a.verify != 0;
   auto verify_failed = [&]() { __hip_atomic_fetch_or(&a.ctrl[2], kStatusVerifyMismatch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
   if (verify) {
@@ -494,7 +479,7 @@ __global__ __launch_bounds__(256) void k_peer_resample_gather(PrgArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
-  if (tid == 0) store_scoped_u64(&a.agg[blockIdx.x], tile_granule(tag4, eb, wsum[0] + wsum[1] + wsum[2] + wsum[3]), sys);
+  if (tid == 0) store_scoped_u64(&a.agg[blockIdx.x], tile_granule(tag4, eb, sum_partials<4>(wsum)), sys);
   if (blockIdx.x == 0 && a.mode == 2 && sys && tid < G)          // this rank's LSE pair, to every rank (ordered before the hop-1 word below)
     store_scoped_u64(peer_ptr(a.wP + a.rank, sPF[tid]), pack_f2(mx_r, sm_sum), true);
   // ---- all-gather of this rank's granules (local) ----
@@ -510,8 +495,9 @@ __global__ __launch_bounds__(256) void k_peer_resample_gather(PrgArgs a) {
         }
         if ((v >> 60) != tag4) { timed_out(); v = 0; }
       }
-      const uint64_t S = v & ((1ull << 40) - 1);
-      const int e = S ? (int)((v >> 40) & 0xFFFFFu) + kTileDead : kTileDead;
+      uint64_t S;
+      int e;
+      tile_granule_unpack(v, S, e);
       P[b + 1] = S;
       Eb[b] = e;
       em = fmaxf(em, (float)e);
@@ -522,25 +508,8 @@ __global__ __launch_bounds__(256) void k_peer_resample_gather(PrgArgs a) {
     __syncthreads();
     return (int)fmaxf(fmaxf(s_em[0], s_em[1]), fmaxf(s_em[2], s_em[3]));
   };
-  // P[b + 1] = S_b >> (E - e_b), then the inclusive prefix in place: thread t owns the entries [t per, (t + 1) per)
-  auto shift_and_prefix = [&](int E) {
-    const int per = (nb + 255) >> 8;
-    const int e0 = tid * per < nb ? tid * per : nb, e1 = (e0 + per) < nb ? (e0 + per) : nb;
-    uint64_t loc = 0;
-    for (int e = e0; e < e1; ++e) {
-      const int sh = E - Eb[e];
-      const uint64_t g = sh < 64 ? P[e + 1] >> sh : 0;
-      P[e + 1] = g;
-      loc += g;
-    }
-    const uint64_t inc = wave_scan_u64(loc);
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    uint64_t run = inc - loc;
-    for (int w = 0; w < wid; ++w) run += wsum[w];
-    for (int e = e0; e < e1; ++e) { run += P[e + 1]; P[e + 1] = run; }
-    __syncthreads();
-  };
+  // P[b + 1] = S_b >> (E - e_b), then the inclusive prefix in place
+  auto shift_and_prefix = [&](int E) { prefix_in_place<256>(P, nb, wsum, [&](int b) { return E - Eb[b]; }); };
   budget = kPollBudget;                          // the local gather: blocks of one launch
   int E = read_granules(a.agg, true);
   // ---- hop 1: the largest tile exponent over all ranks ----
@@ -657,28 +626,13 @@ __global__ __launch_bounds__(256) void k_peer_resample_gather(PrgArgs a) {
       uint64_t Tl[ITEMS];
       int tile[ITEMS];
       bool in[ITEMS];
-      // rank-local thresholds; a block's slots draw from tiles near its own index when the source is its own rank: the nine
-      // boundaries of the eight tiles around blockIdx.x are read together, otherwise (and outside the window) a descent
-      const int wlo = (int)blockIdx.x - 4 < 0 ? 0 : ((int)blockIdx.x - 4 > nb - 8 ? (nb - 8 < 0 ? 0 : nb - 8) : (int)blockIdx.x - 4);
-      uint64_t Pw[9];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Pw[k] = P[wlo + k < nb ? wlo + k : nb];
+      // rank-local thresholds (a slot of another rank searches threshold 0: the thresholds of a lane are not monotone here, so every
+      // slot takes the single-slot search; the window around blockIdx.x pays off when the source is the block's own rank)
 #pragma unroll
       for (int k = 0; k < ITEMS; ++k) {
         in[k] = gk[k] == gs;
         Tl[k] = in[k] ? T[k] - RB[gs] : 0;
-        int tl = wlo;
-        if (Tl[k] >= Pw[0] && Tl[k] < Pw[8]) {
-#pragma unroll
-          for (int w = 1; w < 8; ++w) tl += Pw[w] <= Tl[k] ? 1 : 0;
-        } else {
-          tl = 0;
-#pragma unroll
-          for (int sft = kPrgMaxTiles >> 1; sft >= 1; sft >>= 1) {
-            const int p = tl + sft;              // P[p] = inclusive prefix of tile p - 1
-            if (p <= nb - 1 && P[p] <= Tl[k]) tl = p;
-          }
-        }
+        const int tl = source_tile(P, nb, (int)blockIdx.x, Tl[k]);
         tile[k] = tl;
         Tl[k] = (Tl[k] - P[tl]) << (E - Eb[tl]);                  // residual in the source tile's own units
         const int64_t jslot = a.offset + i0 + k;
@@ -701,54 +655,29 @@ __global__ __launch_bounds__(256) void k_peer_resample_gather(PrgArgs a) {
       };
       for (int idx = next_live(0); idx < ntiles;) {
         const int nidx = next_live(idx + CH);
-        uint64_t qi[CH][ITEMS], sacc[CH], inc[CH];
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
+        // (the barrier inside the round: every lane is done searching the previous round's cumL)
+        rescan_round<256, TILE, ITEMS, CH>(cumL, &s_wtot[0][0], [&](int c, int, uint64_t (&q)[ITEMS]) {
           const bool on = idx + c < ntiles;
           float nv[ITEMS];
 #pragma unroll
           for (int k = 0; k < ITEMS; ++k) nv[k] = -INFINITY;
           if (on) load_tile(tmin + idx + c, nv);
           const int es = on ? Eb[tmin + idx + c] : kTileDead;
-          sacc[c] = 0;
 #pragma unroll
-          for (int k = 0; k < ITEMS; ++k) { sacc[c] += on ? tile_q(nv[k], es) : 0; qi[c][k] = sacc[c]; }
-          inc[c] = sacc[c];
-        }
-#pragma unroll
-        for (int c = 0; c < CH; ++c) inc[c] = wave_scan_u64(inc[c]);
-        if (lane == 63) {
-#pragma unroll
-          for (int c = 0; c < CH; ++c) s_wtot[c][wid] = inc[c];
-        }
-        __syncthreads();                         // also: every lane is done searching the previous round's cumL
-        if (verify && tid < CH && idx + tid < ntiles) {
-          // the log-weights just pulled must quantise to the total their owner published in the tile's granule
-          const int ts = tmin + idx + tid, sh = E - Eb[ts];
-          const uint64_t tot = s_wtot[tid][0] + s_wtot[tid][1] + s_wtot[tid][2] + s_wtot[tid][3];
-          if ((sh < 64 ? tot >> sh : 0) != P[ts + 1] - P[ts]) verify_failed();
-        }
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          uint64_t base = inc[c] - sacc[c];
-          for (int w = 0; w < wid; ++w) base += s_wtot[c][w];
-#pragma unroll
-          for (int k = 0; k < ITEMS; ++k) cumL[c * TILE + tid * ITEMS + k] = base + qi[c][k];
-        }
-        __syncthreads();
+          for (int k = 0; k < ITEMS; ++k) q[k] = tile_q(nv[k], es);
+          return true;
+        }, [&] {
+          if (verify && tid < CH && idx + tid < ntiles) {
+            // the log-weights just pulled must quantise to the total their owner published in the tile's granule
+            const int ts = tmin + idx + tid, sh = E - Eb[ts];
+            const uint64_t tot = sum_partials<4>(s_wtot[tid]);
+            if ((sh < 64 ? tot >> sh : 0) != P[ts + 1] - P[ts]) verify_failed();
+          }
+        });
 #pragma unroll
         for (int k = 0; k < ITEMS; ++k) {
           const int kpos = tile[k] - tmin;
-          if (in[k] && kpos >= idx && kpos < idx + CH) {
-            const uint64_t* cm = cumL + (kpos - idx) * TILE;
-            int pos = 0;                           // number of entries <= the residual, 4-ary
-#pragma unroll
-            for (int q = TILE >> 2; q >= 1; q >>= 2) {
-              const uint64_t pa = cm[pos + q - 1], pb = cm[pos + 2 * q - 1], pc = cm[pos + 3 * q - 1];
-              pos += (pa <= Tl[k] ? q : 0) + (pb <= Tl[k] ? q : 0) + (pc <= Tl[k] ? q : 0);
-            }
-            anc[k] = (gs * nb + tile[k]) * TILE + pos;
-          }
+          if (in[k] && kpos >= idx && kpos < idx + CH) anc[k] = (gs * nb + tile[k]) * TILE + rank_in_tile<TILE>(cumL + (kpos - idx) * TILE, Tl[k]);
         }
         idx = nidx;
       }

@@ -28,7 +28,6 @@
 namespace gjx {
 
 constexpr int kPfCoreThreads = 1024;
-constexpr int kPfCorePad = 8;             // granules one per 64-byte line
 
 struct PfCoreArgs {
   int T;                                  // the run has T steps; this launch runs t = 1 .. T-1 and finishes the records of 0 .. T-1
@@ -39,7 +38,7 @@ struct PfCoreArgs {
   int nt;                                 // tiles of this rank = ceil(K / 1024); sharded: K % 1024 == 0
   int NT;                                 // G * nt
   float* lw_even; float* lw_odd;          // log-weights of step t in lw_odd when (T - 1 - t) is odd
-  unsigned long long* aggA; unsigned long long* aggB;    // [NT * kPfCorePad] this rank's copy of the granules (alternating steps)
+  unsigned long long* aggA; unsigned long long* aggB;    // [NT * kGranulePad] this rank's copy of the granules (alternating steps)
   float* bsum; float* bmax;               // [3][NT] LSE ring: per tile {max, sum exp(lw - max)}
   unsigned* ready;                        // [G * gridDim.x]
   const long long* peer_data;             // [G] byte distance from this rank's data window to rank g's mapping (NULL: one rank)
@@ -307,8 +306,8 @@ GJX_DEV void pf_core(const PfCoreArgs& f_in, Model& m, unsigned char* pf_dyn) {
         const float bs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(row_sum_to_lane15(lane < NW ? fsum[s][lane] : 0.0f)), 15));
         if (ton(s) && lane < G) {
           const long long d = sPF[lane];
-          if constexpr (MULTI) store_scoped_u64(peer_ptr(agg + (size_t)(gt0 + s) * kPfCorePad + 1, d), (tag << 60) | (ex_tile[s] & ((1ull << 60) - 1)), sys);
-          store_scoped_u64(peer_ptr(agg + (size_t)(gt0 + s) * kPfCorePad, d), tile_granule(tag, eb[s], tt), sys);
+          if constexpr (MULTI) store_scoped_u64(peer_ptr(agg + (size_t)(gt0 + s) * kGranulePad + 1, d), (tag << 60) | (ex_tile[s] & ((1ull << 60) - 1)), sys);
+          store_scoped_u64(peer_ptr(agg + (size_t)(gt0 + s) * kGranulePad, d), tile_granule(tag, eb[s], tt), sys);
           const size_t slot = (size_t)((t - 1) % 3) * NT + gt0 + s;
           store_scoped(peer_ptr(f.bsum + slot, d), bs, sys);
           store_scoped(peer_ptr(f.bmax + slot, d), bm[s], sys);
@@ -326,7 +325,7 @@ GJX_DEV void pf_core(const PfCoreArgs& f_in, Model& m, unsigned char* pf_dyn) {
     if (tid < G) store_scoped_u32(peer_ptr(f.ready + f.rank * nb + (int)blockIdx.x, sPF[tid]), rtag, sys);
     stage_step_constants(t);
     // a first look at the granules goes out before the draws (for the last block to publish they are all there already)
-    const unsigned long long gv0 = tid < NT ? load_scoped_u64(&agg[(size_t)tid * kPfCorePad], sys) : 0ull;
+    const unsigned long long gv0 = tid < NT ? load_scoped_u64(&agg[(size_t)tid * kGranulePad], sys) : 0ull;
     const key2 key_t = key2{sKey[t & 1][0], sKey[t & 1][1]};
     if (t < T) m.draw(t, key_t, (uint64_t)(f.offset + jl(0)), hoisted);
     if (fin) lse_ring_reduce(t - 2, rpm, rps);
@@ -334,24 +333,25 @@ GJX_DEV void pf_core(const PfCoreArgs& f_in, Model& m, unsigned char* pf_dyn) {
     {
       float em = (float)kTileDead;
       for (int b = tid; b < NT; b += THREADS) {
-        unsigned long long v = b == tid ? gv0 : load_scoped_u64(&agg[(size_t)b * kPfCorePad], sys);
+        unsigned long long v = b == tid ? gv0 : load_scoped_u64(&agg[(size_t)b * kGranulePad], sys);
         while ((v >> 60) != tag && step_budget) {
           --step_budget;
           __builtin_amdgcn_s_sleep(1);
-          v = load_scoped_u64(&agg[(size_t)b * kPfCorePad], sys);
+          v = load_scoped_u64(&agg[(size_t)b * kGranulePad], sys);
         }
         if ((v >> 60) != tag) { timed_out(); v = 0; }
-        const uint64_t S = v & ((1ull << 40) - 1);
-        const int e = S ? (int)((v >> 40) & 0xFFFFFu) + kTileDead : kTileDead;
+        uint64_t S;
+        int e;
+        tile_granule_unpack(v, S, e);
         P[b + 1] = S;
         Eb[b] = e;
         em = fmaxf(em, (float)e);
         if constexpr (MULTI) {                   // the tile's spacing total: the second word of its granule, under the same tag
-          unsigned long long v2 = load_scoped_u64(&agg[(size_t)b * kPfCorePad + 1], sys);
+          unsigned long long v2 = load_scoped_u64(&agg[(size_t)b * kGranulePad + 1], sys);
           while ((v2 >> 60) != tag && step_budget) {
             --step_budget;
             __builtin_amdgcn_s_sleep(1);
-            v2 = load_scoped_u64(&agg[(size_t)b * kPfCorePad + 1], sys);
+            v2 = load_scoped_u64(&agg[(size_t)b * kGranulePad + 1], sys);
           }
           if ((v2 >> 60) != tag) { timed_out(); v2 = 0; }
           P2[b + 1] = v2 & ((1ull << 60) - 1);
@@ -372,60 +372,16 @@ GJX_DEV void pf_core(const PfCoreArgs& f_in, Model& m, unsigned char* pf_dyn) {
       Emax = pfc_uni_i32((int)em);
       if (fin && tid == 0) lse_ring_write(t - 2);
     }
+    auto shift_of = [&](int b) { return Emax - Eb[b]; };
     if (NT <= 512) {
-      // few tiles: the prefix by ONE wave — ceil(NT / 64) entries per lane, one DPP scan — instead of 16 waves and a barrier between
-      // their partial sums (as k_ssm_persistent does for its 256 tiles)
-      if (wid == 0) {
-        const int per = (NT + 63) >> 6;
-        const int e0 = lane * per < NT ? lane * per : NT, e1 = (e0 + per) < NT ? (e0 + per) : NT;
-        uint64_t loc = 0;
-        for (int e = e0; e < e1; ++e) {
-          const int sh = Emax - Eb[e];
-          const uint64_t g = sh < 64 ? P[e + 1] >> sh : 0;
-          P[e + 1] = g;
-          loc += g;
-        }
-        uint64_t run = wave_scan_u64(loc) - loc;
-        for (int e = e0; e < e1; ++e) { run += P[e + 1]; P[e + 1] = run; }
-      }
-      if (MULTI && wid == 1) {                   // the prefix of the spacing totals, by the next wave at the same time
-        const int per = (NT + 63) >> 6;
-        const int e0 = lane * per < NT ? lane * per : NT, e1 = (e0 + per) < NT ? (e0 + per) : NT;
-        uint64_t loc = 0;
-        for (int e = e0; e < e1; ++e) loc += P2[e + 1];
-        uint64_t run = wave_scan_u64(loc) - loc;
-        for (int e = e0; e < e1; ++e) { run += P2[e + 1]; P2[e + 1] = run; }
-      }
-    } else {
-      // prefix of the shifted tile totals: thread i owns the entries [i per, (i + 1) per)
-      const int per = (NT + THREADS - 1) / THREADS;
-      const int e0 = tid * per < NT ? tid * per : NT, e1 = (e0 + per) < NT ? (e0 + per) : NT;
-      uint64_t loc = 0;
-      for (int e = e0; e < e1; ++e) {
-        const int sh = Emax - Eb[e];
-        const uint64_t g = sh < 64 ? P[e + 1] >> sh : 0;
-        P[e + 1] = g;
-        loc += g;
-      }
-      const uint64_t inc = wave_scan_u64(loc);
-      if (lane == 63) wq[wid] = inc;
+      // few tiles: the prefix by ONE wave, and MULTI: the prefix of the spacing totals by the next wave at the same time
+      if (wid == 0) prefix_in_place_wave(P, NT, shift_of);
+      if (MULTI && wid == 1) prefix_in_place_wave(P2, NT, NoShift{});
       __syncthreads();
-      uint64_t run = inc - loc;
-      for (int w = 0; w < wid; ++w) run += wq[w];
-      for (int e = e0; e < e1; ++e) { run += P[e + 1]; P[e + 1] = run; }
-      if constexpr (MULTI) {                     // ... and of the spacing totals (a second pass: wq is reused)
-        __syncthreads();
-        uint64_t loc2 = 0;
-        for (int e = e0; e < e1; ++e) loc2 += P2[e + 1];
-        const uint64_t inc2 = wave_scan_u64(loc2);
-        if (lane == 63) wq[wid] = inc2;
-        __syncthreads();
-        uint64_t run2 = inc2 - loc2;
-        for (int w = 0; w < wid; ++w) run2 += wq[w];
-        for (int e = e0; e < e1; ++e) { run2 += P2[e + 1]; P2[e + 1] = run2; }
-      }
+    } else {
+      prefix_in_place<THREADS>(P, NT, wq, shift_of);
+      if constexpr (MULTI) prefix_in_place<THREADS>(P2, NT, wq, NoShift{});   // (a second pass: wq is reused behind the first one's barrier)
     }
-    __syncthreads();
     GJX_CSTAMP(4);
     const uint64_t total = pfc_uni_u64(P[NT]);
     if (t == T) {                                // the last record, once every tile's ring entry is complete
@@ -472,24 +428,7 @@ GJX_DEV void pf_core(const PfCoreArgs& f_in, Model& m, unsigned char* pf_dyn) {
           Tj = sorted_threshold(P2[gt0 + s] + ex_incl[s], s_all, total);
         } else
         Tj = comb_threshold(f.offset + (act(s) ? (int64_t)jl(s) : K - 1), u_t, step, total);
-        // a tile's slots draw from tiles near its own index: the nine boundaries around it are read together (one LDS
-        // latency, the same addresses in every lane); a threshold outside that window takes the fixed-trip descent
-        const int own = gt0 + s;
-        const int wlo = own - 4 < 0 ? 0 : (own - 4 > NT - 8 ? (NT - 8 < 0 ? 0 : NT - 8) : own - 4);
-        uint64_t Pw[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Pw[k] = P[wlo + k < NT ? wlo + k : NT];
-        int tile = wlo;
-        if (Tj >= Pw[0] && Tj < Pw[8]) {
-#pragma unroll
-          for (int k = 1; k < 8; ++k) tile += Pw[k] <= Tj ? 1 : 0;
-        } else {
-          tile = 0;
-          for (int sft = 1 << (31 - __builtin_clz((unsigned)NT)); sft >= 1; sft >>= 1) {
-            const int p = tile + sft;                                   // P[p] = inclusive prefix of tile p - 1
-            if (p <= NT - 1 && P[p] <= Tj) tile = p;
-          }
-        }
+        const int tile = source_tile(P, NT, gt0 + s, Tj);
         Tjs[s] = (Tj - P[tile]) << (Emax - Eb[tile]);                 // residual in the source tile's own units (< S_tile)
         tiles[s] = tile;
       }
@@ -506,13 +445,12 @@ GJX_DEV void pf_core(const PfCoreArgs& f_in, Model& m, unsigned char* pf_dyn) {
         while (P[tmin + c0 + 1] == P[tmin + c0]) ++c0;
         if (again) __syncthreads();                                   // previous round's cumL consumed
         again = true;
-        const int tl = wid / WPT, part = wid % WPT;                   // this wave: quarter `part` of source tile c0 + tl
-        const bool on = c0 + tl < ntiles;
-        uint64_t qi[4], sacc = 0, inc = 0;
-        if (on) {
+        // a wave takes 256 particles of source tile c0 + (its index / WPT), from the rank that holds the tile
+        rescan_round<THREADS, THREADS, 4, 1>(cumL, wq, [&](int tl, int o, uint64_t (&q)[4]) {
+          if (c0 + tl >= ntiles) return false;
           const int tsrc = tmin + c0 + tl;
           const int g = tsrc / nt;
-          const int64_t p0 = (int64_t)(tsrc - g * nt) * THREADS + part * 256 + lane * 4;
+          const int64_t p0 = (int64_t)(tsrc - g * nt) * THREADS + o;
           const float* lwp = peer_ptr(lw_prev, sPD[g]);
           float lw4[4];
 #pragma unroll
@@ -524,40 +462,23 @@ GJX_DEV void pf_core(const PfCoreArgs& f_in, Model& m, unsigned char* pf_dyn) {
           }
           const int es = Eb[tsrc];
 #pragma unroll
-          for (int k = 0; k < 4; ++k) { sacc += p0 + k < K ? tile_q(lw4[k], es) : 0; qi[k] = sacc; }
-          inc = wave_scan_u64(sacc);
-          if (lane == 63) wq[wid] = inc;                              // the wave's total: offset of the next quarter
-        }
-        __syncthreads();
-        if (f.verify && on && part == 0 && lane == 0) {
-          // the log-weights this block just pulled must quantise to the total their owner published in the tile's granule
-          const int tsrc = tmin + c0 + tl;
-          uint64_t tot = 0;
-          for (int w = 0; w < WPT; ++w) tot += wq[tl * WPT + w];
-          const int sh = Emax - Eb[tsrc];
-          if ((sh < 64 ? tot >> sh : 0) != P[tsrc + 1] - P[tsrc]) cx.mismatch();
-        }
-        if (on) {
-          uint64_t base = inc - sacc;
-          for (int w = 0; w < part; ++w) base += wq[tl * WPT + w];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) cumL[tl * THREADS + part * 256 + lane * 4 + k] = base + qi[k];
-        }
-        __syncthreads();
+          for (int k = 0; k < 4; ++k) q[k] = p0 + k < K ? tile_q(lw4[k], es) : 0;
+          return true;
+        }, [&] {
+          const int tl = wid / WPT;
+          if (f.verify && c0 + tl < ntiles && wid % WPT == 0 && lane == 0) {
+            // the log-weights this block just pulled must quantise to the total their owner published in the tile's granule
+            const int tsrc = tmin + c0 + tl;
+            uint64_t tot = 0;
+            for (int w = 0; w < WPT; ++w) tot += wq[tl * WPT + w];
+            const int sh = Emax - Eb[tsrc];
+            if ((sh < 64 ? tot >> sh : 0) != P[tsrc + 1] - P[tsrc]) cx.mismatch();
+          }
+        });
 #pragma unroll
         for (int s = 0; s < SPL; ++s) {
           const int kpos = tiles[s] - tmin;
-          if (ton(s) && kpos >= c0 && kpos < c0 + kChunk) {
-            const uint64_t* cm = cumL + (kpos - c0) * THREADS;
-            const uint64_t Tj = Tjs[s];
-            int l2 = 0;                                               // number of entries <= the residual, 4-ary descent
-#pragma unroll
-            for (int q = THREADS >> 2; q >= 1; q >>= 2) {
-              const uint64_t pa = cm[l2 + q - 1], pb = cm[l2 + 2 * q - 1], pc = cm[l2 + 3 * q - 1];
-              l2 += (pa <= Tj ? q : 0) + (pb <= Tj ? q : 0) + (pc <= Tj ? q : 0);
-            }
-            srcs[s] = tiles[s] * THREADS + l2;
-          }
+          if (ton(s) && kpos >= c0 && kpos < c0 + kChunk) srcs[s] = tiles[s] * THREADS + rank_in_tile<THREADS>(cumL + (kpos - c0) * THREADS, Tjs[s]);
         }
       }
     } else {

@@ -94,10 +94,10 @@ void pf_step_keys_res(uint32_t key0, uint32_t key1, int T, std::vector<uint32_t>
 
 PfRegion pf_region(char* base, int64_t nt, int64_t grid, int T, bool with_tabs) {
   PfRegion r;
-  const size_t tile_bytes = (16 * (size_t)kPfCorePad + 24) * (size_t)nt, ready_bytes = 8 * (((size_t)grid + 1) / 2);
+  const size_t tile_bytes = (16 * (size_t)kGranulePad + 24) * (size_t)nt, ready_bytes = 8 * (((size_t)grid + 1) / 2);
   r.nt = (int)nt; r.ctrl = (unsigned*)base + 8;
-  r.aggA = (unsigned long long*)(base + kWsHeaderBytes); r.aggB = r.aggA + (size_t)nt * kPfCorePad;
-  r.bsum = (float*)(r.aggB + (size_t)nt * kPfCorePad); r.bmax = r.bsum + 3 * (size_t)nt;
+  r.aggA = (unsigned long long*)(base + kWsHeaderBytes); r.aggB = r.aggA + (size_t)nt * kGranulePad;
+  r.bsum = (float*)(r.aggB + (size_t)nt * kGranulePad); r.bmax = r.bsum + 3 * (size_t)nt;
   r.ready = (unsigned*)(r.bmax + 3 * (size_t)nt);
   r.us = (double*)((char*)r.ready + ready_bytes); r.keys = (uint32_t*)(r.us + T);
   r.tabs = with_tabs ? (const float**)(r.keys + 2 * (size_t)T) : nullptr;

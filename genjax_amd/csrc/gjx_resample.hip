@@ -389,7 +389,8 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
     if (threadIdx.x == 0) grid_publish(agg, tag, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
   }
   GJX_STAMP(1);
-  // ---- while the totals are in flight: cumulative weights of tiles b - 1, b, b + 1 RELATIVE to each tile's start
+  // ---- while the totals are in flight: cumulative weights of tiles b - 1, b, b + 1 RELATIVE to each tile's start.  Written out, not a
+  //      rescan_round: the own tile's scan above is reused (scanning it again measured 0.3 us per step at K = 2^20)
   //      (the neighbours' log-weights are requested only now: nothing may delay the publication above, every block waits
   //      for the last one) ----
 #pragma unroll
@@ -426,19 +427,7 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
   if (threadIdx.x == 0) P[0] = 0;
   __syncthreads();
   GJX_STAMP(2);
-  {   // prefix of the tile totals, in place: lane t owns entries [t per, (t+1) per)
-    const int per = (nb + 255) >> 8;
-    const int e0 = threadIdx.x * per, e1 = (e0 + per) < nb ? (e0 + per) : nb;
-    uint64_t loc = 0;
-    for (int e = e0; e < e1; ++e) loc += P[e + 1];
-    uint64_t inc = wave_scan_u64(loc);
-    if (lane == 63) wsum[wid] = inc;     // the publish above read wsum before the barrier after the gather
-    __syncthreads();
-    uint64_t run = inc - loc;
-    for (int w = 0; w < wid; ++w) run += wsum[w];
-    for (int e = e0; e < e1; ++e) { run += P[e + 1]; P[e + 1] = run; }
-    __syncthreads();
-  }
+  prefix_in_place<256>(P, nb, wsum, NoShift{});   // (the publish above read wsum before the barrier behind the gather)
   const uint64_t total = P[nb];
   GJX_STAMP(6);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -458,45 +447,8 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
     for (int k = 0; k < ITEMS; ++k) {
       const int64_t j = (i0 + k < K) ? i0 + k : K - 1;
       T[k] = comb_threshold(j, u, step, total);
-      tile[k] = 0;
     }
-    // first tile t with P[t + 1] > T = number of tiles with inclusive prefix <= T: fixed-trip binary descent for the
-    // lane's first and last slot together (independent LDS reads per round); the slots between them are in the same
-    // tile unless the lane straddles a tile boundary (then they are searched too)
-    auto descend = [&](int k0, int k1) {
-#pragma unroll
-      for (int sft = kGatherMaxTiles >> 1; sft >= 1; sft >>= 1) {
-        const int pa = tile[k0] + sft, pb = tile[k1] + sft;     // P[probe] = inclusive prefix of tile probe - 1
-        if (pa <= nb - 1 && P[pa] <= T[k0]) tile[k0] = pa;
-        if (k1 != k0 && pb <= nb - 1 && P[pb] <= T[k1]) tile[k1] = pb;
-      }
-    };
-    // A block's slots draw from tiles near its own index (equal tile totals would make it exactly its own): the nine
-    // boundaries of the eight tiles around blockIdx.x are read together (one LDS latency, the same addresses in every
-    // lane) and the tile of each slot is counted off; only a lane with a threshold outside that window descends
-    const int wlo = (int)blockIdx.x - 4 < 0 ? 0 : ((int)blockIdx.x - 4 > nb - 8 ? (nb - 8 < 0 ? 0 : nb - 8) : (int)blockIdx.x - 4);
-    uint64_t Pw[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Pw[k] = P[wlo + k < nb ? wlo + k : nb];
-    if (T[0] >= Pw[0] && T[ITEMS - 1] < Pw[8]) {            // thresholds are non-decreasing in the slot index
-#pragma unroll
-      for (int k = 0; k < ITEMS; ++k) {
-        int tl = wlo;
-#pragma unroll
-        for (int w = 1; w < 8; ++w) tl += Pw[w] <= T[k] ? 1 : 0;
-        tile[k] = tl;
-      }
-    } else {
-      descend(0, ITEMS - 1);
-      if (ITEMS > 2) {
-        if (tile[0] == tile[ITEMS - 1]) {
-#pragma unroll
-          for (int k = 1; k < ITEMS - 1; ++k) tile[k] = tile[0];
-        } else {
-          descend(1, ITEMS > 3 ? 2 : 1);
-        }
-      }
-    }
+    source_tiles<ITEMS>(P, nb, (int)blockIdx.x, T, tile);        // thresholds are non-decreasing in the slot index
     if (timeline) { asm volatile("" :: "v"(tile[0]), "v"(tile[ITEMS - 1])); GJX_STAMP(7); }
     // the block's source tiles: the tile index is non-decreasing in the slot index, so they are the range between the
     // first and the last slot's tile — no list to build, the two ends travel through LDS behind one barrier.  A round
@@ -506,21 +458,16 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
     if (threadIdx.x == 255) s_range[1] = tile[ITEMS - 1];
     __syncthreads();
     const int tmin = s_range[0], ntiles = s_range[1] - tmin + 1;
+    int pos[ITEMS];
+    const uint64_t* cm[ITEMS];
+    uint64_t Tr[ITEMS];                             // residual of every slot in its source tile
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) Tr[k] = T[k] - P[tile[k]];
     if (tmin >= w0 && s_range[1] <= w0 + 2) {       // block-uniform: every source tile is in the prefetched window
       GJX_STAMP(3);
-      int pos[ITEMS];
-      const uint64_t* cm[ITEMS];
-      uint64_t Tr[ITEMS];
 #pragma unroll
-      for (int k = 0; k < ITEMS; ++k) { cm[k] = cumL + (tile[k] - w0) * TILE; Tr[k] = T[k] - P[tile[k]]; pos[k] = 0; }
-#pragma unroll
-      for (int q = TILE >> 2; q >= 1; q >>= 2) {
-#pragma unroll
-        for (int k = 0; k < ITEMS; ++k) {
-          const uint64_t pa = cm[k][pos[k] + q - 1], pb = cm[k][pos[k] + 2 * q - 1], pc = cm[k][pos[k] + 3 * q - 1];
-          pos[k] += (pa <= Tr[k] ? q : 0) + (pb <= Tr[k] ? q : 0) + (pc <= Tr[k] ? q : 0);
-        }
-      }
+      for (int k = 0; k < ITEMS; ++k) cm[k] = cumL + (tile[k] - w0) * TILE;
+      rank_in_tiles<TILE, ITEMS>(cm, Tr, pos);
 #pragma unroll
       for (int k = 0; k < ITEMS; ++k) anc[k] = (int32_t)((int64_t)tile[k] * TILE + pos[k]);
     } else {
@@ -535,53 +482,25 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
       if (c < ntiles) load_tile((int64_t)(tmin + c) * TILE + (int64_t)threadIdx.x * ITEMS, nv[c]);
     for (int idx = 0; idx < ntiles;) {
       const int nidx = next_live(idx + CH);
-      uint64_t qi[CH][ITEMS], sacc[CH], inc[CH];
-      int tsrc[CH];
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
+      // (the barrier inside the round: every lane is done searching the previous round's cumL)
+      rescan_round<256, TILE, ITEMS, CH>(cumL, &s_wtot[0][0], [&](int c, int o, uint64_t (&q)[ITEMS]) {
         const bool on = idx + c < ntiles;
-        tsrc[c] = on ? tmin + idx + c : 0;
-        const int64_t p0 = (int64_t)tsrc[c] * TILE + (int64_t)threadIdx.x * ITEMS;
-        sacc[c] = 0;
+        const int64_t p0 = (int64_t)(tmin + idx + c) * TILE + o;
+        if (on) {
 #pragma unroll
-        for (int k = 0; k < ITEMS; ++k) { sacc[c] += (on && p0 + k < K) ? weight_q(nv[c], k, mode, mx) : 0; qi[c][k] = sacc[c]; }
-        if (nidx + c < ntiles) load_tile((int64_t)(tmin + nidx + c) * TILE + (int64_t)threadIdx.x * ITEMS, nv[c]);   // next round, in flight
-        inc[c] = sacc[c];
-      }
-#pragma unroll
-      for (int c = 0; c < CH; ++c) inc[c] = wave_scan_u64(inc[c]);     // three independent DPP chains
-      if (lane == 63) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) s_wtot[c][wid] = inc[c];
-      }
-      __syncthreads();           // also: every lane is done searching the previous round's cumL
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        uint64_t base = P[tsrc[c]] + (inc[c] - sacc[c]);
-        for (int w = 0; w < wid; ++w) base += s_wtot[c][w];
-#pragma unroll
-        for (int k = 0; k < ITEMS; ++k) cumL[c * TILE + threadIdx.x * ITEMS + k] = base + qi[c][k];
-      }
-      __syncthreads();
-      // first particle p of the slot's tile with cum_incl(p) > T
-      int pos[ITEMS];
-      const uint64_t* cm[ITEMS];
+          for (int k = 0; k < ITEMS; ++k) q[k] = (p0 + k < K) ? weight_q(nv[c], k, mode, mx) : 0;
+        }
+        if (nidx + c < ntiles) load_tile((int64_t)(tmin + nidx + c) * TILE + o, nv[c]);   // next round, in flight
+        return on;
+      }, [] {});
+      // first particle p of the slot's tile with cum_incl(p) > T (a slot of another round searches the round's first tile for nothing)
       bool mine[ITEMS];
 #pragma unroll
       for (int k = 0; k < ITEMS; ++k) {
         mine[k] = kpos[k] >= idx && kpos[k] < idx + CH;
         cm[k] = cumL + (mine[k] ? (kpos[k] - idx) * TILE : 0);
-        pos[k] = 0;
       }
-      // (number of entries <= T, 4-ary: three independent probes per level and slot, 5 LDS latencies for 1024 entries)
-#pragma unroll
-      for (int q = TILE >> 2; q >= 1; q >>= 2) {
-#pragma unroll
-        for (int k = 0; k < ITEMS; ++k) {
-          const uint64_t pa = cm[k][pos[k] + q - 1], pb = cm[k][pos[k] + 2 * q - 1], pc = cm[k][pos[k] + 3 * q - 1];
-          pos[k] += (pa <= T[k] ? q : 0) + (pb <= T[k] ? q : 0) + (pc <= T[k] ? q : 0);
-        }
-      }
+      rank_in_tiles<TILE, ITEMS>(cm, Tr, pos);
 #pragma unroll
       for (int k = 0; k < ITEMS; ++k)
         if (mine[k]) anc[k] = (int32_t)((int64_t)tile[k] * TILE + pos[k]);
@@ -645,22 +564,12 @@ __global__ __launch_bounds__(kTileQ) void k_tile_totals(const float* __restrict_
   if (GATED && *gate == 0) return;
   __shared__ float fred[NW];
   __shared__ uint64_t wsum[NW];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int64_t i = (int64_t)blockIdx.x * kTileQ + threadIdx.x;
-  const float lw = i < K ? logw[i] : -INFINITY;
-  const float wm = wave_max(lw);
-  if (lane == 0) fred[wid] = wm;
-  __syncthreads();
-  float bm = fred[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) bm = fmaxf(bm, fred[w]);
-  const int e = tile_exponent(bm);
-  const uint64_t tot_w = wave_total_u64(i < K ? tile_q(lw, e) : 0);
-  if (lane == 0) wsum[wid] = tot_w;
-  __syncthreads();
+  const float lw[1] = {i < K ? logw[i] : -INFINITY};
+  uint64_t q[1], inc;
+  const int e = tile_quantise<kTileQ, 1>(lw, fred, wsum, q, inc);
   if (threadIdx.x == 0) {
-    uint64_t tot = 0;
-    for (int w = 0; w < NW; ++w) tot += wsum[w];
+    const uint64_t tot = sum_partials<NW>(wsum);
     S[blockIdx.x] = tot;
     E[blockIdx.x] = tot ? e : kTileDead;
   }
@@ -932,6 +841,111 @@ int launch_ess_accumulate(const float* inc, float* W, float* w_copy, int64_t K, 
   return GJX_OK;
 }
 
+// ---- the tile-scaled systematic resampler as three plain launches (gjx_resample_indices_tiled): the step-by-step
+//      form of what k_pf_persistent (gjx_pfilter.inl) does inside its loop; bit-identical ancestors ----
+__global__ __launch_bounds__(kTileQ) void k_tiled_quantise(const float* logw, int64_t K, uint64_t* cq, uint64_t* S, int32_t* E,
+                                                           uint32_t* q_out, int32_t* e_out) {
+  constexpr int NW = kTileQ / 64;
+  __shared__ float fred[NW];
+  __shared__ uint64_t wsum[NW];
+  const int wid = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * kTileQ + threadIdx.x;
+  const bool active = i < K;
+  const float lw[1] = {active ? logw[i] : -INFINITY};
+  uint64_t q[1], inc;
+  const int e = tile_quantise<kTileQ, 1>(lw, fred, wsum, q, inc);
+  uint64_t base = 0, tot = 0;
+  for (int w = 0; w < NW; ++w) { if (w < wid) base += wsum[w]; tot += wsum[w]; }
+  if (active) { cq[i] = base + inc; if (q_out) q_out[i] = (uint32_t)q[0]; }
+  if (threadIdx.x == 0) {
+    const int es = tot ? e : kTileDead;
+    S[blockIdx.x] = tot; E[blockIdx.x] = es;
+    if (e_out) e_out[blockIdx.x] = es;
+  }
+}
+
+// GATED (the adaptive filter): *gate == 0 means "this step does not resample" — nothing is read or written
+template <bool GATED = false>
+__global__ __launch_bounds__(1024) void k_tiled_plan(const uint64_t* S, const int32_t* E, int nt, uint64_t* P, int32_t* sh, unsigned* ctrl,
+                                                     const int32_t* gate = nullptr) {
+  __shared__ float fred[16];
+  if (GATED && *gate == 0) return;
+  __shared__ uint64_t wsum[16];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  float em = (float)kTileDead;
+  for (int b = threadIdx.x; b < nt; b += 1024) em = fmaxf(em, (float)E[b]);
+  em = wave_max(em);
+  if (lane == 0) fred[wid] = em;
+  __syncthreads();
+  em = fred[0];
+  for (int w = 1; w < 16; ++w) em = fmaxf(em, fred[w]);
+  const int Emax = (int)em;
+  if (threadIdx.x == 0) P[0] = 0;
+  const uint64_t total = block_scan_chunked(nt, wsum, [&](int b) {
+    const int s = Emax - E[b];
+    sh[b] = s < 64 ? s : 64;
+    return s < 64 ? S[b] >> s : 0ull;
+  }, [&](int b, uint64_t p) { P[b + 1] = p; });
+  if (threadIdx.x == 0 && total == 0 && ctrl) __hip_atomic_fetch_or(&ctrl[2], kStatusZeroTotal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void k_tiled_ancestors(const uint64_t* P, const int32_t* sh, const uint64_t* cq, int nt, int64_t K,
+                                                         double u, int64_t N, int32_t* anc) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= N) return;
+  const uint64_t total = P[nt];
+  if (total == 0) { anc[j] = (int32_t)(j < K ? j : K - 1); return; }   // dead collection: identity, flagged by the plan
+  const double step = (double)total / (double)N;
+  anc[j] = (int32_t)tiled_lookup(P, sh, cq, nt, K, comb_threshold(j, u, step, total));
+}
+
+// ---- multinomial resampling by SORTED uniforms on the tile-scaled weight line (gjx_resample_sorted_multinomial_tiled): slot j's
+//      threshold is floor(total * S_j / S_N+1) with S_j the running sum of the exponential spacings exp_spacing(bits(key, j)) — the
+//      order statistics of N iid uniforms, so the ancestors are a multinomial draw delivered in non-decreasing order.  The spacings
+//      are exact integers (gjx_device.h): their sums do not depend on how the slots are cut into tiles. ----
+__global__ __launch_bounds__(kTileQ) void k_spacing_totals(key2 key, int64_t N, uint64_t* SS) {
+  constexpr int NW = kTileQ / 64;
+  __shared__ uint64_t wsum[NW];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t j = (int64_t)blockIdx.x * kTileQ + threadIdx.x;
+  uint64_t e = j <= N ? exp_spacing(fold_in64(key, (uint64_t)j).a) : 0ull;     // (slot N: the spacing that closes the unit interval)
+  e = wave_scan_u64(e);
+  if (lane == 63) wsum[wid] = e;
+  __syncthreads();
+  if (threadIdx.x == 0) SS[blockIdx.x] = sum_partials<NW>(wsum);
+}
+
+__global__ __launch_bounds__(1024) void k_spacing_plan(const uint64_t* SS, int nb, uint64_t* SP) {
+  __shared__ uint64_t wsum[16];
+  if (threadIdx.x == 0) SP[0] = 0;
+  block_scan_chunked(nb, wsum, [&](int b) { return SS[b]; }, [&](int b, uint64_t p) { SP[b + 1] = p; });
+}
+
+__global__ __launch_bounds__(kTileQ) void k_sorted_ancestors(const uint64_t* P, const int32_t* sh, const uint64_t* cq, int nt, int64_t K, key2 key,
+                                                             const uint64_t* SP, int nb, int64_t N, int32_t* anc) {
+  constexpr int NW = kTileQ / 64;
+  __shared__ uint64_t wsum[NW];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t j = (int64_t)blockIdx.x * kTileQ + threadIdx.x;
+  uint64_t e = j < N ? exp_spacing(fold_in64(key, (uint64_t)j).a) : 0ull;
+  e = wave_scan_u64(e);
+  if (lane == 63) wsum[wid] = e;
+  __syncthreads();
+  uint64_t Sj = SP[blockIdx.x] + e;
+  for (int w = 0; w < wid; ++w) Sj += wsum[w];
+  if (j >= N) return;
+  const uint64_t total = P[nt];
+  if (total == 0) { anc[j] = (int32_t)(j < K ? j : K - 1); return; }   // dead collection: identity, flagged by the plan
+  anc[j] = (int32_t)tiled_lookup(P, sh, cq, nt, K, sorted_threshold(Sj, SP[nb], total));
+}
+
+int launch_tiled_plan(const uint64_t* S, const int32_t* E, int nt, uint64_t* P, int32_t* sh, unsigned* ctrl, hipStream_t st, const int32_t* gate) {
+  if (gate) hipLaunchKernelGGL(k_tiled_plan<true>, dim3(1), dim3(1024), 0, st, S, E, nt, P, sh, ctrl, gate);
+  else hipLaunchKernelGGL(k_tiled_plan<false>, dim3(1), dim3(1024), 0, st, S, E, nt, P, sh, ctrl, (const int32_t*)nullptr);
+  GJX_CHECK_LAUNCH("k_tiled_plan");
+  return GJX_OK;
+}
+
 }  // namespace gjx
 
 using namespace gjx;
@@ -1137,6 +1151,55 @@ extern "C" int gjx_resample_gather_tiled(const float* logw, int64_t K, const uin
                                          int64_t K_total, void* workspace, size_t workspace_bytes, void* stream) {
   return gjx::resample_gather_tiled_gated(logw, K, tile_S, tile_E, lse_mode, lse, n_partials, u, src, src_stride, rows, dst, dst_stride, ancestors,
                                           lse_out, K_total, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int gjx_resample_indices_tiled(const float* logw, int64_t K, double u, int64_t N, int32_t* ancestors, uint64_t* cum,
+                                          uint32_t* q_out, int32_t* e_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!logw || !ancestors || !cum || K <= 0 || N <= 0 || K > (int64_t)1 << 31) return gjx_fail(GJX_EINVAL, "gjx_resample_indices_tiled: bad argument");
+  const int64_t nt = (K + kTileQ - 1) / kTileQ;
+  // workspace: [256 B control][S u64 nt][P u64 nt + 1][E i32 nt][shift i32 nt]
+  if (!workspace || workspace_bytes < gjx_workspace_bytes(GJX_OP_RESAMPLE, K) || 256 + 24 * (size_t)nt + 8 > workspace_bytes)
+    return gjx_fail(GJX_EWORKSPACE, "gjx_resample_indices_tiled: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  uint64_t* S = (uint64_t*)((char*)workspace + kWsHeaderBytes);
+  uint64_t* P = S + nt;
+  int32_t* E = (int32_t*)(P + nt + 1);
+  int32_t* sh = E + nt;
+  hipLaunchKernelGGL(k_tiled_quantise, dim3((unsigned)nt), dim3(kTileQ), 0, st, logw, K, cum, S, E, q_out, e_out);
+  hipLaunchKernelGGL(k_tiled_plan<false>, dim3(1), dim3(1024), 0, st, (const uint64_t*)S, (const int32_t*)E, (int)nt, P, sh, (unsigned*)workspace + 8, (const int32_t*)nullptr);
+  hipLaunchKernelGGL(k_tiled_ancestors, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (const uint64_t*)P, (const int32_t*)sh,
+                     (const uint64_t*)cum, (int)nt, K, u, N, ancestors);
+  GJX_CHECK_LAUNCH("gjx_resample_indices_tiled");
+  return GJX_OK;
+}
+
+extern "C" int gjx_resample_sorted_multinomial_tiled(const float* logw, int64_t K, uint32_t key0, uint32_t key1, int64_t N, int32_t* ancestors,
+                                                     uint64_t* cum, uint32_t* q_out, int32_t* e_out, void* workspace, size_t workspace_bytes,
+                                                     void* stream) {
+  if (!logw || !ancestors || !cum || K <= 0 || N <= 0 || K > (int64_t)1 << 31 || N > (int64_t)1 << 31)
+    return gjx_fail(GJX_EINVAL, "gjx_resample_sorted_multinomial_tiled: bad argument");
+  const int64_t nt = (K + kTileQ - 1) / kTileQ;
+  const int64_t nb = (N + 1 + kTileQ - 1) / kTileQ;        // tiles of SLOTS (N + 1 spacings)
+  // workspace: [256 B control][S u64 nt][P u64 nt + 1][E i32 nt][shift i32 nt][SS u64 nb][SP u64 nb + 1]
+  const size_t off_ss = (256 + 24 * (size_t)nt + 8 + 7) & ~(size_t)7;
+  if (!workspace || workspace_bytes < gjx_workspace_bytes(GJX_OP_RESAMPLE, K) || off_ss + 16 * (size_t)nb + 8 > workspace_bytes)
+    return gjx_fail(GJX_EWORKSPACE, "gjx_resample_sorted_multinomial_tiled: workspace too small (OP_RESAMPLE of K, and 288 + 24 ceil(K / 1024) + 16 ceil((N + 1) / 1024) bytes)");
+  hipStream_t st = (hipStream_t)stream;
+  uint64_t* S = (uint64_t*)((char*)workspace + kWsHeaderBytes);
+  uint64_t* P = S + nt;
+  int32_t* E = (int32_t*)(P + nt + 1);
+  int32_t* sh = E + nt;
+  uint64_t* SS = (uint64_t*)((char*)workspace + off_ss);
+  uint64_t* SP = SS + nb;
+  const key2 key{key0, key1};
+  hipLaunchKernelGGL(k_tiled_quantise, dim3((unsigned)nt), dim3(kTileQ), 0, st, logw, K, cum, S, E, q_out, e_out);
+  hipLaunchKernelGGL(k_tiled_plan<false>, dim3(1), dim3(1024), 0, st, (const uint64_t*)S, (const int32_t*)E, (int)nt, P, sh, (unsigned*)workspace + 8, (const int32_t*)nullptr);
+  hipLaunchKernelGGL(k_spacing_totals, dim3((unsigned)nb), dim3(kTileQ), 0, st, key, N, SS);
+  hipLaunchKernelGGL(k_spacing_plan, dim3(1), dim3(1024), 0, st, (const uint64_t*)SS, (int)nb, SP);
+  hipLaunchKernelGGL(k_sorted_ancestors, dim3((unsigned)((N + kTileQ - 1) / kTileQ)), dim3(kTileQ), 0, st, (const uint64_t*)P, (const int32_t*)sh,
+                     (const uint64_t*)cum, (int)nt, K, key, (const uint64_t*)SP, (int)nb, N, ancestors);
+  GJX_CHECK_LAUNCH("gjx_resample_sorted_multinomial_tiled");
+  return GJX_OK;
 }
 
 extern "C" int gjx_resample_gather_systematic(const uint64_t* cum, int64_t K, const uint64_t* base_total_dev, double u,

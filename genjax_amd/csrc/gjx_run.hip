@@ -855,22 +855,10 @@ __global__ __launch_bounds__(THREADS) void k_run_gmm_flat(GmmArgs a) {
     if constexpr (TILES) {
       // {e_b, S_b} of this tile (GJX_WEIGHTS_TILE_SCALED, include/gjx.h; K % 1024 == 0: every wave of the block is here):
       // the resampling kernel that follows needs no grid-wide exchange of its own (gjx_resample_gather_tiled)
-      const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-      float m = lw[0];
-#pragma unroll
-      for (int p = 1; p < PPT; ++p) m = fmaxf(m, lw[p]);
-      const float wm = wave_max(m);
-      if (lane == 0) red_tm[wid] = wm;
-      __syncthreads();
-      const int e = tile_exponent(fmaxf(fmaxf(red_tm[0], red_tm[1]), fmaxf(red_tm[2], red_tm[3])));
-      uint64_t q = 0;
-#pragma unroll
-      for (int p = 0; p < PPT; ++p) q += tile_q(lw[p], e);
-      const uint64_t wq = wave_total_u64(q);
-      if (lane == 0) red_tq[wid] = wq;
-      __syncthreads();
+      uint64_t q[PPT], inc;
+      const int e = tile_quantise<THREADS, PPT>(lw, red_tm, red_tq, q, inc);
       if (threadIdx.x == 0) {
-        const uint64_t tot = red_tq[0] + red_tq[1] + red_tq[2] + red_tq[3];
+        const uint64_t tot = sum_partials<THREADS / 64>(red_tq);
         a.tile_S[tix] = tot;
         a.tile_E[tix] = tot ? e : kTileDead;
       }

@@ -53,7 +53,7 @@ __global__ void k_tiles_to_granules(const uint64_t* __restrict__ S, const int32_
   const int b = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (b >= nt) return;
   const uint64_t sv = S[b];
-  gran[(size_t)b * kLiveGranulePad] = tile_granule(tag, sv ? E[b] : kTileDead, sv);
+  gran[(size_t)b * kGranulePad] = tile_granule(tag, sv ? E[b] : kTileDead, sv);
   part[b] = pairs[b];
 }
 
@@ -291,7 +291,7 @@ static int run_steps_tail(const FilterCall& a, RowsOf& rows_of, const FilterLayo
   const gjx_program* steps = a.steps;
   const int T = a.T;
   const int64_t K = a.K, nt = K / 1024;
-  const size_t area_need = (16 * (size_t)kLiveGranulePad + 16) * (size_t)nt + 24 * (size_t)T + 64;   // granules, pair arrays, per-step arguments
+  const size_t area_need = (16 * (size_t)kGranulePad + 16) * (size_t)nt + 24 * (size_t)T + 64;   // granules, pair arrays, per-step arguments
   if (T < 4 || !L.area || K % 1024 != 0 || L.area_bytes < area_need || info.engine != 4 || info.tiles_offset == 0 || info.n_partials != (int)nt ||
       a.has(GJX_FILTER_NO_STEPS) || a.has(GJX_FILTER_ABSOLUTE_INPUTS) || gjx_plain_launches_forced() ||
       !periodic_steps(steps, T, [](const gjx_program* p, const gjx_program* q) { return gen_same_kernel(p, q, 4); }))
@@ -303,13 +303,13 @@ static int run_steps_tail(const FilterCall& a, RowsOf& rows_of, const FilterLayo
   if (grid <= 0 || nt > 4 * grid) return kNotThisForm;
   hipStream_t st = a.st();
   unsigned long long* gran_a = (unsigned long long*)L.area;           // even steps
-  unsigned long long* gran_b = gran_a + nt * kLiveGranulePad;
-  unsigned long long* part_a = gran_b + nt * kLiveGranulePad;
+  unsigned long long* gran_b = gran_a + nt * kGranulePad;
+  unsigned long long* part_a = gran_b + nt * kGranulePad;
   unsigned long long* part_b = part_a + nt;
   const float** tabs_dev = (const float**)(part_b + nt);
   uint32_t* keys_dev = (uint32_t*)(tabs_dev + T);
   double* us_dev = (double*)(keys_dev + 2 * (size_t)T);
-  const hipError_t e = hipMemsetAsync(gran_a, 0, 16 * (size_t)kLiveGranulePad * (size_t)nt, st);
+  const hipError_t e = hipMemsetAsync(gran_a, 0, 16 * (size_t)kGranulePad * (size_t)nt, st);
   if (e != hipSuccess) return gjx_fail_hip(e, "gjx_scan_filter(step arguments)");
   if (int rcu = pf_upload_tabs(tabs_dev, steps, T, st)) return rcu;
   if (int rcu = upload_words(keys_dev, a.keys.data(), (size_t)T, st)) return rcu;

@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void k_ssm_fused_step(SsmFusedArgs f) {
   __shared__ float fred[16];
   __shared__ uint64_t wsum[4];
   __shared__ uint64_t P[kSsmFusedMaxTiles + 1];   // P[t] = total weight of tiles < t; P[nb] = grand total
-  __shared__ uint64_t cumL[kChunk * 256];         // inclusive cumulative weights of the loaded tiles (absolute)
+  __shared__ uint64_t cumL[kChunk * 256];         // inclusive cumulative weights of the loaded tiles (relative to the tile's start)
   __shared__ int32_t s_tof[256], s_tiles[256];
   __shared__ int s_cnt[4];
   unsigned epoch;
@@ -256,21 +256,8 @@ __global__ __launch_bounds__(256) void k_ssm_fused_step(SsmFusedArgs f) {
   grid_gather(f.agg, tag, f.ctrl, [&](int b, unsigned long long val) { P[b + 1] = val; });
   if (threadIdx.x == 0) P[0] = 0;
   __syncthreads();
-  // ---- prefix of the tile totals, in place: lane t owns entries [t per, (t+1) per) ----
-  {
-    const int per = (nb + 255) >> 8;
-    const int e0 = threadIdx.x * per, e1 = (e0 + per) < nb ? (e0 + per) : nb;
-    uint64_t loc = 0;
-    for (int e = e0; e < e1; ++e) loc += P[e + 1];
-    uint64_t inc = wave_scan_u64(loc);
-    __syncthreads();            // wsum of the publish above has been read by thread 0
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    uint64_t run = inc - loc;
-    for (int w = 0; w < wid; ++w) run += wsum[w];
-    for (int e = e0; e < e1; ++e) { run += P[e + 1]; P[e + 1] = run; }
-    __syncthreads();
-  }
+  __syncthreads();              // wsum of the publish above has been read by thread 0
+  prefix_in_place<256>(P, nb, wsum, NoShift{});
   const uint64_t total = P[nb];
   GJX_STAMP(3);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -302,9 +289,10 @@ __global__ __launch_bounds__(256) void k_ssm_fused_step(SsmFusedArgs f) {
     GJX_STAMP(4);
     for (int c0 = 0; c0 < ntiles; c0 += kChunk) {
       __syncthreads();           // s_tiles written / previous chunk's cumL consumed
-      if (c0 + wid < ntiles) {   // wave-uniform: this wave re-scans tile s_tiles[c0 + wid], 4 particles per lane
-        const int tsrc = s_tiles[c0 + wid];
-        const int64_t p0 = (int64_t)tsrc * 256 + lane * 4;
+      // a wave re-scans tile s_tiles[c0 + its index], 4 particles per lane
+      rescan_round<256, 256, 4, 1>(cumL, nullptr, [&](int tl, int o, uint64_t (&q)[4]) {
+        if (c0 + tl >= ntiles) return false;
+        const int64_t p0 = (int64_t)s_tiles[c0 + tl] * 256 + o;
         float lw4[4];
         if (p0 + 4 <= K) {
           const float4 v = *(const float4*)(f.logw_prev + p0);
@@ -313,21 +301,17 @@ __global__ __launch_bounds__(256) void k_ssm_fused_step(SsmFusedArgs f) {
 #pragma unroll
           for (int k = 0; k < 4; ++k) lw4[k] = p0 + k < K ? f.logw_prev[p0 + k] : -INFINITY;
         }
-        uint64_t qi[4], sacc = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { sacc += p0 + k < K ? weight_q(lw4, k, 1, mx) : 0; qi[k] = sacc; }
-        uint64_t inc = wave_scan_u64(sacc);
-        const uint64_t base = P[tsrc] + (inc - sacc);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) cumL[wid * 256 + lane * 4 + k] = base + qi[k];
-      }
-      __syncthreads();
+        for (int k = 0; k < 4; ++k) q[k] = p0 + k < K ? weight_q(lw4, k, 1, mx) : 0;
+        return true;
+      }, [] {});
       if (kpos >= c0 && kpos < c0 + kChunk) {
         const uint64_t* cm = cumL + (kpos - c0) * 256;
-        int l2 = 0, h2 = 255;    // first particle p of the tile with cum_incl(p) > T
+        const uint64_t Tr = T - P[tile];
+        int l2 = 0, h2 = 255;    // first particle p of the tile with cum_incl(p) > T (cumL is relative to the tile's start)
         while (l2 < h2) {
           const int mid = (l2 + h2) >> 1;
-          if (cm[mid] > T) h2 = mid; else l2 = mid + 1;
+          if (cm[mid] > Tr) h2 = mid; else l2 = mid + 1;
         }
         src = (int64_t)tile * 256 + l2;
       }
@@ -445,9 +429,6 @@ struct SsmPersistArgs {
   unsigned long long* timeline;    // debug (gjx_debug_timeline): 16 realtime stamps per block for step T / 2
 };
 
-// granules of the persistent filter's rendezvous sit one per 64-byte line: 256 blocks storing into 32 shared lines serialise
-// in the L2 (11.6 -> 11.0 us per filter step; 128-byte spacing measured the same)
-constexpr int kGranulePad = 8;
 template <int RNG, int DX, int THREADS>
 __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
   // THREADS = 1024 (one block per CU, 256 blocks at K = 2^18) quarters the granules of each all-gather: a rendezvous
@@ -619,16 +600,7 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
     grid_gather<kGranulePad>(f.aggB, tagB, f.ctrl, [&](int b, unsigned long long val) { P[b + 1] = val; });
     if (threadIdx.x == 0) P[0] = 0;
     __syncthreads();
-    if (wid == 0) {
-      // prefix of the tile totals by ONE wave — ceil(nb / 64) entries per lane, one DPP scan — instead of four waves and a
-      // barrier between their partial sums
-      const int per = (nb + 63) >> 6;
-      const int e0 = lane * per < nb ? lane * per : nb, e1 = (e0 + per) < nb ? (e0 + per) : nb;
-      uint64_t loc = 0;
-      for (int e = e0; e < e1; ++e) loc += P[e + 1];
-      uint64_t run = wave_scan_u64(loc) - loc;
-      for (int e = e0; e < e1; ++e) { run += P[e + 1]; P[e + 1] = run; }
-    }
+    if (wid == 0) prefix_in_place_wave(P, nb, NoShift{});
     __syncthreads();
     const uint64_t total = P[nb];
     GJX_PSTAMP(4);
@@ -639,34 +611,16 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
     }
     if (t == T) break;
     if (total == 0 && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_fetch_or(&f.ctrl[2], kStatusZeroTotal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // ---- ancestor of slot j (k_ssm_fused_step's search; foreign log-weights through agent-scope loads) ----
+    // ---- ancestor of slot j (source_tile, rescan_round, rank_in_tile: gjx_tile.h; foreign log-weights through agent-scope loads) ----
     const float* lw_prev = lw_buf(t - 1);
     int64_t src = j;
     if (total > 0) {
       const double step = (double)total / (double)K;
-      // the slot's source tile: first tile t with P[t + 1] > T = number of tiles whose inclusive prefix is <= T (fixed-trip
-      // descent in the LDS prefix).  The tile index is non-decreasing in the slot index, so the block's source tiles are
-      // the range between its first and its last slot's tile: no list to build, the two ends travel through LDS behind
-      // one barrier
+      // The tile index is non-decreasing in the slot index, so the block's source tiles are the range between its first and
+      // its last slot's tile: no list to build, the two ends travel through LDS behind one barrier
       const uint64_t Tj = comb_threshold(active ? j : K - 1, sU, step, total);
-      // A block's slots draw from tiles near its own index (equal tile totals would make it exactly its own): the nine
-      // boundaries of the eight tiles around blockIdx.x are read together (one LDS latency, same addresses in every lane)
-      // and the tile is counted off; a threshold outside that window takes the fixed-trip descent (nine dependent reads)
-      const int wlo = (int)blockIdx.x - 4 < 0 ? 0 : ((int)blockIdx.x - 4 > nb - 8 ? (nb - 8 < 0 ? 0 : nb - 8) : (int)blockIdx.x - 4);
-      uint64_t Pw[9];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) Pw[k] = P[wlo + k < nb ? wlo + k : nb];
-      int tile = wlo;
-      if (Tj >= Pw[0] && Tj < Pw[8]) {
-#pragma unroll
-        for (int k = 1; k < 8; ++k) tile += Pw[k] <= Tj ? 1 : 0;
-      } else {
-        tile = 0;
-        for (int sft = 1 << (31 - __builtin_clz((unsigned)nb)); sft >= 1; sft >>= 1) {
-          const int p = tile + sft;                                     // P[p] = inclusive prefix of tile p - 1
-          if (p <= nb - 1 && P[p] <= Tj) tile = p;
-        }
-      }
+      const int tile = source_tile(P, nb, (int)blockIdx.x, Tj);
+      const uint64_t Tr = Tj - P[tile];                                 // residual in the source tile
       if (threadIdx.x == 0) s_range[0] = tile;
       if (threadIdx.x == THREADS - 1) s_range[1] = tile;                // (inactive lanes searched slot K - 1)
       GJX_PSTAMP(9);
@@ -680,13 +634,10 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
         while (P[tmin + c0 + 1] == P[tmin + c0]) ++c0;
         if (again) __syncthreads();                                   // previous round's cumL consumed
         again = true;
-        const int tl = wid / WPT, part = wid % WPT;               // this wave: quarter `part` of source tile c0 + tl
-        const bool on = c0 + tl < ntiles;
-        uint64_t qi[4], sacc = 0, inc = 0;
-        int tsrc = 0;
-        if (on) {
-          tsrc = tmin + c0 + tl;
-          const int64_t p0 = (int64_t)tsrc * THREADS + part * 256 + lane * 4;
+        // a wave takes 256 particles of source tile c0 + (its index / WPT)
+        rescan_round<THREADS, THREADS, 4, 1>(cumL, wsum, [&](int tl, int o, uint64_t (&q)[4]) {
+          if (c0 + tl >= ntiles) return false;
+          const int64_t p0 = (int64_t)(tmin + c0 + tl) * THREADS + o;
           float lw4[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) lw4[k] = -INFINITY;
@@ -697,34 +648,11 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
           }
           if (f.timeline && c0 == 0) { asm volatile("" :: "v"(lw4[0]), "v"(lw4[3])); GJX_PSTAMP(10); }
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            sacc += p0 + k < K ? weight_q(lw4, k, 1, mx) : 0;
-            qi[k] = sacc;
-          }
-          inc = wave_scan_u64(sacc);
-          if (WPT > 1 && lane == 63) wsum[wid] = inc;             // the wave's total: offset of the next quarter
-        }
-        if (WPT > 1) __syncthreads();
-        if (on) {
-          uint64_t base = P[tsrc] + (inc - sacc);
-          for (int w = 0; w < part; ++w) base += wsum[tl * WPT + w];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) cumL[tl * THREADS + part * 256 + lane * 4 + k] = base + qi[k];
-        }
-        __syncthreads();
+          for (int k = 0; k < 4; ++k) q[k] = p0 + k < K ? weight_q(lw4, k, 1, mx) : 0;
+          return true;
+        }, [] {});
         if (c0 == 0) GJX_PSTAMP(11);
-        if (kpos >= c0 && kpos < c0 + kChunk) {
-          const uint64_t* cm = cumL + (kpos - c0) * THREADS;
-          // first particle whose cumulative weight exceeds the threshold = number of entries <= it: a 4-ary descent, three
-          // independent probes per level (5 LDS latencies for 1024 entries instead of 10)
-          int l2 = 0;
-#pragma unroll
-          for (int q = THREADS >> 2; q >= 1; q >>= 2) {
-            const uint64_t pa = cm[l2 + q - 1], pb = cm[l2 + 2 * q - 1], pc = cm[l2 + 3 * q - 1];
-            l2 += (pa <= Tj ? q : 0) + (pb <= Tj ? q : 0) + (pc <= Tj ? q : 0);
-          }
-          src = (int64_t)tile * THREADS + l2;
-        }
+        if (kpos >= c0 && kpos < c0 + kChunk) src = (int64_t)tile * THREADS + rank_in_tile<THREADS>(cumL + (kpos - c0) * THREADS, Tr);
       }
     }
     GJX_PSTAMP(5);
@@ -771,177 +699,6 @@ __global__ __launch_bounds__(THREADS) void k_ssm_persistent(SsmPersistArgs f) {
 #undef GJX_PSTAMP
   if (blockIdx.x == 0 && threadIdx.x == 0)
     __hip_atomic_store(&f.ctrl[0], epoch + 2u * (unsigned)T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---- the tile-scaled systematic resampler as three plain launches (gjx_resample_indices_tiled): the step-by-step
-//      form of what k_pf_persistent (gjx_pfilter.inl) does inside its loop; bit-identical ancestors ----
-__global__ __launch_bounds__(kTileQ) void k_tiled_quantise(const float* logw, int64_t K, uint64_t* cq, uint64_t* S, int32_t* E,
-                                                           uint32_t* q_out, int32_t* e_out) {
-  constexpr int NW = kTileQ / 64;
-  __shared__ float fred[NW];
-  __shared__ uint64_t wsum[NW];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t i = (int64_t)blockIdx.x * kTileQ + threadIdx.x;
-  const bool active = i < K;
-  const float lw = active ? logw[i] : -INFINITY;
-  const float wm = wave_max(lw);
-  if (lane == 0) fred[wid] = wm;
-  __syncthreads();
-  float bm = fred[0];
-#pragma unroll
-  for (int w = 1; w < NW; ++w) bm = fmaxf(bm, fred[w]);
-  const int e = tile_exponent(bm);
-  const uint64_t q = active ? tile_q(lw, e) : 0;
-  uint64_t inc = wave_scan_u64(q);
-  if (lane == 63) wsum[wid] = inc;
-  __syncthreads();
-  uint64_t base = 0, tot = 0;
-  for (int w = 0; w < NW; ++w) { if (w < wid) base += wsum[w]; tot += wsum[w]; }
-  if (active) { cq[i] = base + inc; if (q_out) q_out[i] = (uint32_t)q; }
-  if (threadIdx.x == 0) {
-    const int es = tot ? e : kTileDead;
-    S[blockIdx.x] = tot; E[blockIdx.x] = es;
-    if (e_out) e_out[blockIdx.x] = es;
-  }
-}
-
-// GATED (the adaptive filter): *gate == 0 means "this step does not resample" — nothing is read or written
-template <bool GATED = false>
-__global__ __launch_bounds__(1024) void k_tiled_plan(const uint64_t* S, const int32_t* E, int nt, uint64_t* P, int32_t* sh, unsigned* ctrl,
-                                                     const int32_t* gate = nullptr) {
-  __shared__ float fred[16];
-  if (GATED && *gate == 0) return;
-  __shared__ uint64_t wsum[16];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  float em = (float)kTileDead;
-  for (int b = threadIdx.x; b < nt; b += 1024) em = fmaxf(em, (float)E[b]);
-  em = wave_max(em);
-  if (lane == 0) fred[wid] = em;
-  __syncthreads();
-  em = fred[0];
-  for (int w = 1; w < 16; ++w) em = fmaxf(em, fred[w]);
-  const int Emax = (int)em;
-  uint64_t carry = 0;
-  if (threadIdx.x == 0) P[0] = 0;
-  for (int b0 = 0; b0 < nt; b0 += 1024) {
-    const int b = b0 + threadIdx.x;
-    uint64_t g = 0;
-    if (b < nt) {
-      const int s = Emax - E[b];
-      g = s < 64 ? S[b] >> s : 0;
-      sh[b] = s < 64 ? s : 64;
-    }
-    uint64_t inc = wave_scan_u64(g);
-    __syncthreads();
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    uint64_t base = carry, tot = 0;
-    for (int w = 0; w < 16; ++w) { if (w < wid) base += wsum[w]; tot += wsum[w]; }
-    if (b < nt) P[b + 1] = base + inc;
-    carry += tot;
-  }
-  if (threadIdx.x == 0 && carry == 0 && ctrl) __hip_atomic_fetch_or(&ctrl[2], kStatusZeroTotal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__global__ __launch_bounds__(256) void k_tiled_ancestors(const uint64_t* P, const int32_t* sh, const uint64_t* cq, int nt, int64_t K,
-                                                         double u, int64_t N, int32_t* anc) {
-  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (j >= N) return;
-  const uint64_t total = P[nt];
-  if (total == 0) { anc[j] = (int32_t)(j < K ? j : K - 1); return; }   // dead collection: identity, flagged by the plan
-  const double step = (double)total / (double)N;
-  const uint64_t Tj = comb_threshold(j, u, step, total);
-  int lo = 0, hi = nt - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (P[mid + 1] > Tj) hi = mid; else lo = mid + 1;
-  }
-  const uint64_t r = (Tj - P[lo]) << sh[lo];
-  const uint64_t* cm = cq + (int64_t)lo * kTileQ;
-  const int64_t left = K - (int64_t)lo * kTileQ;
-  int l2 = 0, h2 = (int)(left < kTileQ ? left : kTileQ) - 1;
-  while (l2 < h2) {
-    const int mid = (l2 + h2) >> 1;
-    if (cm[mid] > r) h2 = mid; else l2 = mid + 1;
-  }
-  anc[j] = (int32_t)((int64_t)lo * kTileQ + l2);
-}
-
-// ---- multinomial resampling by SORTED uniforms on the tile-scaled weight line (gjx_resample_sorted_multinomial_tiled): slot j's
-//      threshold is floor(total * S_j / S_N+1) with S_j the running sum of the exponential spacings exp_spacing(bits(key, j)) — the
-//      order statistics of N iid uniforms, so the ancestors are a multinomial draw delivered in non-decreasing order.  The spacings
-//      are exact integers (gjx_device.h): their sums do not depend on how the slots are cut into tiles. ----
-__global__ __launch_bounds__(kTileQ) void k_spacing_totals(key2 key, int64_t N, uint64_t* SS) {
-  constexpr int NW = kTileQ / 64;
-  __shared__ uint64_t wsum[NW];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t j = (int64_t)blockIdx.x * kTileQ + threadIdx.x;
-  uint64_t e = j <= N ? exp_spacing(fold_in64(key, (uint64_t)j).a) : 0ull;     // (slot N: the spacing that closes the unit interval)
-  e = wave_scan_u64(e);
-  if (lane == 63) wsum[wid] = e;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t tot = 0;
-    for (int w = 0; w < NW; ++w) tot += wsum[w];
-    SS[blockIdx.x] = tot;
-  }
-}
-
-__global__ __launch_bounds__(1024) void k_spacing_plan(const uint64_t* SS, int nb, uint64_t* SP) {
-  __shared__ uint64_t wsum[16];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  uint64_t carry = 0;
-  if (threadIdx.x == 0) SP[0] = 0;
-  for (int b0 = 0; b0 < nb; b0 += 1024) {
-    const int b = b0 + threadIdx.x;
-    const uint64_t inc = wave_scan_u64(b < nb ? SS[b] : 0ull);
-    __syncthreads();
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    uint64_t base = carry, tot = 0;
-    for (int w = 0; w < 16; ++w) { if (w < wid) base += wsum[w]; tot += wsum[w]; }
-    if (b < nb) SP[b + 1] = base + inc;
-    carry += tot;
-  }
-}
-
-__global__ __launch_bounds__(kTileQ) void k_sorted_ancestors(const uint64_t* P, const int32_t* sh, const uint64_t* cq, int nt, int64_t K, key2 key,
-                                                             const uint64_t* SP, int nb, int64_t N, int32_t* anc) {
-  constexpr int NW = kTileQ / 64;
-  __shared__ uint64_t wsum[NW];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t j = (int64_t)blockIdx.x * kTileQ + threadIdx.x;
-  uint64_t e = j < N ? exp_spacing(fold_in64(key, (uint64_t)j).a) : 0ull;
-  e = wave_scan_u64(e);
-  if (lane == 63) wsum[wid] = e;
-  __syncthreads();
-  uint64_t Sj = SP[blockIdx.x] + e;
-  for (int w = 0; w < wid; ++w) Sj += wsum[w];
-  if (j >= N) return;
-  const uint64_t total = P[nt];
-  if (total == 0) { anc[j] = (int32_t)(j < K ? j : K - 1); return; }   // dead collection: identity, flagged by the plan
-  const uint64_t Tj = sorted_threshold(Sj, SP[nb], total);
-  int lo = 0, hi = nt - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (P[mid + 1] > Tj) hi = mid; else lo = mid + 1;
-  }
-  const uint64_t r = (Tj - P[lo]) << sh[lo];
-  const uint64_t* cm = cq + (int64_t)lo * kTileQ;
-  const int64_t left = K - (int64_t)lo * kTileQ;
-  int l2 = 0, h2 = (int)(left < kTileQ ? left : kTileQ) - 1;
-  while (l2 < h2) {
-    const int mid = (l2 + h2) >> 1;
-    if (cm[mid] > r) h2 = mid; else l2 = mid + 1;
-  }
-  anc[j] = (int32_t)((int64_t)lo * kTileQ + l2);
-}
-
-int launch_tiled_plan(const uint64_t* S, const int32_t* E, int nt, uint64_t* P, int32_t* sh, unsigned* ctrl, hipStream_t st, const int32_t* gate) {
-  if (gate) hipLaunchKernelGGL(k_tiled_plan<true>, dim3(1), dim3(1024), 0, st, S, E, nt, P, sh, ctrl, gate);
-  else hipLaunchKernelGGL(k_tiled_plan<false>, dim3(1), dim3(1024), 0, st, S, E, nt, P, sh, ctrl, (const int32_t*)nullptr);
-  GJX_CHECK_LAUNCH("k_tiled_plan");
-  return GJX_OK;
 }
 
 }  // namespace gjx
@@ -1040,56 +797,6 @@ extern "C" int gjx_ssm_step_move(const gjx_ssm* m, uint32_t key0, uint32_t key1,
                                            : launch_ssm_move<GJX_RNG_FLAT>(a, m->dx, nblocks, st);
   if (rc) return gjx_fail(GJX_EUNSUPPORTED, "gjx_ssm_step_move: dx must be one of 2,4,8,16");
   GJX_CHECK_LAUNCH("gjx_ssm_step_move");
-  return GJX_OK;
-}
-
-
-extern "C" int gjx_resample_indices_tiled(const float* logw, int64_t K, double u, int64_t N, int32_t* ancestors, uint64_t* cum,
-                                          uint32_t* q_out, int32_t* e_out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!logw || !ancestors || !cum || K <= 0 || N <= 0 || K > (int64_t)1 << 31) return gjx_fail(GJX_EINVAL, "gjx_resample_indices_tiled: bad argument");
-  const int64_t nt = (K + kTileQ - 1) / kTileQ;
-  // workspace: [256 B control][S u64 nt][P u64 nt + 1][E i32 nt][shift i32 nt]
-  if (!workspace || workspace_bytes < gjx_workspace_bytes(GJX_OP_RESAMPLE, K) || 256 + 24 * (size_t)nt + 8 > workspace_bytes)
-    return gjx_fail(GJX_EWORKSPACE, "gjx_resample_indices_tiled: workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  uint64_t* S = (uint64_t*)((char*)workspace + kWsHeaderBytes);
-  uint64_t* P = S + nt;
-  int32_t* E = (int32_t*)(P + nt + 1);
-  int32_t* sh = E + nt;
-  hipLaunchKernelGGL(k_tiled_quantise, dim3((unsigned)nt), dim3(kTileQ), 0, st, logw, K, cum, S, E, q_out, e_out);
-  hipLaunchKernelGGL(k_tiled_plan<false>, dim3(1), dim3(1024), 0, st, (const uint64_t*)S, (const int32_t*)E, (int)nt, P, sh, (unsigned*)workspace + 8, (const int32_t*)nullptr);
-  hipLaunchKernelGGL(k_tiled_ancestors, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (const uint64_t*)P, (const int32_t*)sh,
-                     (const uint64_t*)cum, (int)nt, K, u, N, ancestors);
-  GJX_CHECK_LAUNCH("gjx_resample_indices_tiled");
-  return GJX_OK;
-}
-
-extern "C" int gjx_resample_sorted_multinomial_tiled(const float* logw, int64_t K, uint32_t key0, uint32_t key1, int64_t N, int32_t* ancestors,
-                                                     uint64_t* cum, uint32_t* q_out, int32_t* e_out, void* workspace, size_t workspace_bytes,
-                                                     void* stream) {
-  if (!logw || !ancestors || !cum || K <= 0 || N <= 0 || K > (int64_t)1 << 31 || N > (int64_t)1 << 31)
-    return gjx_fail(GJX_EINVAL, "gjx_resample_sorted_multinomial_tiled: bad argument");
-  const int64_t nt = (K + kTileQ - 1) / kTileQ;
-  const int64_t nb = (N + 1 + kTileQ - 1) / kTileQ;        // tiles of SLOTS (N + 1 spacings)
-  // workspace: [256 B control][S u64 nt][P u64 nt + 1][E i32 nt][shift i32 nt][SS u64 nb][SP u64 nb + 1]
-  const size_t off_ss = (256 + 24 * (size_t)nt + 8 + 7) & ~(size_t)7;
-  if (!workspace || workspace_bytes < gjx_workspace_bytes(GJX_OP_RESAMPLE, K) || off_ss + 16 * (size_t)nb + 8 > workspace_bytes)
-    return gjx_fail(GJX_EWORKSPACE, "gjx_resample_sorted_multinomial_tiled: workspace too small (OP_RESAMPLE of K, and 288 + 24 ceil(K / 1024) + 16 ceil((N + 1) / 1024) bytes)");
-  hipStream_t st = (hipStream_t)stream;
-  uint64_t* S = (uint64_t*)((char*)workspace + kWsHeaderBytes);
-  uint64_t* P = S + nt;
-  int32_t* E = (int32_t*)(P + nt + 1);
-  int32_t* sh = E + nt;
-  uint64_t* SS = (uint64_t*)((char*)workspace + off_ss);
-  uint64_t* SP = SS + nb;
-  const key2 key{key0, key1};
-  hipLaunchKernelGGL(k_tiled_quantise, dim3((unsigned)nt), dim3(kTileQ), 0, st, logw, K, cum, S, E, q_out, e_out);
-  hipLaunchKernelGGL(k_tiled_plan<false>, dim3(1), dim3(1024), 0, st, (const uint64_t*)S, (const int32_t*)E, (int)nt, P, sh, (unsigned*)workspace + 8, (const int32_t*)nullptr);
-  hipLaunchKernelGGL(k_spacing_totals, dim3((unsigned)nb), dim3(kTileQ), 0, st, key, N, SS);
-  hipLaunchKernelGGL(k_spacing_plan, dim3(1), dim3(1024), 0, st, (const uint64_t*)SS, (int)nb, SP);
-  hipLaunchKernelGGL(k_sorted_ancestors, dim3((unsigned)((N + kTileQ - 1) / kTileQ)), dim3(kTileQ), 0, st, (const uint64_t*)P, (const int32_t*)sh,
-                     (const uint64_t*)cum, (int)nt, K, key, (const uint64_t*)SP, (int)nb, N, ancestors);
-  GJX_CHECK_LAUNCH("gjx_resample_sorted_multinomial_tiled");
   return GJX_OK;
 }
 

@@ -1,6 +1,7 @@
 // gjx_tile.h — device helpers shared by the one-launch filters (gjx_ssm.hip, gjx_pfilter.inl): agent- / system-scope
-// accesses for data other blocks (or other ranks) of the SAME launch read, the propagation noise in two halves, and the
-// tile-scaled fixed point (GJX_WEIGHTS_TILE_SCALED, include/gjx.h).
+// accesses for data other blocks (or other ranks) of the SAME launch read, the propagation noise in two halves, the
+// tile-scaled fixed point (GJX_WEIGHTS_TILE_SCALED, include/gjx.h), and the primitives every resampling kernel is built from
+// (tile totals, prefix, source tile, re-scan round, in-tile search).
 #pragma once
 #include "gjx_device.h"
 #include "gjx_scan.h"
@@ -114,7 +115,7 @@ GJX_DEV void ssm_noise_normals(const SsmNoiseBits<RNG, DX>& nb, float (&nz)[DX])
   }
 }
 
-// ---- tile-scaled fixed point (shared by k_ssm_persistent<TILED> and the gjx_resample_indices_tiled kernels) ----
+// ---- tile-scaled fixed point (shared by the one-launch filters and the tile-scaled resamplers of gjx_resample.hip) ----
 constexpr int kTileQ = 1024;                       // particles per quantisation tile
 constexpr float kTileScale = 536870912.0f;         // 2^29
 constexpr int kTileDead = -524288;                 // exponent of a tile without a finite positive weight (-2^19)
@@ -138,6 +139,249 @@ GJX_DEV uint64_t tile_q(float lw, int e) {         // floor(2^29 * min(1, 2^(lw 
 GJX_DEV unsigned long long tile_granule(unsigned long long tag, int e, uint64_t S) {
   return (tag << 60) | ((unsigned long long)(unsigned)(e - kTileDead) << 40) | (S & ((1ull << 40) - 1));
 }
+GJX_DEV void tile_granule_unpack(unsigned long long v, uint64_t& S, int& e) {   // (a tile without weight is dead whatever its exponent field says)
+  S = v & ((1ull << 40) - 1);
+  e = S ? (int)((v >> 40) & 0xFFFFFu) + kTileDead : kTileDead;
+}
+// the granules of a rendezvous sit one per 64-byte line: 256 blocks storing into 32 shared lines serialise in the L2 (11.6 -> 11.0 us
+// per step of k_ssm_persistent; 128-byte spacing measured the same)
+constexpr int kGranulePad = 8;
+
+// ---- the pieces every resampling kernel is built from ("Resampling primitives").  They cover the arithmetic BETWEEN the
+//      points other blocks or ranks observe: polls, tags, publications and their waits stay in the kernels.  A tile has TILE
+//      particles, a lane takes ITEMS consecutive ones, so TILE / (64 ITEMS) waves cover a tile. ----
+
+// One tile held by a block of THREADS lanes x ITEMS log-weights (-inf where there is no particle) -> the tile's exponent (returned, in
+// every thread), the lane's fixed-point weights q, the inclusive wave scan of the lane's sum (inc), the wave totals in
+// red_q[0 .. THREADS / 64).  Two barriers: red_m / red_q (THREADS / 64 words each) are free before the call, red_q is readable after it.
+template <int THREADS, int ITEMS>
+GJX_DEV int tile_quantise(const float (&lw)[ITEMS], float* red_m, uint64_t* red_q, uint64_t (&q)[ITEMS], uint64_t& inc) {
+  constexpr int NW = THREADS / 64;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  float m = lw[0];
+#pragma unroll
+  for (int k = 1; k < ITEMS; ++k) m = fmaxf(m, lw[k]);
+  const float wm = wave_max(m);
+  if (lane == 0) red_m[wid] = wm;
+  __syncthreads();
+  float bm = red_m[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) bm = fmaxf(bm, red_m[w]);
+  const int e = tile_exponent(bm);
+  uint64_t s = 0;
+#pragma unroll
+  for (int k = 0; k < ITEMS; ++k) { q[k] = tile_q(lw[k], e); s += q[k]; }
+  inc = wave_scan_u64(s);
+  const uint64_t wt = lane63_u64(inc);
+  if (lane == 0) red_q[wid] = wt;
+  __syncthreads();
+  return e;
+}
+template <int NW>
+GJX_DEV uint64_t sum_partials(const uint64_t* w) {
+  uint64_t t = 0;
+#pragma unroll
+  for (int k = 0; k < NW; ++k) t += w[k];
+  return t;
+}
+
+// Tile totals P[1 .. n] -> their inclusive prefix, in place (P[0] stays): thread t owns the stretch [t per, (t + 1) per), the waves'
+// sums meet in wave_partials [THREADS / 64].  shift_of(b): right shift that brings tile b's total to the common exponent (64 or
+// more: the tile is shifted out), or NoShift{} for totals that are on one scale already.  THREADS > 64: every thread of the block
+// calls it, one barrier inside and one at the end.  THREADS == 64: ONE wave calls it (few tiles: ceil(n / 64) entries per lane and one
+// DPP scan instead of all waves and a barrier between their partial sums), no barrier, wave_partials unused.
+struct NoShift {};
+template <class A, class B> struct SameType { static constexpr bool value = false; };
+template <class A> struct SameType<A, A> { static constexpr bool value = true; };
+template <int THREADS, class ShiftOf>
+GJX_DEV void prefix_in_place(uint64_t* P, int n, uint64_t* wave_partials, ShiftOf shift_of) {
+  static_assert(THREADS >= 64 && (THREADS & (THREADS - 1)) == 0, "whole waves, a power of two");
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int t = THREADS == 64 ? lane : (int)threadIdx.x;
+  const int per = (n + THREADS - 1) >> __builtin_ctz((unsigned)THREADS);
+  const int e0 = t * per < n ? t * per : n, e1 = (e0 + per) < n ? (e0 + per) : n;
+  uint64_t loc = 0;
+  for (int e = e0; e < e1; ++e) {
+    uint64_t g = P[e + 1];
+    if constexpr (!SameType<ShiftOf, NoShift>::value) {
+      const int sh = shift_of(e);
+      g = sh < 64 ? g >> sh : 0;
+      P[e + 1] = g;
+    }
+    loc += g;
+  }
+  const uint64_t inc = wave_scan_u64(loc);
+  uint64_t run = inc - loc;
+  if constexpr (THREADS > 64) {
+    if (lane == 63) wave_partials[wid] = inc;
+    __syncthreads();
+    for (int w = 0; w < wid; ++w) run += wave_partials[w];
+  }
+  for (int e = e0; e < e1; ++e) { run += P[e + 1]; P[e + 1] = run; }
+  if constexpr (THREADS > 64) __syncthreads();
+}
+template <class ShiftOf>
+GJX_DEV void prefix_in_place_wave(uint64_t* P, int n, ShiftOf shift_of) { prefix_in_place<64>(P, n, nullptr, shift_of); }
+
+// Inclusive prefix of val(0) .. val(n - 1) by ONE block of 1024 threads, 1024 entries per pass (any n): out(b, prefix) for every entry,
+// the total returned in every thread.  wsum: 16 words of LDS.
+template <class Val, class Out>
+GJX_DEV uint64_t block_scan_chunked(int n, uint64_t* wsum, Val val, Out out) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  uint64_t carry = 0;
+  for (int b0 = 0; b0 < n; b0 += 1024) {
+    const int b = b0 + threadIdx.x;
+    const uint64_t inc = wave_scan_u64(b < n ? val(b) : 0ull);
+    __syncthreads();
+    if (lane == 63) wsum[wid] = inc;
+    __syncthreads();
+    uint64_t base = carry, tot = 0;
+    for (int w = 0; w < 16; ++w) { if (w < wid) base += wsum[w]; tot += wsum[w]; }
+    if (b < n) out(b, base + inc);
+    carry += tot;
+  }
+  return carry;
+}
+
+// Source tiles of ITEMS thresholds that do not decrease with the slot index: tile[k] = first tile t with P[t + 1] > T[k] = number of
+// tiles whose inclusive prefix is <= T[k] (P[0 .. n]: the prefix, P[n] > T).  A block's slots draw from tiles near its own index
+// (equal tile totals would make it exactly `own`): the nine boundaries of the eight tiles around `own` are read together (one
+// LDS latency, the same addresses in every lane) and the tile of each slot is counted off.  Only a lane with a threshold outside
+// that window descends: fixed trip count from the largest power of two <= n (nine dependent reads at n = 256), the first and the
+// last slot together (independent reads per round); the slots between them are in the same tile unless the lane straddles a tile
+// boundary (then they are searched too).
+template <int ITEMS>
+GJX_DEV void source_tiles(const uint64_t* P, int n, int own, const uint64_t (&T)[ITEMS], int (&tile)[ITEMS]) {
+  const int wlo = own - 4 < 0 ? 0 : (own - 4 > n - 8 ? (n - 8 < 0 ? 0 : n - 8) : own - 4);
+  uint64_t Pw[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) Pw[k] = P[wlo + k < n ? wlo + k : n];
+  if (T[0] >= Pw[0] && T[ITEMS - 1] < Pw[8]) {
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+      int tl = wlo;
+#pragma unroll
+      for (int w = 1; w < 8; ++w) tl += Pw[w] <= T[k] ? 1 : 0;
+      tile[k] = tl;
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < ITEMS; ++k) tile[k] = 0;
+  auto descend = [&](int k0, int k1) {
+    for (int sft = 1 << (31 - __builtin_clz((unsigned)n)); sft >= 1; sft >>= 1) {
+      const int pa = tile[k0] + sft, pb = tile[k1] + sft;       // P[probe] = inclusive prefix of tile probe - 1
+      if (pa <= n - 1 && P[pa] <= T[k0]) tile[k0] = pa;
+      if (k1 != k0 && pb <= n - 1 && P[pb] <= T[k1]) tile[k1] = pb;
+    }
+  };
+  descend(0, ITEMS - 1);
+  if constexpr (ITEMS > 2) {
+    if (tile[0] == tile[ITEMS - 1]) {
+#pragma unroll
+      for (int k = 1; k < ITEMS - 1; ++k) tile[k] = tile[0];
+    } else {
+#pragma unroll
+      for (int k = 1; k < ITEMS - 1; k += 2) descend(k, k + 1 < ITEMS - 1 ? k + 1 : k);
+    }
+  }
+}
+GJX_DEV int source_tile(const uint64_t* P, int n, int own, uint64_t T) {
+  const uint64_t T1[1] = {T};
+  int tile[1];
+  source_tiles<1>(P, n, own, T1, tile);
+  return tile[0];
+}
+
+// Ranks of N residuals in tiles of TILE inclusive cumulative weights: pos[k] = number of entries of cm[k] that are <= r[k] = the first
+// particle whose cumulative weight exceeds it.  4-ary: three independent probes per level and slot, 5 LDS latencies for 1024 entries
+// instead of 10; the probes of different slots are interleaved level by level, so they are independent too.
+template <int TILE, int N>
+GJX_DEV void rank_in_tiles(const uint64_t* (&cm)[N], const uint64_t (&r)[N], int (&pos)[N]) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) pos[k] = 0;
+#pragma unroll
+  for (int q = TILE >> 2; q >= 1; q >>= 2) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      const uint64_t pa = cm[k][pos[k] + q - 1], pb = cm[k][pos[k] + 2 * q - 1], pc = cm[k][pos[k] + 3 * q - 1];
+      pos[k] += (pa <= r[k] ? q : 0) + (pb <= r[k] ? q : 0) + (pc <= r[k] ? q : 0);
+    }
+  }
+}
+template <int TILE>
+GJX_DEV int rank_in_tile(const uint64_t* cm, uint64_t r) {
+  const uint64_t* cm1[1] = {cm};
+  const uint64_t r1[1] = {r};
+  int pos[1];
+  rank_in_tiles<TILE, 1>(cm1, r1, pos);
+  return pos[0];
+}
+
+// One round of the re-scan: the inclusive cumulative fixed-point weights of up to THREADS / 64 / (TILE / (64 ITEMS)) * CPT source tiles,
+// each RELATIVE to its tile's start, into cum[tl TILE + i] (tl: the tile's index in the round).  TILE / (64 ITEMS) waves share a
+// tile, 64 ITEMS particles each, and a wave takes CPT tiles: 256 threads x CPT = 3 is the form of the one-tile-per-block kernels (three
+// independent DPP chains per wave), 1024 threads x CPT = 1 four tiles by four waves each.  fill(tl, o, q) gives the ITEMS fixed-point
+// weights from offset o of tile tl — how they are loaded (plain, agent or system scope, peer-mapped, from registers) and quantised
+// (weight_q, tile_q) is the caller's — or returns false for a tile the round leaves out (wave-uniform; its part of cum is not
+// written).  wtot: LDS for the waves' totals [tiles of a round][waves per tile]; mid() runs between the barrier behind them and the
+// stores to cum (verify mode).  Every thread calls it; ends in a barrier.  The caller's barrier keeps a round from overwriting a cum
+// that is still being searched.
+template <int THREADS, int TILE, int ITEMS, int CPT, class Fill, class Mid>
+GJX_DEV void rescan_round(uint64_t* cum, uint64_t* wtot, Fill fill, Mid mid) {
+  constexpr int WPT = TILE / (64 * ITEMS), NW = THREADS / 64;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int tl0 = NW == WPT ? 0 : (wid / WPT) * CPT, part = NW == WPT ? wid : wid % WPT, o = (part * 64 + lane) * ITEMS;
+  uint64_t qi[CPT][ITEMS], sacc[CPT], inc[CPT];
+  bool on[CPT];
+#pragma unroll
+  for (int c = 0; c < CPT; ++c) {
+    uint64_t q[ITEMS];
+    sacc[c] = 0; inc[c] = 0;
+    on[c] = fill(tl0 + c, o, q);
+    if (!on[c]) continue;
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) { sacc[c] += q[k]; qi[c][k] = sacc[c]; }
+  }
+#pragma unroll
+  for (int c = 0; c < CPT; ++c) if (on[c]) inc[c] = wave_scan_u64(sacc[c]);
+  if constexpr (WPT > 1) {
+    if (lane == 63) {
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) if (on[c]) wtot[(tl0 + c) * WPT + part] = inc[c];   // the wave's total: offset of the next part
+    }
+    __syncthreads();
+  }
+  mid();
+#pragma unroll
+  for (int c = 0; c < CPT; ++c) {
+    if (!on[c]) continue;
+    uint64_t base = inc[c] - sacc[c];
+    if constexpr (WPT > 1) for (int w = 0; w < part; ++w) base += wtot[(tl0 + c) * WPT + w];
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) cum[(tl0 + c) * TILE + o + k] = base + qi[c][k];
+  }
+  __syncthreads();
+}
+
+// Ancestor of threshold T from the arrays the three-launch resamplers leave in memory (k_tiled_quantise, k_tiled_plan): prefix P of the
+// shifted tile totals, the shifts sh, the in-tile cumulative fixed-point weights cq — two binary searches.
+GJX_DEV int64_t tiled_lookup(const uint64_t* P, const int32_t* sh, const uint64_t* cq, int nt, int64_t K, uint64_t T) {
+  int lo = 0, hi = nt - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (P[mid + 1] > T) hi = mid; else lo = mid + 1;
+  }
+  const uint64_t r = (T - P[lo]) << sh[lo];
+  const uint64_t* cm = cq + (int64_t)lo * kTileQ;
+  const int64_t left = K - (int64_t)lo * kTileQ;
+  int l2 = 0, h2 = (int)(left < kTileQ ? left : kTileQ) - 1;
+  while (l2 < h2) {
+    const int mid = (l2 + h2) >> 1;
+    if (cm[mid] > r) h2 = mid; else l2 = mid + 1;
+  }
+  return (int64_t)lo * kTileQ + l2;
+}
 
 // ---- the search of the tile-scaled systematic resampler for ONE tile of 1024 output slots (include/gjx.h,
 // GJX_WEIGHTS_TILE_SCALED): lane t of a 256-thread block owns the slots tix 1024 + 4 t .. + 3 and gets their ancestors.
@@ -146,7 +390,6 @@ GJX_DEV unsigned long long tile_granule(unsigned long long tag, int e, uint64_t 
 // every tile; !PLANNED: Pl [nt + 2], Ebl [nt] are block-shared scratch (every block reduces all nt totals), PLANNED: Pg, shg
 // hold the prefix and the shifts (k_tiled_plan).  tix == 0 also finishes the LSE record of the producing run (lse_mode 2) and
 // flags a dead collection.  Every thread of the block must call it (block barriers inside).
-constexpr int kLiveGranulePad = 8;         // words between the granules of the steps kernel (gjx_gen_steps)
 struct TiledSearchShared {
   float fred[8];
   uint64_t wsum[4];
@@ -204,16 +447,16 @@ GJX_DEV void tiled_search_tile(const float* __restrict__ x, int64_t K, const uin
   if constexpr (LIVE) {
     unsigned budget = (ctrl && (__hip_atomic_load(&ctrl[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & kStatusPollTimeout)) ? 0u : kPollBudget;
     for (int b = threadIdx.x; b < nt; b += 256) {
-      // (one granule per 64-byte line, kLiveGranulePad: blocks that store into a shared line serialise in the L2)
-      unsigned long long v = __hip_atomic_load((const unsigned long long*)&S[(size_t)b * kLiveGranulePad], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      unsigned long long v = __hip_atomic_load((const unsigned long long*)&S[(size_t)b * kGranulePad], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       while ((v >> 60) != rtag && budget) {
         --budget;
         __builtin_amdgcn_s_sleep(1);
-        v = __hip_atomic_load((const unsigned long long*)&S[(size_t)b * kLiveGranulePad], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v = __hip_atomic_load((const unsigned long long*)&S[(size_t)b * kGranulePad], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       if ((v >> 60) != rtag) { if (ctrl) __hip_atomic_fetch_or(&ctrl[2], kStatusPollTimeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); v = 0; }
-      const uint64_t sv = v & ((1ull << 40) - 1);
-      const int e = sv ? (int)((v >> 40) & 0xFFFFFu) + kTileDead : kTileDead;
+      uint64_t sv;
+      int e;
+      tile_granule_unpack(v, sv, e);
       Pl[b + 1] = sv;
       Ebl[b] = e;
       em = fmaxf(em, (float)e);
@@ -235,24 +478,7 @@ GJX_DEV void tiled_search_tile(const float* __restrict__ x, int64_t K, const uin
   __syncthreads();
   Emax = (int)fmaxf(fmaxf(sh.fred[0], sh.fred[1]), fmaxf(sh.fred[2], sh.fred[3]));
   GJX_STAMP(1);
-  {   // shifted totals and their prefix, in place: lane t owns entries [t per, (t+1) per)
-    const int per = (nt + 255) >> 8;
-    const int e0 = threadIdx.x * per < nt ? threadIdx.x * per : nt, e1 = (e0 + per) < nt ? (e0 + per) : nt;
-    uint64_t loc = 0;
-    for (int e = e0; e < e1; ++e) {
-      const int sh = Emax - Ebl[e];
-      const uint64_t g = sh < 64 ? Pl[e + 1] >> sh : 0;
-      Pl[e + 1] = g;
-      loc += g;
-    }
-    const uint64_t inc = wave_scan_u64(loc);
-    if (lane == 63) sh.wsum[wid] = inc;
-    __syncthreads();
-    uint64_t run = inc - loc;
-    for (int w = 0; w < wid; ++w) run += sh.wsum[w];
-    for (int e = e0; e < e1; ++e) { run += Pl[e + 1]; Pl[e + 1] = run; }
-    __syncthreads();
-  }
+  prefix_in_place<256>(Pl, nt, sh.wsum, [&](int b) { return Emax - Ebl[b]; });
   }
   auto shift_of = [&](int t) { return PLANNED ? shg[t] : Emax - Eb[t]; };   // (a tile shifted out entirely is never a source)
   const uint64_t total = P[nt];
@@ -278,36 +504,8 @@ GJX_DEV void tiled_search_tile(const float* __restrict__ x, int64_t K, const uin
     for (int k = 0; k < ITEMS; ++k) {
       const int64_t j = (i0 + k < K) ? i0 + k : K - 1;
       T[k] = comb_threshold(j, u, step, total);
-      tile[k] = 0;
     }
-    auto descend = [&](int k0, int k1) {   // first tile t with P[t + 1] > T (fixed trip count; two slots per pass)
-      for (int sft = 1 << (31 - __builtin_clz((unsigned)nt)); sft >= 1; sft >>= 1) {
-        const int pa = tile[k0] + sft, pb = tile[k1] + sft;
-        if (pa <= nt - 1 && P[pa] <= T[k0]) tile[k0] = pa;
-        if (k1 != k0 && pb <= nt - 1 && P[pb] <= T[k1]) tile[k1] = pb;
-      }
-    };
-    const int wlo = tix - 4 < 0 ? 0 : (tix - 4 > nt - 8 ? (nt - 8 < 0 ? 0 : nt - 8) : tix - 4);
-    uint64_t Pw[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) Pw[k] = P[wlo + k < nt ? wlo + k : nt];
-    if (T[0] >= Pw[0] && T[ITEMS - 1] < Pw[8]) {
-#pragma unroll
-      for (int k = 0; k < ITEMS; ++k) {
-        int tl = wlo;
-#pragma unroll
-        for (int w = 1; w < 8; ++w) tl += Pw[w] <= T[k] ? 1 : 0;
-        tile[k] = tl;
-      }
-    } else {
-      descend(0, ITEMS - 1);
-      if (tile[0] == tile[ITEMS - 1]) {
-#pragma unroll
-        for (int k = 1; k < ITEMS - 1; ++k) tile[k] = tile[0];
-      } else {
-        descend(1, 2);
-      }
-    }
+    source_tiles<ITEMS>(P, nt, tix, T, tile);
     // residual of every slot in its source tile's own units (< S of that tile)
     uint64_t Tr[ITEMS];
 #pragma unroll
@@ -319,91 +517,37 @@ GJX_DEV void tiled_search_tile(const float* __restrict__ x, int64_t K, const uin
     GJX_STAMP(3);
     const bool windowed = tmin >= w0 && tmax <= w0 + 2;       // block-uniform: every source tile is among the three loaded at the top
     if (windowed) {
-      // cumulative q of the window tiles the slots fall into (usually two), each against its own exponent, relative to
-      // the tile's start: sh.cumL[c] for tile w0 + c
-      uint64_t qi[CH][ITEMS], sacc[CH], inc[CH];
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
+      // cumulative q of the window tiles the slots fall into (usually two), each against its own exponent: sh.cumL[c] for tile w0 + c
+      // (the log-weights beyond K are -inf: they quantise to 0)
+      rescan_round<256, TILE, ITEMS, CH>(sh.cumL, &sh.s_wtot[0][0], [&](int c, int, uint64_t (&q)[ITEMS]) {
         const int tc = w0 + c;
-        sacc[c] = 0; inc[c] = 0;
-        if (tc < tmin || tc > tmax) continue;                 // block-uniform
-        const int es = Eb[tc];
-        const int64_t p0 = (int64_t)tc * TILE + (int64_t)threadIdx.x * ITEMS;
-        if (p0 + ITEMS <= K) {
+        if (tc < tmin || tc > tmax) return false;                 // block-uniform
 #pragma unroll
-          for (int k = 0; k < ITEMS; ++k) { sacc[c] += tile_q(xw[c][k], es); qi[c][k] = sacc[c]; }
-        } else {
+        for (int k = 0; k < ITEMS; ++k) q[k] = tile_q(xw[c][k], Eb[tc]);
+        return true;
+      }, [] {});
 #pragma unroll
-          for (int k = 0; k < ITEMS; ++k) { sacc[c] += p0 + k < K ? tile_q(xw[c][k], es) : 0; qi[c][k] = sacc[c]; }
-        }
-        inc[c] = wave_scan_u64(sacc[c]);
-        if (lane == 63) sh.s_wtot[c][wid] = inc[c];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int c = 0; c < CH; ++c) {
-        const int tc = w0 + c;
-        if (tc < tmin || tc > tmax) continue;
-        uint64_t base = inc[c] - sacc[c];
-        for (int w = 0; w < wid; ++w) base += sh.s_wtot[c][w];
-#pragma unroll
-        for (int k = 0; k < ITEMS; ++k) sh.cumL[c * TILE + threadIdx.x * ITEMS + k] = base + qi[c][k];
-      }
-      __syncthreads();
-    }
-    auto search = [&](const uint64_t* cm, uint64_t r) {   // entries <= r among TILE (4-ary: three independent probes per level)
-      int pos = 0;
-#pragma unroll
-      for (int q = TILE >> 2; q >= 1; q >>= 2) {
-        const uint64_t pa = cm[pos + q - 1], pb = cm[pos + 2 * q - 1], pc = cm[pos + 3 * q - 1];
-        pos += (pa <= r ? q : 0) + (pb <= r ? q : 0) + (pc <= r ? q : 0);
-      }
-      return pos;
-    };
-    if (windowed) {
-#pragma unroll
-      for (int k = 0; k < ITEMS; ++k) anc[k] = (int32_t)((int64_t)tile[k] * TILE + search(sh.cumL + (tile[k] - w0) * TILE, Tr[k]));
+      for (int k = 0; k < ITEMS; ++k) anc[k] = (int32_t)((int64_t)tile[k] * TILE + rank_in_tile<TILE>(sh.cumL + (tile[k] - w0) * TILE, Tr[k]));
     } else {
       // collapsed or strongly drifting weights: re-scan the source tiles CH at a time (tiles without weight are skipped)
       const int ntiles = tmax - tmin + 1;
       auto next_live = [&](int at) { while (at < ntiles && P[tmin + at + 1] == P[tmin + at]) ++at; return at; };
       for (int idx = 0; idx < ntiles;) {
         const int nidx = next_live(idx + CH);
-        uint64_t qi[CH][ITEMS], sacc[CH], inc[CH];
         __syncthreads();         // every lane is done searching the previous contents of sh.cumL
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          const bool on = idx + c < ntiles;
-          const int tsrc = on ? tmin + idx + c : 0;
-          const int64_t p0 = (int64_t)tsrc * TILE + (int64_t)threadIdx.x * ITEMS;
+        rescan_round<256, TILE, ITEMS, CH>(sh.cumL, &sh.s_wtot[0][0], [&](int c, int o, uint64_t (&q)[ITEMS]) {
+          if (idx + c >= ntiles) return false;
+          const int tsrc = tmin + idx + c;
           float nv[ITEMS];
+          load_tile((int64_t)tsrc * TILE + o, nv);
 #pragma unroll
-          for (int k = 0; k < ITEMS; ++k) nv[k] = -INFINITY;
-          if (on) load_tile(p0, nv);
-          const int es = Eb[tsrc];
-          sacc[c] = 0;
-#pragma unroll
-          for (int k = 0; k < ITEMS; ++k) { sacc[c] += (on && p0 + k < K) ? tile_q(nv[k], es) : 0; qi[c][k] = sacc[c]; }
-        }
-#pragma unroll
-        for (int c = 0; c < CH; ++c) inc[c] = wave_scan_u64(sacc[c]);
-        if (lane == 63) {
-#pragma unroll
-          for (int c = 0; c < CH; ++c) sh.s_wtot[c][wid] = inc[c];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          uint64_t base = inc[c] - sacc[c];
-          for (int w = 0; w < wid; ++w) base += sh.s_wtot[c][w];
-#pragma unroll
-          for (int k = 0; k < ITEMS; ++k) sh.cumL[c * TILE + threadIdx.x * ITEMS + k] = base + qi[c][k];
-        }
-        __syncthreads();
+          for (int k = 0; k < ITEMS; ++k) q[k] = tile_q(nv[k], Eb[tsrc]);
+          return true;
+        }, [] {});
 #pragma unroll
         for (int k = 0; k < ITEMS; ++k) {
           const int kp = tile[k] - tmin;
-          if (kp >= idx && kp < idx + CH) anc[k] = (int32_t)((int64_t)tile[k] * TILE + search(sh.cumL + (kp - idx) * TILE, Tr[k]));
+          if (kp >= idx && kp < idx + CH) anc[k] = (int32_t)((int64_t)tile[k] * TILE + rank_in_tile<TILE>(sh.cumL + (kp - idx) * TILE, Tr[k]));
         }
         idx = nidx;
       }

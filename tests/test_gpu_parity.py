@@ -535,7 +535,7 @@ def test_resampling_fuzz_against_oracle(K_, oracle):
     np.testing.assert_array_equal(_np(got), oracle.resample_systematic(cum_o, 0.25, K))
 
 
-@pytest.mark.parametrize("K", [1, 255, 4096, 65_537, 1 << 18, (1 << 18) + 1024, 999_999, 1 << 20])
+@pytest.mark.parametrize("K", [1, 255, 4096, 16 * 1024 + 5, 65_537, 1 << 18, (1 << 18) + 1024, 999_999, 1 << 20])
 @pytest.mark.parametrize("kind", ["normal", "wide", "two_ends", "one", "stretch"])
 def test_one_launch_resample_gather(K_, oracle, K, kind):
     """gjx_resample_gather (weights -> ancestors -> children in one co-resident launch, consumer side: binary search

@@ -294,7 +294,7 @@ def _resample_worker(rank, world, port, K_total, R, shape, q):
         raise
 
 
-@pytest.mark.parametrize("world,shape", [(1, "mild"), (2, "mild"), (2, "wide"), (4, "first"), (4, "dead_tiles"), (2, "spiky")])
+@pytest.mark.parametrize("world,shape", [(1, "mild"), (1, "first"), (1, "spiky"), (2, "mild"), (2, "wide"), (4, "first"), (4, "dead_tiles"), (2, "spiky")])
 def test_peer_resample_gather_equals_unsharded(world, shape):
     """gjx_peer_resample_gather on `world` ranks == gjx_resample_indices_tiled + gjx_gather_rows on the whole collection:
     ancestors and children bit for bit (children crossing rank boundaries in both directions, dead and shifted-out tiles,

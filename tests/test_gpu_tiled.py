@@ -49,10 +49,13 @@ def _weight_shapes(K, rs):
     one = np.full(K, -np.inf, np.float32)
     one[K // 3] = -1234.5
     yield "one_live", one
+    first = np.full(K, -np.inf, np.float32)
+    first[min(5, K - 1)] = -1234.5                     # ... in tile 0: every block but the first few searches outside its window
+    yield "one_live_tile0", first
     yield "ramp", np.linspace(-60000.0, 0.0, K).astype(np.float32)   # tile exponents span the whole shift range
 
 
-@pytest.mark.parametrize("K,N", [(1, 1), (777, 777), (1024, 1024), (1025, 3000), (10_000, 10_000), (1 << 18, 1 << 18), ((1 << 20) + 5, 1 << 19)])
+@pytest.mark.parametrize("K,N", [(1, 1), (777, 777), (1024, 1024), (1025, 3000), (10_000, 10_000), (16 * 1024 + 5, 16 * 1024 + 5), (1 << 18, 1 << 18), ((1 << 20) + 5, 1 << 19)])
 def test_tiled_resampler_against_oracle(K_, oracle, K, N):
     import torch
     rs = np.random.default_rng(K)
@@ -289,7 +292,7 @@ def test_tiled_bootstrap_filter_full_size(K_):
     np.testing.assert_allclose(_np(out["increments"]), incs, atol=0.2)
 
 
-@pytest.mark.parametrize("K", [1, 777, 1024, 4096 + 3, 100_000, 1 << 20, (1 << 22) - 5])
+@pytest.mark.parametrize("K", [1, 777, 1024, 4096 + 3, 16 * 1024 + 5, 100_000, 1 << 20, (1 << 22) - 5])
 def test_plain_launch_resample_gather_equals_the_three_launch_tiled_resampler(K_, K):
     """gjx_resample_gather_tiled (ONE plain launch: tile totals read, no block waits for another) gives the ancestors of
     gjx_resample_indices_tiled — itself compared with the oracle above — bit for bit, for every weight shape (collapsed
@@ -313,7 +316,7 @@ def test_plain_launch_resample_gather_equals_the_three_launch_tiled_resampler(K_
     assert (_np(anc) == np.arange(K)).all() and K_.workspace_status(ws, raise_on_error=False) == 2
 
 
-@pytest.mark.parametrize("K", [777, 100_000, 1 << 20])
+@pytest.mark.parametrize("K", [777, 16 * 1024 + 5, 100_000, 1 << 20])
 def test_plain_launch_resample_gather_planned_form(K_, K, monkeypatch):
     """the form for many tiles (prefix and shifts computed once by k_tiled_plan and read from memory; what K > 2^20 runs),
     forced at small sizes: the same ancestors"""

@@ -233,7 +233,10 @@ def test_a_return_value_through_the_torch_path():
 @pytest.mark.parametrize("body", [
     lambda a, b, x: x.sum(keepdims=True), lambda a, b, x: np.sum(x, keepdims=True), lambda a, b, x: x.sum(axis=1), lambda a, b, x: np.max(x, axis=1),
     lambda a, b, x: np.add.accumulate(x), lambda a, b, x: np.arctan(a), lambda a, b, x: genjax.logsumexp(x, axis=1),
-    lambda a, b, x: np.multiply.reduce(x), lambda a, b, x: np.linalg.norm(x)], ids=str)
+    lambda a, b, x: np.multiply.reduce(x), lambda a, b, x: np.linalg.norm(x)],
+    # names, not str(): a lambda's repr holds its address, which differs from run to run
+    ids=["method_sum_keepdims", "np_sum_keepdims", "method_sum_axis1", "np_max_axis1", "add_accumulate", "arctan", "logsumexp_axis1",
+         "multiply_reduce", "linalg_norm"])
 def test_what_is_not_supported_says_so(body):
     with pytest.raises(genjax.NotSupportedInModelBody):
         _model(body).site_list(())
