@@ -500,6 +500,14 @@ class ScanBootstrapFilter:
                     return out["choices"][p.slot_of[s.addr]: p.slot_of[s.addr] + s.dim]
         raise KeyError(name)
 
+    def posterior_moments(self, out: dict, name, cov: bool = False) -> dict:
+        """E[x_T | y_{1:T}] and the spread about it from the run's last particles: ``self.latent(out, name)`` under ``out["logw"]`` in
+        one gjx_weighted_moments call -> dict(mean f32[dim], var f32[dim]), or dict(mean, cov f32[dim][dim]) with ``cov``"""
+        from .. import kernels
+        want = "cov" if cov else "var"
+        m = kernels.weighted_moments(self.latent(out, name), out["logw"], want)
+        return {"mean": m["mean"], want: m[want]}
+
 
 class ScanHistory:
     """Record of a filter run over a Scan: the choices of every step (SoA rows of the step's program) and the ancestors of every

@@ -51,6 +51,58 @@ class Target:
         return ("Target", _IdKey(self.p), _args_key(self.args), tuple(items))
 
 
+class Moments:
+    """Posterior means and variances of every choice of a weighted collection, computed by ONE gjx_weighted_moments call over the whole
+    ``choices`` matrix (the reference's users write ``jnp.average(x, weights=w)`` per address).  ``mean(addr)`` / ``variance(addr)``
+    are views into the device results: 0-d for a scalar site, f32[dim] for a vector site, f32[T][...] for the stacked name of Scan
+    sites ``("x", t)`` (what ``Trace.get_choices`` stacks under ``"x"``); a collection of trials adds a leading ``n_trials`` axis.
+    A site constrained to one shared value reports that value and variance 0.  Discrete sites are stored as floats: the mean of a
+    ``flip`` is its posterior probability.  The variance is the population form: sum w (x - mean)^2 / sum w."""
+
+    def __init__(self, trace: Trace, stats, mean, var):
+        self._trace, self.stats, self._mean, self._var = trace, stats, mean, var     # stats [..][4], mean / var [..][n_slots]
+
+    @property
+    def ess(self):
+        """effective sample size of the weights (0-d, or f32[n_trials])"""
+        return self.stats[..., 3]
+
+    def _site(self, arr, s, shared_value: bool):
+        import torch
+        slot = self._trace.prog.slot_of[s.addr]
+        if slot >= 0:
+            v = arr[..., slot:slot + s.dim]
+        else:
+            sh = np.broadcast_to(np.asarray(self._trace.shared[s.addr], np.float32).ravel(), (s.dim,)).copy()
+            v = torch.as_tensor(sh if shared_value else np.zeros_like(sh), device=arr.device).expand(*arr.shape[:-1], s.dim)
+        return v[..., 0] if s.dim == 1 else v
+
+    def _get(self, arr, addr, shared_value: bool):
+        import torch
+        from ..core import key_of
+        sl = self._trace.prog.site_list
+        k = addr if addr in sl else key_of(addr)
+        if k in sl:
+            return self._site(arr, sl[k], shared_value)
+        steps = [s for s in sl.sites if isinstance(s.addr, tuple) and len(s.addr) == 2 and s.addr[0] == k and isinstance(s.addr[1], int)]
+        if not steps:
+            raise KeyError(addr)
+        return torch.stack([self._site(arr, s, shared_value) for s in steps], dim=arr.dim() - 1)
+
+    def mean(self, addr):
+        return self._get(self._mean, addr, True)
+
+    def variance(self, addr):
+        return self._get(self._var, addr, False)
+
+
+def _moments_of(trace: Trace, log_weights, n_segments: int = 1) -> Moments:
+    from .. import kernels
+    rows = trace.choices if trace.choices.shape[0] > 0 else log_weights.reshape(1, -1)    # (no per-particle slot: the stats alone)
+    m = kernels.weighted_moments(rows, log_weights, "var", n_segments)
+    return Moments(trace, m["stats"], m["mean"], m["var"])
+
+
 class ParticleCollection:
     """Weighted particles (smc.py:76-109): a batched Trace + log-weights, all on the device."""
 
@@ -93,6 +145,36 @@ class ParticleCollection:
         from .. import kernels
         return kernels.ess(self.log_weights)[3]
 
+    def moments(self) -> Moments:
+        """posterior mean and variance of every choice under the collection's weights (one gjx_weighted_moments call, kept)"""
+        if getattr(self, "_moments", None) is None:
+            self._moments = _moments_of(self.particles, self.log_weights)
+        return self._moments
+
+    def mean(self, addr):
+        """E[addr] under the self-normalised weights: ``moments().mean(addr)``"""
+        return self.moments().mean(addr)
+
+    def variance(self, addr):
+        """Var[addr] (population form) under the self-normalised weights: ``moments().variance(addr)``"""
+        return self.moments().variance(addr)
+
+    def covariance(self, addr):
+        """f32[dim][dim]: the weighted covariance matrix of the components of ONE site, from one gjx_weighted_moments call over its rows"""
+        import torch
+        from .. import _abi as A
+        from .. import kernels
+        from ..core import key_of
+        tr = self.particles
+        sl = tr.prog.site_list
+        s = sl[addr if addr in sl else key_of(addr)]
+        if s.dim > A.MOMENTS_MAX_COV_ROWS:
+            raise ValueError(f"covariance({addr!r}): the site has {s.dim} components, a covariance takes at most {A.MOMENTS_MAX_COV_ROWS}")
+        slot = tr.prog.slot_of[s.addr]
+        if slot < 0:                                      # one shared value: no spread
+            return torch.zeros((s.dim, s.dim), dtype=torch.float32, device=self.log_weights.device)
+        return kernels.weighted_moments(tr.choices[slot:slot + s.dim], self.log_weights, "cov")["cov"]
+
     def lse_partials(self):
         """kernels.RunPartials of the producing run if still valid (for ``inference.pf.resample(..., collection=)``)"""
         p = self._partials
@@ -132,6 +214,16 @@ class TrialCollections:
 
     def get_log_weights(self):
         return self.log_weights.view(self.n_trials, self.K)
+
+    def moments(self) -> Moments:
+        """per-trial posterior means and variances of every choice, each trial normalised on its own: a Moments whose results carry a
+        leading ``n_trials`` axis (one gjx_weighted_moments call with n_segments = n_trials, kept)"""
+        if getattr(self, "_moments", None) is None:
+            self._moments = _moments_of(self.particles, self.log_weights, self.n_trials)
+            if self.n_trials == 1:                        # (the kernel wrapper drops a segment axis of 1)
+                m = self._moments
+                self._moments = Moments(m._trace, m.stats[None], m._mean[None], m._var[None])
+        return self._moments
 
     def get_log_marginal_likelihood_estimates(self):
         """f32[n_trials]: logsumexp(log_weights of the trial) - log K  (smc.py:96-97 per trial)"""

@@ -392,6 +392,53 @@ def ess(logw: torch.Tensor, ws=None) -> torch.Tensor:
     return out
 
 
+_MOMENTS_WANT = {"mean": A.MOMENTS_MEAN, "var": A.MOMENTS_VAR, "cov": A.MOMENTS_COV}
+
+
+def weighted_moments(rows: torch.Tensor, logw=None, want: str = "var", n_segments: int = 1, ws=None) -> dict:
+    """gjx_weighted_moments: rows f32[n_rows][K] (a view is fine as long as its column stride is 1) and log-weights f32[K] (None: equal
+    weights) -> dict(stats f32[4] = {max, sum e, sum e^2, ESS}, mean f32[n_rows], and var f32[n_rows] | cov f32[n_rows][n_rows]):
+    the self-normalised weighted mean and the population (co)variance about it; dead particles (weight -inf / NaN) are left out.
+    ``n_segments`` > 1: the K particles are that many consecutive segments, each normalised on its own, and every output
+    gets a leading segment axis.  Two launches, bit-reproducible."""
+    if want not in _MOMENTS_WANT:
+        raise ValueError(f"weighted_moments: want is 'mean', 'var' or 'cov', not {want!r}")
+    if rows.dim() == 1:
+        rows = rows.unsqueeze(0)
+    if rows.dim() != 2 or rows.dtype != torch.float32:
+        raise ValueError("weighted_moments: rows must be f32[n_rows][K]")
+    n_rows, K = int(rows.shape[0]), int(rows.shape[1])
+    if K > 1 and rows.stride(1) != 1:
+        raise ValueError("weighted_moments: the particles of a row must be contiguous (column stride 1)")
+    stride = int(rows.stride(0)) if n_rows > 1 else K
+    if stride < K:
+        raise ValueError("weighted_moments: rows overlap (row stride < K)")
+    if want == "cov" and n_rows > A.MOMENTS_MAX_COV_ROWS:
+        raise ValueError(f"weighted_moments: a covariance takes at most {A.MOMENTS_MAX_COV_ROWS} rows, not {n_rows}")
+    if logw is not None:
+        if logw.dtype != torch.float32 or logw.numel() != K:
+            raise ValueError("weighted_moments: logw must be f32[K]")
+        logw = logw.reshape(-1)
+        if K > 1 and logw.stride(0) != 1:
+            logw = logw.contiguous()
+    S, code = int(n_segments), _MOMENTS_WANT[want]
+    if S <= 0 or K <= 0 or K % S:
+        raise ValueError(f"weighted_moments: {S} segments do not divide {K} particles")
+    dev = rows.device
+    need = load().gjx_weighted_moments_workspace_bytes(n_rows, K, S, code)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)        # partials only: needs no initialisation
+    stats = torch.empty((S, 4), dtype=torch.float32, device=dev)
+    mean = torch.empty((S, n_rows), dtype=torch.float32, device=dev)
+    second = None if want == "mean" else torch.empty((S, n_rows) + ((n_rows,) if want == "cov" else ()), dtype=torch.float32, device=dev)
+    check(load().gjx_weighted_moments(_ptr(rows), stride, n_rows, _ptr(logw), K, S, code, _ptr(stats), _ptr(mean), _ptr(second),
+                                      _ptr(ws), ws.numel(), _stream()), "gjx_weighted_moments")
+    out = {"stats": stats, "mean": mean}
+    if second is not None:
+        out[want] = second
+    return {k: v[0] for k, v in out.items()} if S == 1 else out
+
+
 def resample_sorted_multinomial_tiled(logw: torch.Tensor, key, N: int | None = None, anc=None, cum=None, ws=None, want_q=False):
     """gjx_resample_sorted_multinomial_tiled: log-weights -> MULTINOMIAL ancestors (sorted uniforms from exponential spacings under
     `key`, tile-scaled fixed point), non-decreasing.  -> ancestors int32[N], or (ancestors, q, e) with want_q"""

@@ -897,6 +897,35 @@ int gjx_scan_filter_adaptive_history(const gjx_program* steps, int32_t T, uint32
  * max); NaN and -inf weights count as dead, a dead collection gives {-inf, 0, 0, 0}.  The reduction of the filter above (one launch,
  * 4 B read per particle).  workspace: gjx_workspace_bytes(GJX_OP_RESAMPLE, K), zero-filled once. */
 int gjx_ess(const float* logw, int64_t K, float* out4, void* workspace, size_t workspace_bytes, void* stream);
+/* Weighted posterior moments of a particle collection: means, and variances or a covariance matrix, of n_rows rows under the
+ * self-normalised weights of logw (NULL: equal weights).  The reference has no counterpart: its users write
+ * jnp.average(x, weights=jnp.exp(logw - logw.max())) and a second line for the variance.
+ *   rows    SoA f32[n_rows][row_stride] (the layout of a trace's choices and of the filter's row buffers), row_stride >= K
+ *   The K particles are n_segments consecutive segments of K / n_segments particles (K must divide evenly), each normalised on its
+ *   own: the trials of one n_trials * K-particle run.  With e_i = exp(logw_i - max over the segment), per segment:
+ *   stats   f32[n_segments][4]  = {max, sum e, sum e^2, ESS = (sum e)^2 / sum e^2}, as gjx_ess
+ *   mean    f32[n_segments][n_rows]:           mean_r = sum e_i x_ri / sum e_i
+ *   second  GJX_MOMENTS_VAR: f32[n_segments][n_rows], GJX_MOMENTS_COV: f32[n_segments][n_rows][n_rows] (exactly symmetric),
+ *           GJX_MOMENTS_MEAN: not written, may be NULL:
+ *           sum e_i (x_ri - mean_r) (x_si - mean_s) / sum e_i — the POPULATION form of the weighted (co)variance: no n / (n - 1)
+ *           or ESS correction.
+ * A particle whose weight is -inf or NaN is dead: it is selected out by its weight and contributes nothing, whatever its row values
+ * (NaN, inf).  A segment without a live particle gets stats {-inf, 0, 0, 0} and NaN means and second moments ("no weight, no
+ * estimate").  Float32 throughout; second moments are accumulated centred: every 1024-particle tile centres the values it holds in
+ * registers on its own weighted mean, and the tiles are merged by the pairwise update of Chan, Golub and LeVeque in an order that
+ * depends on K / n_segments alone.  Two launches (tiles; merge), no atomics, no block waits for another: the outputs are
+ * bit-reproducible, and a segment's outputs are those of a call on that segment alone.  Rows whose address is not 16-byte aligned
+ * (a view that starts at an odd column) take a scalar load path.
+ * Traffic: 4 B per particle for the weights and 4 B per particle and row, each read once.
+ * GJX_EINVAL: a NULL rows, stats, mean or workspace, second NULL with want != GJX_MOMENTS_MEAN, K <= 0, n_rows <= 0, row_stride < K,
+ * n_segments <= 0 or not dividing K, an unknown want.  GJX_EUNSUPPORTED: GJX_MOMENTS_COV with n_rows > GJX_MOMENTS_MAX_COV_ROWS
+ * (means and variances take any n_rows).  GJX_EWORKSPACE: less than gjx_weighted_moments_workspace_bytes(...) of the same
+ * arguments (0 for arguments the call refuses); the workspace needs no initialisation.  Nothing is launched on a refusal. */
+enum { GJX_MOMENTS_MEAN = 0, GJX_MOMENTS_VAR = 1, GJX_MOMENTS_COV = 2 };
+#define GJX_MOMENTS_MAX_COV_ROWS 16
+size_t gjx_weighted_moments_workspace_bytes(int32_t n_rows, int64_t K, int64_t n_segments, int32_t want);
+int gjx_weighted_moments(const float* rows, int64_t row_stride, int32_t n_rows, const float* logw, int64_t K, int64_t n_segments,
+                         int32_t want, float* stats, float* mean, float* second, void* workspace, size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
