@@ -56,6 +56,7 @@ WEIGHTS_GLOBAL_MAX, WEIGHTS_TILE_SCALED = 0, 1      # gjx.h: fixed-point weight 
 WEIGHTS_PLAIN_LAUNCHES = 256                        # OR-ed into the scheme: plain launches only (the repeat after a poll time-out)
 MOMENTS_MEAN, MOMENTS_VAR, MOMENTS_COV = 0, 1, 2   # gjx_weighted_moments: what is wanted beside the means
 MOMENTS_MAX_COV_ROWS = 16
+QUANTILES_MAX_LEVELS, HISTOGRAM_MAX_BINS = 16, 4096   # gjx_weighted_quantiles / gjx_weighted_histogram: the caps of one call
 MAX_PARAMS = 4
 
 i32, i64, u32, u64, f32, f64 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_double
@@ -201,6 +202,10 @@ PROTOTYPES = {
     "gjx_ess": (C.c_int, [vp, i64, vp, vp, C.c_size_t, vp]),
     "gjx_weighted_moments_workspace_bytes": (C.c_size_t, [i32, i64, i64, i32]),
     "gjx_weighted_moments": (C.c_int, [vp, i64, i32, vp, i64, i64, i32, vp, vp, vp, vp, C.c_size_t, vp]),
+    "gjx_weighted_quantiles_workspace_bytes": (C.c_size_t, [i32, i64, i64, i32]),
+    "gjx_weighted_quantiles": (C.c_int, [vp, i64, i32, vp, i64, i64, vp, i32, vp, vp, vp, C.c_size_t, vp]),
+    "gjx_weighted_histogram_workspace_bytes": (C.c_size_t, [i32, i64, i64, i32]),
+    "gjx_weighted_histogram": (C.c_int, [vp, i64, i32, vp, i64, i64, f32, f32, i32, vp, vp, vp, C.c_size_t, vp]),
     "gjx_program_filter_source": (i64, [PP, i32, C.c_char_p, i64]),
     "gjx_program_filter_precompile": (C.c_int, [PP, i32]),
     "gjx_resample_indices_tiled": (C.c_int, [vp, i64, f64, i64, vp, vp, vp, vp, vp, C.c_size_t, vp]),

@@ -508,6 +508,13 @@ class ScanBootstrapFilter:
         m = kernels.weighted_moments(self.latent(out, name), out["logw"], want)
         return {"mean": m["mean"], want: m[want]}
 
+    def posterior_quantiles(self, out: dict, name, q=(0.05, 0.5, 0.95)):
+        """quantiles of x_T | y_{1:T} from the run's last particles: ``self.latent(out, name)`` under ``out["logw"]`` in one
+        gjx_weighted_quantiles call -> f32[dim][n_levels] ([dim] for a scalar ``q``)"""
+        from .. import kernels
+        r = kernels.weighted_quantiles(self.latent(out, name), out["logw"], q)["q"]
+        return r[:, 0] if isinstance(q, (int, float)) else r
+
 
 class ScanHistory:
     """Record of a filter run over a Scan: the choices of every step (SoA rows of the step's program) and the ancestors of every

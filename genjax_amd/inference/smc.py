@@ -103,6 +103,107 @@ def _moments_of(trace: Trace, log_weights, n_segments: int = 1) -> Moments:
     return Moments(trace, m["stats"], m["mean"], m["var"])
 
 
+def _estimate_sites(trace: Trace, addr, lead: int, of_rows, of_shared):
+    """an estimate of every component of the site(s) ``addr`` names, addresses resolved exactly as ``Moments._get`` resolves them:
+    ``of_rows(rows [n][K])`` -> tensor [lead axes][n][X] for per-particle rows (ONE call where the sites' slots are adjacent),
+    ``of_shared(value)`` -> tensor [lead axes][X] for a component constrained to one shared value.  -> [lead axes][T?][dim?][X]"""
+    import torch
+    from ..core import key_of
+    sl = trace.prog.site_list
+    k = addr if addr in sl else key_of(addr)
+    if k in sl:
+        sites, stacked = [sl[k]], False
+    else:
+        sites = [s for s in sl.sites if isinstance(s.addr, tuple) and len(s.addr) == 2 and s.addr[0] == k and isinstance(s.addr[1], int)]
+        stacked = True
+        if not sites:
+            raise KeyError(addr)
+    slots = [trace.prog.slot_of[s.addr] for s in sites]
+    live = [(a, s.dim) for a, s in zip(slots, sites) if a >= 0]
+    block, a0 = None, 0
+    if len(live) > 1 and max(a + d for a, d in live) - min(a for a, _ in live) == sum(d for _, d in live):
+        a0 = min(a for a, _ in live)
+        block = of_rows(trace.choices[a0:max(a + d for a, d in live)])
+    outs = []
+    for a, s in zip(slots, sites):
+        if a >= 0:
+            v = block[..., a - a0:a - a0 + s.dim, :] if block is not None else of_rows(trace.choices[a:a + s.dim])
+        else:
+            sh = np.broadcast_to(np.asarray(trace.shared[s.addr], np.float32).ravel(), (s.dim,))
+            v = torch.stack([of_shared(x) for x in sh], dim=lead)
+        outs.append(v[..., 0, :] if s.dim == 1 else v)
+    return torch.stack(outs, dim=lead) if stacked else outs[0]
+
+
+def _quantile_of(trace: Trace, log_weights, addr, q, n_segments: int = 1, lead: int = 0):
+    import torch
+    from .. import _abi as A
+    from .. import kernels
+    scalar = isinstance(q, (int, float))
+    levels = [float(q)] if scalar else [float(v) for v in q]
+    dev = log_weights.device
+
+    def of_rows(rows):
+        r = kernels.weighted_quantiles(rows, log_weights, levels, n_segments)["q"]
+        return r[None] if lead and n_segments == 1 else r
+
+    def of_shared(x):                                     # one shared value: every quantile is that value
+        return torch.full((n_segments,) * lead + (len(levels),), float(x), dtype=torch.float32, device=dev)
+
+    if not levels or len(levels) > A.QUANTILES_MAX_LEVELS or any(not (0.0 <= v <= 1.0) for v in levels):
+        raise ValueError(f"quantile({addr!r}): 1 to {A.QUANTILES_MAX_LEVELS} levels in [0, 1], not {levels}")
+    out = _estimate_sites(trace, addr, lead, of_rows, of_shared)
+    return out[..., 0] if scalar else out
+
+
+def _histogram_of(trace: Trace, log_weights, addr, bins: int, span, n_segments: int = 1, lead: int = 0):
+    """-> (mass [lead axes][T?][dim?][bins + 2], edges f32[bins + 1])"""
+    import torch
+    from .. import kernels
+    dev = log_weights.device
+    lo, hi, nb = np.float32(span[0]), np.float32(span[1]), int(bins)
+    edges = []
+
+    def of_rows(rows):
+        h = kernels.weighted_histogram(rows, log_weights, nb, (lo, hi), n_segments)
+        edges.append(h["edges"])
+        return h["mass"][None] if lead and n_segments == 1 else h["mass"]
+
+    def of_shared(x):                                     # one shared value: all the weight in its entry (the library's bin formula)
+        x = np.float32(x)
+        if x < lo:
+            e = 0
+        elif not x < hi:
+            e = nb + 1
+        else:
+            b = np.floor(np.float32(np.float32(x - lo) * (np.float32(nb) / np.float32(hi - lo))))
+            e = 1 + int(b) if b < nb else nb + 1
+        m = torch.zeros((n_segments,) * lead + (nb + 2,), dtype=torch.float32, device=dev)
+        m[..., e] = 1.0
+        return m
+
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi) or nb <= 0:
+        raise ValueError(f"histogram({addr!r}): bins > 0 and a finite range with lo < hi, not {bins}, {tuple(span)}")
+    mass = _estimate_sites(trace, addr, lead, of_rows, of_shared)
+    if not edges:
+        edges.append(torch.tensor([float(lo) + (float(hi) - float(lo)) * i / nb for i in range(nb)] + [float(hi)], dtype=torch.float32, device=dev))
+    return mass, edges[0]
+
+
+def _probabilities_of(trace: Trace, log_weights, addr, n_segments: int = 1, lead: int = 0):
+    """posterior probabilities of the values 0 .. ncat - 1 of a discrete site: the histogram with one bin per value, inner bins only"""
+    from .. import _abi as A
+    from ..core import key_of
+    sl = trace.prog.site_list
+    k = addr if addr in sl else key_of(addr)
+    s = sl[k]
+    ncat = 2 if s.kind in (A.FLIP, A.BERNOULLI_LOGITS) else int(s.ncat)
+    if ncat <= 0:
+        raise ValueError(f"probabilities({addr!r}): the site is neither a flip nor a categorical; use histogram(addr, bins, range)")
+    mass, _ = _histogram_of(trace, log_weights, k, ncat, (-0.5, ncat - 0.5), n_segments, lead)
+    return mass[..., 1:ncat + 1]
+
+
 class ParticleCollection:
     """Weighted particles (smc.py:76-109): a batched Trace + log-weights, all on the device."""
 
@@ -175,6 +276,35 @@ class ParticleCollection:
             return torch.zeros((s.dim, s.dim), dtype=torch.float32, device=self.log_weights.device)
         return kernels.weighted_moments(tr.choices[slot:slot + s.dim], self.log_weights, "cov")["cov"]
 
+    def quantile(self, addr, q):
+        """the weighted quantile(s) of a site at the level(s) ``q`` in [0, 1] (NumPy's "inverted_cdf" under the self-normalised weights:
+        always the value of a live particle; one gjx_weighted_quantiles call, a radix select — no sort): 0-d for a scalar site and a
+        scalar ``q``, else [dim], [n_levels] or [dim][n_levels]; [T][...] for the stacked name of Scan sites.  A site constrained to one
+        shared value reports that value."""
+        return _quantile_of(self.particles, self.log_weights, addr, q)
+
+    def median(self, addr):
+        """``quantile(addr, 0.5)``"""
+        return self.quantile(addr, 0.5)
+
+    def credible_interval(self, addr, mass: float = 0.9):
+        """the equal-tailed interval that holds ``mass`` of the posterior: the quantiles at (1 - mass) / 2 and (1 + mass) / 2 on a
+        trailing axis of size 2"""
+        m = float(mass)
+        if not 0.0 <= m <= 1.0:
+            raise ValueError(f"credible_interval({addr!r}): mass must be in [0, 1], not {mass}")
+        return self.quantile(addr, ((1.0 - m) / 2.0, (1.0 + m) / 2.0))
+
+    def histogram(self, addr, bins: int, range):
+        """the weighted marginal of a site over ``bins`` equal bins of ``range`` = (lo, hi) (one gjx_weighted_histogram call)
+        -> (mass [dim?][bins + 2], edges f32[bins + 1]); mass[..., 0] is the weight below lo, mass[..., bins + 1] the weight at or above
+        hi (and of NaN values), and the entries of a row sum to 1"""
+        return _histogram_of(self.particles, self.log_weights, addr, bins, range)
+
+    def probabilities(self, addr):
+        """the posterior probabilities of a discrete site: f32[2] for a flip, f32[ncat] for a categorical (ValueError for any other)"""
+        return _probabilities_of(self.particles, self.log_weights, addr)
+
     def lse_partials(self):
         """kernels.RunPartials of the producing run if still valid (for ``inference.pf.resample(..., collection=)``)"""
         p = self._partials
@@ -224,6 +354,15 @@ class TrialCollections:
                 m = self._moments
                 self._moments = Moments(m._trace, m.stats[None], m._mean[None], m._var[None])
         return self._moments
+
+    def quantile(self, addr, q):
+        """per-trial weighted quantiles: ``ParticleCollection.quantile`` with a leading ``n_trials`` axis, every trial normalised on
+        its own (one gjx_weighted_quantiles call with n_segments = n_trials)"""
+        return _quantile_of(self.particles, self.log_weights, addr, q, self.n_trials, 1)
+
+    def probabilities(self, addr):
+        """per-trial posterior probabilities of a discrete site: f32[n_trials][2 | ncat] (one call with n_segments = n_trials)"""
+        return _probabilities_of(self.particles, self.log_weights, addr, self.n_trials, 1)
 
     def get_log_marginal_likelihood_estimates(self):
         """f32[n_trials]: logsumexp(log_weights of the trial) - log K  (smc.py:96-97 per trial)"""

@@ -439,6 +439,89 @@ def weighted_moments(rows: torch.Tensor, logw=None, want: str = "var", n_segment
     return {k: v[0] for k, v in out.items()} if S == 1 else out
 
 
+def _weighted_rows(name: str, rows: torch.Tensor, logw, n_segments):
+    """the arguments gjx_weighted_quantiles / gjx_weighted_histogram share with weighted_moments, checked the same way
+    -> rows [n_rows][K], row stride, n_rows, K, logw, S"""
+    if rows.dim() == 1:
+        rows = rows.unsqueeze(0)
+    if rows.dim() != 2 or rows.dtype != torch.float32:
+        raise ValueError(f"{name}: rows must be f32[n_rows][K]")
+    n_rows, K = int(rows.shape[0]), int(rows.shape[1])
+    if K > 1 and rows.stride(1) != 1:
+        raise ValueError(f"{name}: the particles of a row must be contiguous (column stride 1)")
+    stride = int(rows.stride(0)) if n_rows > 1 else K
+    if stride < K:
+        raise ValueError(f"{name}: rows overlap (row stride < K)")
+    if logw is not None:
+        if logw.dtype != torch.float32 or logw.numel() != K:
+            raise ValueError(f"{name}: logw must be f32[K]")
+        logw = logw.reshape(-1)
+        if K > 1 and logw.stride(0) != 1:
+            logw = logw.contiguous()
+    S = int(n_segments)
+    if S <= 0 or K <= 0 or n_rows <= 0 or K % S:
+        raise ValueError(f"{name}: {S} segments do not divide {K} particles")
+    return rows, stride, n_rows, K, logw, S
+
+
+def weighted_quantiles(rows: torch.Tensor, logw=None, q=(0.5,), n_segments: int = 1, ws=None) -> dict:
+    """gjx_weighted_quantiles: rows f32[n_rows][K] (a view is fine as long as its column stride is 1), log-weights f32[K] (None: equal
+    weights) and levels ``q`` in [0, 1] (a number or up to 16 of them, any order) -> dict(stats f32[4] = {max, sum e, sum e^2, ESS},
+    q f32[n_rows][n_levels]): NumPy's "inverted_cdf" quantile under the self-normalised weights — always the value of a live particle;
+    NaN values sort last, dead particles (weight -inf / NaN) are left out, a collection without weight gives NaN.  ``n_segments`` > 1:
+    that many consecutive segments, each normalised on its own, and a leading segment axis on every output.  A radix select (four
+    passes over the rows, no sort, no temporary); integer weights, bit-reproducible."""
+    import math
+    levels = [float(q)] if isinstance(q, (int, float)) else [float(v) for v in q]
+    if not levels:
+        raise ValueError("weighted_quantiles: no level")
+    if len(levels) > A.QUANTILES_MAX_LEVELS:
+        raise ValueError(f"weighted_quantiles: a call takes at most {A.QUANTILES_MAX_LEVELS} levels, not {len(levels)}")
+    if any(math.isnan(v) or v < 0.0 or v > 1.0 for v in levels):
+        raise ValueError(f"weighted_quantiles: levels must be in [0, 1], not {levels}")
+    rows, stride, n_rows, K, logw, S = _weighted_rows("weighted_quantiles", rows, logw, n_segments)
+    dev, n = rows.device, len(levels)
+    need = load().gjx_weighted_quantiles_workspace_bytes(n_rows, K, S, n)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)        # the library zeroes what it needs
+    stats = torch.empty((S, 4), dtype=torch.float32, device=dev)
+    out = torch.empty((S, n_rows, n), dtype=torch.float32, device=dev)
+    check(load().gjx_weighted_quantiles(_ptr(rows), stride, n_rows, _ptr(logw), K, S, (C.c_float * n)(*levels), n, _ptr(stats), _ptr(out),
+                                        _ptr(ws), ws.numel(), _stream()), "gjx_weighted_quantiles")
+    res = {"stats": stats, "q": out}
+    return {k: v[0] for k, v in res.items()} if S == 1 else res
+
+
+def weighted_histogram(rows: torch.Tensor, logw=None, bins: int = 64, range=None, n_segments: int = 1, ws=None) -> dict:
+    """gjx_weighted_histogram: the weighted marginal of every row over ``bins`` equal bins of ``range`` = (lo, hi) -> dict(stats f32[4],
+    mass f32[n_rows][bins + 2], edges f32[bins + 1]): mass[:, 0] is the weight below lo, mass[:, 1 + b] that of bin b =
+    floor((x - lo) * (bins / (hi - lo))) in float32, mass[:, bins + 1] the weight at or above hi and of NaN values; a row sums to 1.
+    Dead particles are left out, a collection without weight gives NaN; ``n_segments`` as in weighted_quantiles."""
+    import math
+    if range is None or len(range) != 2:
+        raise ValueError("weighted_histogram: range = (lo, hi) is required")
+    lo, hi, nb = C.c_float(float(range[0])).value, C.c_float(float(range[1])).value, int(bins)      # as the library sees them
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+        raise ValueError(f"weighted_histogram: range must be finite with lo < hi, not {(lo, hi)}")
+    if nb <= 0:
+        raise ValueError(f"weighted_histogram: bins must be positive, not {nb}")
+    if nb > A.HISTOGRAM_MAX_BINS:
+        raise ValueError(f"weighted_histogram: a call takes at most {A.HISTOGRAM_MAX_BINS} bins, not {nb}")
+    rows, stride, n_rows, K, logw, S = _weighted_rows("weighted_histogram", rows, logw, n_segments)
+    dev = rows.device
+    need = load().gjx_weighted_histogram_workspace_bytes(n_rows, K, S, nb)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    stats = torch.empty((S, 4), dtype=torch.float32, device=dev)
+    mass = torch.empty((S, n_rows, nb + 2), dtype=torch.float32, device=dev)
+    check(load().gjx_weighted_histogram(_ptr(rows), stride, n_rows, _ptr(logw), K, S, lo, hi, nb, _ptr(stats), _ptr(mass),
+                                        _ptr(ws), ws.numel(), _stream()), "gjx_weighted_histogram")
+    res = {"stats": stats, "mass": mass}
+    res = {k: v[0] for k, v in res.items()} if S == 1 else res
+    res["edges"] = torch.linspace(lo, hi, nb + 1, dtype=torch.float32, device=dev)      # (on the device: no copy, no synchronisation)
+    return res
+
+
 def resample_sorted_multinomial_tiled(logw: torch.Tensor, key, N: int | None = None, anc=None, cum=None, ws=None, want_q=False):
     """gjx_resample_sorted_multinomial_tiled: log-weights -> MULTINOMIAL ancestors (sorted uniforms from exponential spacings under
     `key`, tile-scaled fixed point), non-decreasing.  -> ancestors int32[N], or (ancestors, q, e) with want_q"""

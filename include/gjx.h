@@ -926,6 +926,52 @@ enum { GJX_MOMENTS_MEAN = 0, GJX_MOMENTS_VAR = 1, GJX_MOMENTS_COV = 2 };
 size_t gjx_weighted_moments_workspace_bytes(int32_t n_rows, int64_t K, int64_t n_segments, int32_t want);
 int gjx_weighted_moments(const float* rows, int64_t row_stride, int32_t n_rows, const float* logw, int64_t K, int64_t n_segments,
                          int32_t want, float* stats, float* mean, float* second, void* workspace, size_t workspace_bytes, void* stream);
+/* Weighted quantiles and histograms of a particle collection: the median, a credible interval, the marginal of a site, the posterior
+ * probabilities of a discrete site.  The reference has no counterpart: its users write jnp.quantile on resampled particles.  rows,
+ * row_stride, logw (NULL: equal weights), K and n_segments are those of gjx_weighted_moments, so the three calls compose.
+ * Integer weights.  Per segment, M is the maximum log-weight and e_i = exp(logw_i - M) in float32 (the hardware exponential).  The
+ * weight of a particle is the INTEGER u_i = (uint64) rint(e_i 2^32) (round to nearest even), U = sum u_i (64 bits: no overflow for
+ * K / n_segments < 2^31, more is GJX_EINVAL).  A particle whose weight is -inf or NaN, or whose u_i is 0, is dead: it is selected out
+ * whatever its row value.  Every accumulation of weight in both calls is an integer addition, which is associative: the outputs are
+ * bit-reproducible however the hardware orders the atomics, and a segment's outputs are those of a call on that segment alone.
+ *   stats   f32[n_segments][4] = {M, U / 2^32, Q / 2^32, ESS = (U / 2^32)^2 / (Q / 2^32)} with Q = sum rint(e_i^2 2^32), as gjx_ess;
+ *           a segment without weight: {-inf, 0, 0, 0}
+ * Quantiles (NumPy's method="inverted_cdf", weighted).  For a level q the target is t = max(1, ceil(q U)), the product evaluated in
+ * double and t never above U.  The result is the smallest row value v among the live particles with sum of u_i over {x_i <= v} >= t:
+ * always the value of a live particle, bit for bit (up to the folding below); q = 0 the smallest live value, q = 1 the largest.
+ * Values are ordered by the key  bits ^ (sign ? 0xFFFFFFFF : 0x80000000)  of their float bits, after -0.0 has been folded onto +0.0
+ * and every NaN of a live particle onto one key above +inf (a NaN sorts last, as in np.sort; it is reported as the quiet NaN
+ * 0x7FC00000, -0.0 as +0.0).  Bits are compared, not floats: denormal values keep their order.  A segment without weight: NaN.
+ *   levels  HOST f32[n_levels], each in [0, 1]; any order, duplicates allowed; a level's result does not depend on the other levels
+ *   out     f32[n_segments][n_rows][n_levels]
+ * A most-significant-digit radix select on the keys, 8 bits per pass, 4 passes; per pass one launch that adds u_i into a histogram
+ * of the digit (in LDS, then the block's non-zero bins into the workspace with 64-bit integer atomics; one histogram per distinct
+ * prefix among the levels) and one small launch that picks each level's digit.  Plain launches on `stream`, nothing read back, no
+ * block waits for another.  Traffic: 4 passes x (4 B per particle and row for the values + 4 B per particle and row for the weights,
+ * which every row's blocks read again — from the caches for all rows but the first); no particle-sized temporary is written.
+ * Histogram.  scale = (float)n_bins / (hi - lo) in float32, once; the bin of a live particle, UNFUSED in float32:
+ *   x < lo: entry 0;   x >= hi, NaN, or b >= n_bins: entry n_bins + 1;   else entry 1 + b,  b = floorf((x - lo) * scale)
+ *   (the difference rounded to float32, then the product rounded to float32: no fused multiply-add).
+ *   mass    f32[n_segments][n_rows][n_bins + 2]: each entry (double)(sum of u_i in the bin) / (double)U rounded to float — the
+ *           integer ratio rounded once, so a row's entries sum to 1 up to those n_bins + 2 roundings; a segment without weight: NaN
+ * One histogram launch and one normalise launch: 4 B per particle and row, and the weights as above, read once.
+ * GJX_EINVAL: a NULL rows, stats, out / mass, workspace or levels; K <= 0, n_rows <= 0, row_stride < K, n_segments <= 0 or not
+ * dividing K, K / n_segments >= 2^31; n_levels <= 0, a level outside [0, 1] or NaN; n_bins <= 0, !(lo < hi) or a non-finite lo or
+ * hi.  GJX_EUNSUPPORTED: n_levels > GJX_QUANTILES_MAX_LEVELS, n_bins > GJX_HISTOGRAM_MAX_BINS.  GJX_EWORKSPACE: less than the
+ * *_workspace_bytes(...) of the same arguments (0 for arguments the call refuses).  The workspace needs no initialisation: the
+ * call zeroes what it needs on `stream`.  Nothing is launched on a refusal. */
+#define GJX_QUANTILES_MAX_LEVELS 16
+#define GJX_HISTOGRAM_MAX_BINS   4096
+size_t gjx_weighted_quantiles_workspace_bytes(int32_t n_rows, int64_t K, int64_t n_segments, int32_t n_levels);
+int gjx_weighted_quantiles(const float* rows, int64_t row_stride, int32_t n_rows, const float* logw, int64_t K, int64_t n_segments,
+                           const float* levels /* HOST f32[n_levels], each in [0, 1] */, int32_t n_levels,
+                           float* stats /* f32[S][4] as gjx_ess */, float* out /* f32[S][n_rows][n_levels] */,
+                           void* workspace, size_t workspace_bytes, void* stream);
+size_t gjx_weighted_histogram_workspace_bytes(int32_t n_rows, int64_t K, int64_t n_segments, int32_t n_bins);
+int gjx_weighted_histogram(const float* rows, int64_t row_stride, int32_t n_rows, const float* logw, int64_t K, int64_t n_segments,
+                           float lo, float hi, int32_t n_bins,
+                           float* stats, float* mass /* f32[S][n_rows][n_bins + 2] */,
+                           void* workspace, size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
