@@ -14,6 +14,7 @@ from .. import _abi as A
 from .._lib import GjxError
 from .. import config
 from ..core import Key, fold_in, split, threefry2x32
+from .smoothing import LineageSmoothing
 
 
 _warned_timeout = [False]
@@ -133,7 +134,7 @@ class LinearGaussianSSM:
         return s
 
 
-class ParticleHistory:
+class ParticleHistory(LineageSmoothing):
     """Append-only record of a filter run: the particles of every step (SoA rows) and the ancestor indices of every
     resampling.  The reference's ScanTrace keeps the whole stacked trace per particle and its resampling idiom gathers
     whole particles (scan.py:56-97; O(T^2) copies over a run); here a trajectory is reconstructed lazily by following
@@ -184,6 +185,27 @@ class ParticleHistory:
         import torch
         w = torch.softmax(self.logw.double(), dim=0)
         return (self.paths().double() * w).sum(dim=2).float()
+
+    # ---- smoothed estimates without a path gather (inference/smoothing.py); replace_parents keeps states and links consistent,
+    #      so step t's stored particles stand under w[t] with or without resample-move ----
+    def _ancestor_table(self):
+        import torch
+        if self.ancestors:
+            return torch.stack(self.ancestors)
+        return torch.empty((0, self.states[-1].shape[1]), dtype=torch.int32, device=self.states[-1].device)
+
+    def _smoothing_rows(self, t, name=None):
+        return self.states[t], t
+
+    def smoothed_moments(self, cov: bool = False) -> dict:
+        """E[x_t | y_{1:T}] and the spread about it for every step: dict(mean f32[T][dx], var f32[T][dx], ess f32[T]), or cov
+        f32[T][dx][dx] in place of var with ``cov``: one gjx_weighted_moments call per step on the stored particles under the log
+        of ``smoothing_weights()``"""
+        return self._smoothed_moments(None, cov)
+
+    def smoothed_quantiles(self, q=(0.05, 0.5, 0.95)):
+        """quantiles of x_t | y_{1:T} for every step: f32[T][dx][n_levels], one gjx_weighted_quantiles call per step"""
+        return self._smoothed_quantiles(None, q)
 
 
 class BootstrapFilter:

@@ -22,6 +22,7 @@ from .._lib import check, load
 from ..core import ChoiceMap, Key
 from ..gen import MissingAddress, ScanCombinator, _constraint_value, _value_rows
 from ..program import PackedProgram, Site, SiteList, fold_known
+from .smoothing import LineageSmoothing
 
 
 def _step_of(site) -> int:
@@ -516,7 +517,7 @@ class ScanBootstrapFilter:
         return r[:, 0] if isinstance(q, (int, float)) else r
 
 
-class ScanHistory:
+class ScanHistory(LineageSmoothing):
     """Record of a filter run over a Scan: the choices of every step (SoA rows of the step's program) and the ancestors of every
     resampling.  The reference's ScanTrace stacks the whole trace per particle and a resampling gathers whole traces
     (scan.py:56-97); here the trajectory that ends in particle i of the last step is read back lazily: i_{t-1} =
@@ -580,6 +581,32 @@ class ScanHistory:
         """E[x_t | y_{1:T}] from the reconstructed trajectories, weighted by the last step's weights: f32[T][dim]"""
         w = torch.softmax(self.logw.double(), dim=0)
         return (self.paths(name).double() * w).sum(dim=2).float()
+
+    # ---- smoothed estimates without a path gather (inference/smoothing.py) ----
+    def _ancestor_table(self):
+        return self.ancestors
+
+    def _smoothing_rows(self, t, name):
+        """the rows that hold x_t of every surviving path, and the step whose descendant weights they stand under: step t's own rows
+        under w[t]; with resample-move, for t < T-1, the moved carry in step t+1's INPUT rows at the child's index, under w[t+1] —
+        the value ``paths`` gives a trajectory at step t"""
+        if self.moved and t < len(self.programs) - 1:
+            rin = self._input_rows_of(t + 1, name)
+            if rin is None:
+                raise NotImplementedError(f"ScanHistory.paths({name!r}) with resample-move: step {t + 1} does not receive {name!r} as carry")
+            return self.rows_all[t + 1, rin[0]:rin[0] + rin[1]], t + 1
+        return self.step(t, name), t
+
+    def smoothed_moments(self, name, cov: bool = False) -> dict:
+        """E[x_t | y_{1:T}] and the spread about it for every step: dict(mean f32[T][dim], var f32[T][dim], ess f32[T]), or cov
+        f32[T][dim][dim] in place of var with ``cov``.  One gjx_weighted_moments call per step on the step's stored rows (a view)
+        under the log of ``smoothing_weights()``; ess is the effective sample size of the step's smoothing weights."""
+        return self._smoothed_moments(name, cov)
+
+    def smoothed_quantiles(self, name, q=(0.05, 0.5, 0.95)) -> torch.Tensor:
+        """quantiles of x_t | y_{1:T} for every step — the credible band of the smoothed trajectory: f32[T][dim][n_levels], one
+        gjx_weighted_quantiles call per step; every result is the value of a particle of that step that has a descendant"""
+        return self._smoothed_quantiles(name, q)
 
 
 def _name(addr):

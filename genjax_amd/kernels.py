@@ -439,6 +439,40 @@ def weighted_moments(rows: torch.Tensor, logw=None, want: str = "var", n_segment
     return {k: v[0] for k, v in out.items()} if S == 1 else out
 
 
+def weighted_moments_steps(steps, logw: torch.Tensor, want: str = "var") -> dict:
+    """gjx_weighted_moments once per step of a history, into one set of outputs: ``steps`` is a sequence of T pairs (rows f32[n_rows][K]
+    — views of one shape, column stride 1 —, the row of ``logw`` f32[n][K] they stand under) -> dict(stats f32[T][4], mean f32[T][n_rows],
+    var f32[T][n_rows] | cov f32[T][n_rows][n_rows]).  Entry t is bitwise ``weighted_moments(rows_t, logw[row_t], want)``: the same
+    library call on the same arguments; what is saved is the host's work per call (outputs and workspace are allocated once, pointers
+    are computed, nothing is sliced), which is what T small calls cost."""
+    if want not in ("var", "cov"):
+        raise ValueError(f"weighted_moments_steps: want is 'var' or 'cov', not {want!r}")
+    T = len(steps)
+    if T == 0:
+        raise ValueError("weighted_moments_steps: no step")
+    n_rows, K = int(steps[0][0].shape[0]), int(steps[0][0].shape[1])
+    if logw.dim() != 2 or logw.dtype != torch.float32 or int(logw.shape[1]) != K or not logw.is_contiguous():
+        raise ValueError("weighted_moments_steps: logw must be a contiguous f32[n][K]")
+    if want == "cov" and n_rows > A.MOMENTS_MAX_COV_ROWS:
+        raise ValueError(f"weighted_moments_steps: a covariance takes at most {A.MOMENTS_MAX_COV_ROWS} rows, not {n_rows}")
+    dev, code = logw.device, _MOMENTS_WANT[want]
+    ws = torch.empty(load().gjx_weighted_moments_workspace_bytes(n_rows, K, 1, code), dtype=torch.uint8, device=dev)
+    stats = torch.empty((T, 4), dtype=torch.float32, device=dev)
+    mean = torch.empty((T, n_rows), dtype=torch.float32, device=dev)
+    second = torch.empty((T, n_rows) + ((n_rows,) if want == "cov" else ()), dtype=torch.float32, device=dev)
+    call, st, p_ws, n_ws = load().gjx_weighted_moments, _stream(), _ptr(ws), ws.numel()
+    p_lw, p_stats, p_mean, p_second, b_second = logw.data_ptr(), stats.data_ptr(), mean.data_ptr(), second.data_ptr(), 4 * second[0].numel()
+    for t, (rows, tw) in enumerate(steps):
+        if rows.dtype != torch.float32 or tuple(rows.shape) != (n_rows, K) or (K > 1 and rows.stride(1) != 1) or rows.device != dev:
+            raise ValueError("weighted_moments_steps: every step's rows must be f32[n_rows][K] views of one shape with column stride 1")
+        stride = int(rows.stride(0)) if n_rows > 1 else K
+        if stride < K or not 0 <= int(tw) < int(logw.shape[0]):
+            raise ValueError("weighted_moments_steps: rows overlap (row stride < K), or a weight row outside logw")
+        check(call(C.c_void_p(rows.data_ptr()), stride, n_rows, C.c_void_p(p_lw + 4 * K * int(tw)), K, 1, code, C.c_void_p(p_stats + 16 * t),
+                   C.c_void_p(p_mean + 4 * n_rows * t), C.c_void_p(p_second + b_second * t), p_ws, n_ws, st), "gjx_weighted_moments")
+    return {"stats": stats, "mean": mean, want: second}
+
+
 def _weighted_rows(name: str, rows: torch.Tensor, logw, n_segments):
     """the arguments gjx_weighted_quantiles / gjx_weighted_histogram share with weighted_moments, checked the same way
     -> rows [n_rows][K], row stride, n_rows, K, logw, S"""
@@ -520,6 +554,42 @@ def weighted_histogram(rows: torch.Tensor, logw=None, bins: int = 64, range=None
     res = {k: v[0] for k, v in res.items()} if S == 1 else res
     res["edges"] = torch.linspace(lo, hi, nb + 1, dtype=torch.float32, device=dev)      # (on the device: no copy, no synchronisation)
     return res
+
+
+def lineage_weights(ancestors: torch.Tensor, logw=None, ws=None) -> dict:
+    """gjx_lineage_weights: ancestors i32[T-1][K] (the parents of every step's particles, ``ScanHistory.ancestors``; a view is fine
+    as long as its column stride is 1; shape (0, K) means T = 1) and the LAST step's log-weights f32[K] (None: equal weights)
+    -> dict(w f32[T][K], survivors i32[T], stats f32[4], n_bad i32[1]), all on the device, nothing read back.  w[t][j] is the final
+    weight of the last-step particles that descend from particle j of step t: step t's stored particles under w[t] are the smoothing
+    marginal.  survivors[t] counts the non-zero entries of w[t]; n_bad the links outside [0, K) that carried weight (their weight
+    is dropped).  Integer weights, bit-reproducible; one launch per step."""
+    if ancestors.dim() != 2 or ancestors.dtype != torch.int32:
+        raise ValueError("lineage_weights: ancestors must be i32[T-1][K]")
+    T, K = int(ancestors.shape[0]) + 1, int(ancestors.shape[1])
+    if K <= 0:
+        raise ValueError("lineage_weights: no particles")
+    if T > 1 and K > 1 and ancestors.stride(1) != 1:      # (an empty table has no strides to speak of)
+        raise ValueError("lineage_weights: the particles of a step must be contiguous (column stride 1)")
+    stride = int(ancestors.stride(0)) if T > 2 else K
+    if stride < K:
+        raise ValueError("lineage_weights: steps overlap (row stride < K)")
+    if logw is not None:
+        if logw.dtype != torch.float32 or logw.numel() != K:
+            raise ValueError("lineage_weights: logw must be f32[K]")
+        logw = logw.reshape(-1)
+        if K > 1 and logw.stride(0) != 1:
+            logw = logw.contiguous()
+    dev = ancestors.device
+    need = load().gjx_lineage_weights_workspace_bytes(T, K)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)        # the library zeroes what it needs
+    w = torch.empty((T, K), dtype=torch.float32, device=dev)
+    survivors = torch.empty(T, dtype=torch.int32, device=dev)
+    stats = torch.empty(4, dtype=torch.float32, device=dev)
+    n_bad = torch.empty(1, dtype=torch.int32, device=dev)
+    check(load().gjx_lineage_weights(_ptr(ancestors) if T > 1 else None, stride, T, K, _ptr(logw), _ptr(stats), _ptr(w), _ptr(survivors),
+                                     _ptr(n_bad), _ptr(ws), ws.numel(), _stream()), "gjx_lineage_weights")
+    return {"w": w, "survivors": survivors, "stats": stats, "n_bad": n_bad}
 
 
 def resample_sorted_multinomial_tiled(logw: torch.Tensor, key, N: int | None = None, anc=None, cum=None, ws=None, want_q=False):

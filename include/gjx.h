@@ -972,6 +972,38 @@ int gjx_weighted_histogram(const float* rows, int64_t row_stride, int32_t n_rows
                            float lo, float hi, int32_t n_bins,
                            float* stats, float* mass /* f32[S][n_rows][n_bins + 2] */,
                            void* workspace, size_t workspace_bytes, void* stream);
+/* Descendant weights of a recorded filter run: w[t][j] is the final weight of all last-step particles whose lineage passes through
+ * particle j of step t.  The smoothing marginal p(x_t | y_{1:T}) is step t's STORED particles under w[t], so gjx_weighted_moments and
+ * gjx_weighted_quantiles on a step's rows with log(w[t]) as log-weights give the smoothed mean, variance and credible band without
+ * gathering a path.  The reference has no counterpart: its traces carry whole trajectories through every resampling.
+ *   ancestors  i32[T-1][anc_stride], anc_stride >= K: ancestors[t-1][i] is the particle of step t-1 that particle i of step t
+ *              descends from (the layout of the filter's ancestors_all); may be NULL when T == 1
+ *   logw       f32[K], the log-weights of the LAST step; NULL: equal weights
+ * Integer weights, exactly those of gjx_weighted_quantiles: M = max logw, e_i = exp(logw_i - M) in float32 (the hardware exponential),
+ * u_i = (uint64) rint(e_i 2^32) (2^32 where logw is NULL; 0 for a weight of -inf or NaN), U = sum u_i; K >= 2^31 is GJX_EINVAL.
+ * Recursion:  W_{T-1}[i] = u_i,   W_{t-1}[a] = sum of W_t[i] over { i : ancestors[t-1][i] = a }.  Every addition is an integer
+ * addition (64-bit atomics), which is associative: the outputs do not depend on the order in which the hardware serves the atomics.
+ *   w          f32[T][K]: w[t][j] = (float)((double)W_t[j] / (double)U), the integer ratio rounded once (as the histogram's mass):
+ *              every row sums to 1 up to those K roundings
+ *   survivors  i32[T]: survivors[t] = #{ j : W_t[j] > 0 }, the particles of step t that still have a descendant at the end
+ *   stats      f32[4] = {M, U / 2^32, Q / 2^32, ESS} of the last step's weights, as gjx_weighted_quantiles (and gjx_ess)
+ *   n_bad      i32[1]: the links ancestors[t-1][i] outside [0, K) that carried a non-zero W_t[i].  Such an ancestor is never used as
+ *              an index (a compare stands in front of the one access); the weight it carries is dropped, so the rows of w below
+ *              the link sum to less than 1.
+ * A collection without weight (U = 0): stats {-inf, 0, 0, 0}, every w NaN, survivors all 0.  T == 1: w[0] = u / U, no scatter.
+ * One plain launch per step on `stream` (step t-1 needs step t complete), after the maximum and the conversion of the weights; no
+ * block waits for another, nothing is read back.  The launch of step t reads W_t, writes row t of w, counts the survivors (one
+ * atomic per block) and scatters into W_{t-1}: runs of equal adjacent ancestors (resampled ancestors are non-decreasing) are summed
+ * inside the wave and added once, by the head of the run; a run whose sum is 0 adds nothing.  Any ancestor order is correct.
+ * The integer arrays rotate through three u64[K] buffers: the workspace is 24 K bytes and a small constant, whatever T is.
+ * GJX_EINVAL: a NULL stats, w, survivors, n_bad or workspace; NULL ancestors or anc_stride < K with T > 1; T <= 0, K <= 0, K >= 2^31.
+ * GJX_EWORKSPACE: less than gjx_lineage_weights_workspace_bytes(T, K) (0 for arguments the call refuses).  The workspace needs no
+ * initialisation: the call zeroes what it uses on `stream`.  Nothing is launched on a refusal. */
+size_t gjx_lineage_weights_workspace_bytes(int32_t T, int64_t K);
+int gjx_lineage_weights(const int32_t* ancestors /* i32[T-1][anc_stride], may be NULL when T == 1 */, int64_t anc_stride,
+                        int32_t T, int64_t K, const float* logw /* f32[K] of the LAST step; NULL: equal weights */,
+                        float* stats /* f32[4] as gjx_ess */, float* w /* f32[T][K] */, int32_t* survivors /* i32[T] */,
+                        int32_t* n_bad /* i32[1] */, void* workspace, size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
