@@ -599,6 +599,43 @@ GJX_DEV float normal_interval_mass(float lo, float hi) {
   return normal_cdf(hi) - normal_cdf(lo);
 }
 
+// log of the standard normal's upper tail Q(z), z >= 0, in double: log(erfc) while erfc is a normal number, the asymptotic series of
+// Mills' ratio beyond (at z = 25 its sixth term is 2e-13)
+GJX_DEV double log_normal_tail_d(double z) {
+  if (z < 25.0) return log(0.5 * erfc(z * 0.70710678118654752440));
+  const double r = 1.0 / (z * z);
+  return -0.5 * z * z - log(z) - 0.91893853320467274178 + log(1.0 + r * (-1.0 + r * (3.0 + r * (-15.0 + r * (105.0 - r * 945.0)))));
+}
+// a window [lo, hi] of the standard normal that lies wholly in one tail, 2 or more units out: everything goes through the log of the
+// tail mass (tests/test_gpu_samplers.py: in float32 Phi(hi) - Phi(lo) is 0 from 13 units out, and 2 q - 1 rounds to +-1 from 5.4 — every
+// draw of [8, 10] was 8).  Double precision: the truncated normal is no hot path, and a window 1e-3 wide 5 units out is a difference
+// of two logs that agree to 4 digits.
+constexpr float kTnTailFrom = 2.0f;
+GJX_DEV bool tn_tail_window(float lo, float hi) { return lo >= kTnTailFrom || hi <= -kTnTailFrom; }
+// log(Phi(hi) - Phi(lo)) of such a window: log Q(near) + log(1 - Q(far) / Q(near))
+GJX_DEV double tn_tail_log_mass_d(double lo, double hi) {
+  const double n = lo > 0.0 ? lo : -hi, f = lo > 0.0 ? hi : -lo;
+  const double gn = log_normal_tail_d(n);
+  return gn + log(-expm1(log_normal_tail_d(f) - gn));
+}
+// the inverse CDF inside such a window, u in [0, 1): in the upper tail Q(z) = Q(lo) (1 - u (1 - rho)), rho = Q(hi) / Q(lo), solved for z on
+// the log scale: start at sqrt(lo^2 - 2 log s) (exact for a tail e^(-z^2 / 2); the true root lies just below), then Newton on the concave
+// log Q — from the right of the root it converges monotonically, three steps leave 1e-10.  The lower tail mirrors the upper.
+GJX_DEV float tn_tail_variate(float lo, float hi, float u) {
+  const bool upper = lo > 0.0f;
+  const double n = upper ? lo : -hi, f = upper ? hi : -lo;
+  const double gn = log_normal_tail_d(n), omr = -expm1(log_normal_tail_d(f) - gn);
+  const double ls = log1p(-(upper ? (double)u : 1.0 - (double)u) * omr);      // log of s = Q(z) / Q(near), s in [rho, 1]
+  const double T = gn + ls;
+  double z = sqrt(n * n - 2.0 * ls);
+  for (int it = 0; it < 3; ++it) {
+    const double g = log_normal_tail_d(z);
+    z += (g - T) * exp(0.5 * z * z + 0.91893853320467274178 + g);                // (g - T) / hazard, hazard = phi(z) / Q(z)
+  }
+  z = fmin(fmax(z, n), f);
+  return (float)(upper ? z : -z);
+}
+
 // atan(hi) - atan(lo), lo <= hi (the truncated Cauchy's interval mass): with lo hi > -1 it is atan((hi - lo) / (1 + lo hi)), which
 // has no cancellation — a window [1000, 1050] scale units out leaves 5e-5 of two values of 1.57, 2e-3 of the mass in float32
 GJX_DEV float atan_diff(float lo, float hi) {
@@ -633,6 +670,7 @@ GJX_DEV float bessel_i1_over_i0(float x) {
 // parameters a (non-categorical) kind reads, and stream elements one scalar of it may draw (host and device: the emitters use them too)
 constexpr int kGammaMaxIt = 32;
 constexpr int kGammaNDraw = 4 * kGammaMaxIt + 2;  // draw schedule: see GAMMA_NDRAW in the oracle
+constexpr float kGammaSeriesFrom = 1.0e4f;        // log_gamma_variate: the acceptance bound as a series from this shape on
 constexpr int kPoissonTries = 16;
 constexpr int kVonMisesTries = 16;
 constexpr int kind_params(int kind) {
@@ -695,8 +733,12 @@ GJX_DEV float elem_logpdf(int kind, float x, float a, float b, float c = 0.0f, f
     }
     case GJX_KUMARASWAMY: {  // a = concentration1, b = concentration0
       if (!(x > 0.0f && x < 1.0f)) return -INFINITY;
-      const float lx = fast_log(x);
-      return fast_log(a * b) + ((a - 1.0f) == 0.0f ? 0.0f : (a - 1.0f) * lx) + ((b - 1.0f) == 0.0f ? 0.0f : (b - 1.0f) * log1p_acc(-fast_exp(a * lx)));
+      // log(1 - x^a): next to x = 1 (42 % of the draws of kumaraswamy(0.05, 0.05) are the clamp value 1 - 2^-24) x^a rounds to 1 and the
+      // log to -inf; there 1 - x^a = -expm1(a log x) with log x from log1p(x - 1) (x - 1 is exact)
+      const float lx = x > 0.5f ? log1p_acc(x - 1.0f) : fast_log(x);
+      const float al = a * lx;
+      const float l1 = al > -0.69314718f ? fast_log(one_minus_exp(al)) : log1p_acc(-fast_exp(al));
+      return fast_log(a * b) + ((a - 1.0f) == 0.0f ? 0.0f : (a - 1.0f) * lx) + ((b - 1.0f) == 0.0f ? 0.0f : (b - 1.0f) * l1);
     }
     case GJX_MOYAL: {  // a = loc, b = scale
       const float z = (x - a) * fast_rcp(b);
@@ -714,7 +756,8 @@ GJX_DEV float elem_logpdf(int kind, float x, float a, float b, float c = 0.0f, f
     case GJX_TRUNCATED_NORMAL: {  // a = loc, b = scale, c = low, d = high
       if (x < c || x > d) return -INFINITY;
       const float rs = fast_rcp(b);
-      return normal_logpdf(x, a, b) - fast_log(normal_interval_mass((c - a) * rs, (d - a) * rs));
+      const float lo = (c - a) * rs, hi = (d - a) * rs;
+      return normal_logpdf(x, a, b) - (tn_tail_window(lo, hi) ? (float)tn_tail_log_mass_d(lo, hi) : fast_log(normal_interval_mass(lo, hi)));
     }
     case GJX_POISSON:
       if (x < 0.0f || x != floorf(x)) return -INFINITY;
@@ -800,14 +843,24 @@ GJX_DEV float elem_logpdf(int kind, float x, float a, float b, float c = 0.0f, f
 
 // ---- samplers ----------------------------------------------------------------------------------
 GJX_DEV int draws_per_elem(int kind) { return kind_draws(kind); }
+// a draw of a kind with an OPEN support never sits on its edge (TFP's convention for gamma): float32 underflow would put an atom at 0
+// (36 % of gamma(0.01)) or 1 whose own score is +inf or NaN
+constexpr float kOneMinus = 0.99999994f;      // 1 - 2^-24
+// the uniform behind an inverse CDF of the form log(u): u = 0 (one draw in 2^23) stands for the cell [0, 2^-23) and takes its middle, 2^-24, so the
+// draw is -log(2^-24) = 16.6 units out where the cell's mass belongs; with the smallest float32 in its place it was 87.3 units out — an
+// exponential(1) draw of 87.3, a student-t(1) draw of 1e36 (beyond the 1 - 1e-12 quantile).  Every other u is unchanged.
+constexpr float kHalfStep = 5.9604645e-8f;      // 2^-24
+GJX_DEV float unit_open(uint32_t bits) { return fmaxf(bits_to_unit(bits), kHalfStep); }
+GJX_DEV float clamp_positive(float x) { return fmaxf(x, kTiny); }
+GJX_DEV float clamp_unit(float x) { return fminf(fmaxf(x, kTiny), kOneMinus); }
 
 // Marsaglia & Tsang (2000), log space, fixed draw budget (same element schedule as the oracle)
 template <int RNG, class BS>
 GJX_DEV float log_gamma_variate(BS& bs, uint32_t base, float a) {
   float boost = 0.0f, aa = a;
   if (a < 1.0f) {
-    const float u = uniform_from_bits(bs.get(base + 4 * kGammaMaxIt), kTiny, 1.0f);
-    boost = safe_log(u) / a;
+    const float u = unit_open(bs.get(base + 4 * kGammaMaxIt));
+    boost = fast_log(u) / a;
     aa = a + 1.0f;
   }
   const float d = aa - (1.0f / 3.0f);
@@ -816,6 +869,18 @@ GJX_DEV float log_gamma_variate(BS& bs, uint32_t base, float a) {
   for (int t = 0; t < kGammaMaxIt; ++t) {
     const float x = stream_normal<RNG>(bs, base + 4 * t);
     const float u = uniform_from_bits(bs.get(base + 4 * t + 2), kTiny, 1.0f);
+    if (aa >= kGammaSeriesFrom) {
+      // the log acceptance bound x^2 / 2 + d (1 - v^3 + 3 log v), v = 1 + t, t = c x, is d (-3/4 t^4 + 3/5 t^5 - ...) (c^2 = 1 / (9 d): the t^2 and
+      // t^3 terms cancel identically).  In float32 the closed form subtracts terms of size d to leave 1e-6: from shape 1e4 (|t| < 0.02) the
+      // series itself — gamma(1e6) sat at z = 5.4 at one edge, chi(2e6) at 6.9 (tests/test_gpu_samplers.py)
+      const float t = c * x;
+      const float rhs = d * (t * t) * (t * t) * (-0.75f + t * (0.6f + t * (-0.5f + t * (0.428571429f - 0.375f * t))));
+      if (safe_log(u) < rhs) {
+        res = fast_log(d) + 3.0f * log1p_acc(t);
+        break;
+      }
+      continue;
+    }
     float v = fmaf(c, x, 1.0f);
     if (v <= 0.0f) continue;
     const float lv = 3.0f * fast_log(v);
@@ -830,6 +895,15 @@ GJX_DEV float log_gamma_variate(BS& bs, uint32_t base, float a) {
 
 // Poisson: inversion by sequential search on one uniform for rate < 10, Hörmann's transformed rejection (PTRS,
 // 1993) with a fixed budget of tries above (same element schedule as the oracle: try t uses elements c+2+2t, +1)
+// log of the Poisson mass, -lam + k log lam - lgamma(k + 1).  From rate 1000 on in the deviance form k (log1p(d) - d) - 1/2 log(2 pi k) - S(k),
+// d = (lam - k) / k, S = Stirling's correction (gamma_kernel_big's form): the closed form subtracts terms of size k log lam (1.6e8 at rate
+// 1e7, where float32 moves in steps of 16) to leave O(log k) — the CDF was off by 0.014 at rate 1e7.  Below, the form it always was.
+constexpr float kPoissonDevianceFrom = 1000.0f;
+GJX_DEV float poisson_log_mass(float k, float lam, float loglam) {
+  if (!(lam >= kPoissonDevianceFrom && k >= 8.0f)) return -lam + k * loglam - lgammaf(k + 1.0f);
+  const float d = (lam - k) * fast_rcp(k);
+  return fmaf(k, log1p_minus(d, [&]() { return loglam - fast_log(k); }), -0.5f * fast_log(6.28318531f * k) - stirling_corr(k));
+}
 template <int RNG, class BS>
 GJX_DEV float poisson_variate(BS& bs, uint32_t c, float lam) {
   if (lam < 10.0f) {
@@ -853,7 +927,7 @@ GJX_DEV float poisson_variate(BS& bs, uint32_t c, float lam) {
     const float k = floorf((2.0f * a / us + b) * U + lam + 0.43f);
     if (us >= 0.07f && V <= vr) return k;
     if (k < 0.0f || (us < 0.013f && V > us)) continue;
-    if (fast_log(V) + fast_log(inv_alpha) - fast_log(a / (us * us) + b) <= -lam + k * loglam - lgammaf(k + 1.0f)) return k;
+    if (fast_log(V) + fast_log(inv_alpha) - fast_log(a / (us * us) + b) <= poisson_log_mass(k, lam, loglam)) return k;
   }
   return floorf(lam);
 }
@@ -870,8 +944,21 @@ GJX_DEV float elem_sample(int kind, BS& bs, uint32_t c, float a, float b, float 
     }
     case GJX_TRUNCATED_CAUCHY: {  // inverse CDF on the arctangent scale
       const float rs = fast_rcp(b);
-      const float lo = atanf((p3 - a) * rs), hi = atanf((p4 - a) * rs);
-      return fminf(fmaxf(fmaf(b, tanf(fmaf(bits_to_unit(bs.get(c)), hi - lo, lo)), a), p3), p4);
+      const float zl = (p3 - a) * rs, zh = (p4 - a) * rs, u = bits_to_unit(bs.get(c));
+      float z;
+      if (zl >= 1.0f || zh <= -1.0f) {
+        // a window wholly beyond one scale unit: atan z = pi / 2 - atan(1 / z), so the angle is uniform on the RECIPROCAL scale, where float32
+        // resolves it (atan(1e6) and atan(1.25e6) are two float32 steps apart: K-S distance 0.3); its width from atan's difference formula
+        const bool up = zl > 0.0f;
+        const float n = up ? zl : -zh, f = up ? zh : -zl;
+        const float phi = fmaf(-(up ? u : 1.0f - u), atanf((f - n) / fmaf(n, f, 1.0f)), atanf(1.0f / n));
+        z = 1.0f / tanf(phi);
+        z = up ? z : -z;
+      } else {
+        const float lo = atanf(zl), hi = atanf(zh);
+        z = tanf(fmaf(u, hi - lo, lo));
+      }
+      return fminf(fmaxf(fmaf(b, z, a), p3), p4);
     }
     case GJX_NEGATIVE_BINOMIAL: {  // a gamma(r, rate e^-l) mixture of Poissons: rate = exp(log gamma(r, 1) + l)
       const float lg = log_gamma_variate<RNG>(bs, c, a);
@@ -882,33 +969,41 @@ GJX_DEV float elem_sample(int kind, BS& bs, uint32_t c, float a, float b, float 
       const double kd = (double)b;
       const double tau = 1.0 + sqrt(1.0 + 4.0 * kd * kd);
       const double rho = (tau - sqrt(2.0 * tau)) / (2.0 * kd);
-      const float r = (float)((1.0 + rho * rho) / (2.0 * rho));
-      float f = 1.0f;
+      // r - 1 = (1 - rho)^2 / (2 rho) from the double computation, 1 - z = 2 sin^2(pi u / 2), 1 + z = 2 cos^2(pi u / 2): then
+      // 1 - f = (r - 1)(1 - z) / (r + z) and 1 + f = (r + 1)(1 + z) / (r + z) carry no cancellation, kappa (r - f) = kappa ((r - 1) + (1 - f)), and
+      // the angle is 2 atan2(sqrt(1 - f), sqrt(1 + f)).  (r - f in float32 is a difference of two numbers next to 1 once kappa is large:
+      // K-S distance 0.1 at kappa = 1e6; acos(f) has steps of 3e-4 near f = -1.  tests/test_gpu_samplers.py)
+      const float r = (float)((1.0 + rho * rho) / (2.0 * rho)), rm1 = (float)((1.0 - rho) * (1.0 - rho) / (2.0 * rho));
+      float sh = 0.0f, ch = 1.0f;
       for (int t = 0; t < kVonMisesTries; ++t) {
-        const float z = cosf(kPi * bits_to_unit(bs.get(c + 2 * t)));
+        const float hu = 0.5f * kPi * bits_to_unit(bs.get(c + 2 * t));
         const float u2 = uniform_from_bits(bs.get(c + 2 * t + 1), kTiny, 1.0f);
-        f = fmaf(r, z, 1.0f) * fast_rcp(r + z);
-        const float cc = b * (r - f);
+        sh = sinf(hu);
+        ch = cosf(hu);
+        const float omz = 2.0f * sh * sh;                                                  // 1 - z
+        const float cc = b * fmaf(rm1 * omz, fast_rcp(fmaf(2.0f * ch, ch, rm1)), rm1);     // r + z = (r - 1) + (1 + z)
         if (u2 < cc * (2.0f - cc) || fast_log(cc * fast_rcp(u2)) + 1.0f - cc >= 0.0f) break;
       }
-      const float th = acosf(fminf(fmaxf(f, -1.0f), 1.0f));
+      const float th = 2.0f * atan2f(sqrtf(rm1) * sh, sqrtf(r + 1.0f) * ch);
       return a + (bits_to_unit(bs.get(c + 2 * kVonMisesTries)) < 0.5f ? -th : th);
     }
-    case GJX_CHI: return fast_exp(0.5f * (kLn2 + log_gamma_variate<RNG>(bs, c, 0.5f * a)));
+    case GJX_CHI: return clamp_positive(fast_exp(0.5f * (kLn2 + log_gamma_variate<RNG>(bs, c, 0.5f * a))));
     case GJX_EXP_GAMMA: return log_gamma_variate<RNG>(bs, c, a) - fast_log(b);
     case GJX_EXP_INVERSE_GAMMA: return fast_log(b) - log_gamma_variate<RNG>(bs, c, a);
     case GJX_KUMARASWAMY: {  // x = (1 - (1 - u)^(1 / b))^(1 / a)
       const float t = log1p_acc(-bits_to_unit(bs.get(c))) * fast_rcp(b);
-      return fast_exp(safe_log(-expm1f(t)) * fast_rcp(a));
+      return clamp_unit(fast_exp(safe_log(-expm1f(t)) * fast_rcp(a)));
     }
     case GJX_MOYAL: {  // -log of a chi2(1) variate: loc - scale log(n^2)
       const float n = stream_normal<RNG>(bs, c);
-      return fmaf(-2.0f * b, safe_log(fabsf(n)), a);
+      return fmaf(-2.0f * b, fast_log(fmaxf(fabsf(n), kHalfStep)), a);      // (a FLAT normal is exactly 0 once in 2^23 draws: -log 0)
     }
     case GJX_DOUBLESIDED_MAXWELL: {  // a random sign times the root of a chi2(3) variate
       const float sgn = bits_to_unit(bs.get(c)) < 0.5f ? -1.0f : 1.0f;
       const float r = fast_exp(0.5f * (kLn2 + log_gamma_variate<RNG>(bs, c + 2, 1.5f)));
-      return fmaf(b * sgn, r, a);
+      const float x = fmaf(b * sgn, r, a);
+      // the density is 0 AT loc: a draw that rounds onto it (scale below loc's float32 step) takes the neighbour on its own side
+      return x != a ? x : nextafterf(a, sgn * INFINITY);
     }
     case GJX_INVERSE_GAUSSIAN: {  // Michael, Schucany & Haas (1976): a = mean, b = concentration
       const float n = stream_normal<RNG>(bs, c);
@@ -924,23 +1019,25 @@ GJX_DEV float elem_sample(int kind, BS& bs, uint32_t c, float a, float b, float 
       const float lo = (p3 - a) * rs, hi = (p4 - a) * rs;
       const float u = bits_to_unit(bs.get(c));
       float z;
-      if (lo > 0.0f) {
-        const float q = fmaf(-u, normal_cdf(-lo) - normal_cdf(-hi), normal_cdf(-lo));   // upper-tail mass
-        z = -kSqrt2 * erfinv_f32(fmaf(2.0f, q, -1.0f));
+      if (tn_tail_window(lo, hi)) {
+        z = tn_tail_variate(lo, hi, u);
       } else {
-        const float q = fmaf(u, normal_cdf(hi) - normal_cdf(lo), normal_cdf(lo));
-        z = kSqrt2 * erfinv_f32(fmaf(2.0f, q, -1.0f));
+        // every other window: 2 q - 1 = erf(lo / sqrt 2) + u (erf(hi / sqrt 2) - erf(lo / sqrt 2)) straight from erf, which keeps its RELATIVE precision
+        // around 0 — Phi(hi) - Phi(lo) of the window [-1e-3, 1e-3] is a difference of two numbers next to 1/2, and erfc left 1e-3 of it
+        // (tests/test_gpu_samplers.py: CDF off by 9.8e-4, z 10.9; the CPU oracle's libm passed)
+        const float el = erff(lo * 0.70710678f), eh = erff(hi * 0.70710678f);
+        z = kSqrt2 * erfinv_f32(fmaf(u, eh - el, el));
       }
       return fminf(fmaxf(fmaf(b, z, a), p3), p4);
     }
     case GJX_POISSON: return poisson_variate<RNG>(bs, c, a);
-    case GJX_GEOMETRIC: return floorf(safe_log(uniform_from_bits(bs.get(c), kTiny, 1.0f)) / log1p_acc(-a));
-    case GJX_GUMBEL: return a - b * safe_log(-safe_log(uniform_from_bits(bs.get(c), kTiny, 1.0f)));
+    case GJX_GEOMETRIC: return floorf(fast_log(unit_open(bs.get(c))) / log1p_acc(-a));
+    case GJX_GUMBEL: return a - b * fast_log(-fast_log(unit_open(bs.get(c))));
     case GJX_HALF_CAUCHY: return fmaf(b, tanf(0.5f * kPi * bits_to_unit(bs.get(c))), a);
-    case GJX_INVERSE_GAMMA: return b * fast_exp(-log_gamma_variate<RNG>(bs, c, a));
-    case GJX_WEIBULL: return b * fast_exp(safe_log(-log1p_acc(-bits_to_unit(bs.get(c)))) / a);
-    case GJX_LOGIT_NORMAL: return sigmoid(fmaf(b, stream_normal<RNG>(bs, c), a));
-    case GJX_CHI2: return 2.0f * fast_exp(log_gamma_variate<RNG>(bs, c, 0.5f * a));
+    case GJX_INVERSE_GAMMA: return clamp_positive(b * fast_exp(-log_gamma_variate<RNG>(bs, c, a)));
+    case GJX_WEIBULL: return clamp_positive(b * fast_exp(safe_log(-log1p_acc(-bits_to_unit(bs.get(c)))) / a));
+    case GJX_LOGIT_NORMAL: return clamp_unit(sigmoid(fmaf(b, stream_normal<RNG>(bs, c), a)));
+    case GJX_CHI2: return clamp_positive(2.0f * fast_exp(log_gamma_variate<RNG>(bs, c, 0.5f * a)));
     case GJX_NORMAL:
     case GJX_MVNORMAL_DIAG: return fmaf(b, stream_normal<RNG>(bs, c), a);
     case GJX_FLIP: return bits_to_unit(bs.get(c)) < a ? 1.0f : 0.0f;
@@ -948,10 +1045,10 @@ GJX_DEV float elem_sample(int kind, BS& bs, uint32_t c, float a, float b, float 
     case GJX_BETA: {
       const float g1 = log_gamma_variate<RNG>(bs, c, a);
       const float g2 = log_gamma_variate<RNG>(bs, c + kGammaNDraw, b);
-      return sigmoid(g1 - g2);
+      return clamp_unit(sigmoid(g1 - g2));
     }
     case GJX_UNIFORM: return fmaf(b - a, bits_to_unit(bs.get(c)), a);
-    case GJX_EXPONENTIAL: return -safe_log(uniform_from_bits(bs.get(c), kTiny, 1.0f)) / a;
+    case GJX_EXPONENTIAL: return -fast_log(unit_open(bs.get(c))) / a;
     case GJX_HALF_NORMAL: return fabsf(stream_normal<RNG>(bs, c)) * a;
     case GJX_LAPLACE: {
       const float u = uniform_from_bits(bs.get(c), kNeg1PlusUlp, 1.0f);
@@ -960,7 +1057,7 @@ GJX_DEV float elem_sample(int kind, BS& bs, uint32_t c, float a, float b, float 
     }
     case GJX_LOG_NORMAL: return fast_exp(fmaf(b, stream_normal<RNG>(bs, c), a));
     case GJX_CAUCHY: return fmaf(b, tanf(kPi * (bits_to_unit(bs.get(c)) - 0.5f)), a);
-    case GJX_GAMMA: return fast_exp(log_gamma_variate<RNG>(bs, c, a)) / b;
+    case GJX_GAMMA: return clamp_positive(fast_exp(log_gamma_variate<RNG>(bs, c, a)) / b);
     default: return __builtin_nanf("");
   }
 }

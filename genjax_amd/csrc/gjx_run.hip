@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void k_run_generic(RunArgs a) {
         float se = 0.0f;
         for (int d = 0; d < n; ++d) se += fast_exp(get(d) - mx);
         const float lse = mx + fast_log(se);
-        for (int d = 0; d < n; ++d) put(d, fast_exp(get(d) - lse));
+        for (int d = 0; d < n; ++d) put(d, clamp_unit(fast_exp(get(d) - lse)));      // (no component ON the simplex's edge: its score would be +-inf)
       }
       float sa = 0.0f;
       for (int d = 0; d < n; ++d) {

@@ -197,6 +197,16 @@ float gjxo_erfinv(float x) { return erfinv_f32(x); }
 
 #define NEG1_PLUS_ULP (-0.99999994f) /* nextafter(-1, 0) */
 #define F32_TINY 1.17549435e-38f
+#define F32_ONE_MINUS 0.99999994f /* 1 - 2^-24 */
+/* a draw of a kind with an OPEN support never sits on its edge (TFP's convention for gamma): float32 underflow would put an atom at
+ * 0 (36 % of gamma(0.01)) or 1 whose own score is +inf or NaN */
+/* the uniform behind an inverse CDF of the form log(u): u = 0 (one draw in 2^23) stands for the cell [0, 2^-23) and takes its middle, 2^-24, so
+ * the draw is -log(2^-24) = 16.6 units out where the cell's mass belongs; with the smallest float32 in its place it was 87.3 units out — an
+ * exponential(1) draw of 87.3, a student-t(1) draw of 1e36 (tests/test_samplers_cpu.py: beyond the 1 - 1e-12 quantile).  Every other u is unchanged. */
+#define F32_HALF_STEP 5.9604645e-8f /* 2^-24 */
+static inline float unit_open(uint32_t bits) { float f = bits_to_unit(bits); return f > F32_HALF_STEP ? f : F32_HALF_STEP; }
+static inline float clamp_positive(float x) { return x < F32_TINY ? F32_TINY : x; }
+static inline float clamp_unit(float x) { return x < F32_TINY ? F32_TINY : (x > F32_ONE_MINUS ? F32_ONE_MINUS : x); }
 #define SQRT2_F 1.41421356f
 #define HALF_LOG_2PI 0.918938533f
 #define LOG_PI 1.14472989f
@@ -234,6 +244,7 @@ float gjxo_unit_from_bits(uint32_t bits) { return bits_to_unit(bits); }
 #define VON_MISES_TRIES 16
 #define GAMMA_MAXIT 32
 #define GAMMA_NDRAW (4 * GAMMA_MAXIT + 2)
+#define GAMMA_SERIES_FROM 1.0e4f
 /* draw schedule of one gamma variate (element indices relative to `base`): iteration t takes its normal
  * from element 4t and its uniform from element 4t+2 (a FLAT normal consumes the element pair (4t, 4t+1));
  * the a < 1 boost uniform is element 4*MAXIT. */
@@ -241,7 +252,7 @@ static float log_gamma_variate(const ostream* sk, uint32_t base, float a) {
   float boost = 0.0f;
   float aa = a;
   if (a < 1.0f) {
-    float u = uniform_from_bits(elem_bits(sk, base + 4 * GAMMA_MAXIT), F32_TINY, 1.0f);
+    float u = unit_open(elem_bits(sk, base + 4 * GAMMA_MAXIT));
     boost = logf(u) / a;
     aa = a + 1.0f;
   }
@@ -251,6 +262,19 @@ static float log_gamma_variate(const ostream* sk, uint32_t base, float a) {
   for (int t = 0; t < GAMMA_MAXIT; ++t) {
     float x = stream_normal(sk, base + 4 * t);
     float u = uniform_from_bits(elem_bits(sk, base + 4 * t + 2), F32_TINY, 1.0f);
+    if (aa >= GAMMA_SERIES_FROM) {
+      /* the log acceptance bound x^2 / 2 + d (1 - v^3 + 3 log v), v = 1 + t, t = c x, is d (-3/4 t^4 + 3/5 t^5 - ...) (c^2 = 1 / (9 d): the t^2 and
+       * t^3 terms cancel identically).  In float32 the closed form subtracts terms of size d to leave 1e-6: from shape 1e4 (|t| < 0.02) the
+       * series itself — gamma(1e6) sat at z = 5.4 at one edge, chi(2e6) at 6.9 (tests/test_samplers_cpu.py) */
+      const float t = c * x;
+      const float rhs = d * (t * t) * (t * t) * (-0.75f + t * (0.6f + t * (-0.5f + t * (0.428571429f - 0.375f * t))));
+      decide(logf(u), rhs);
+      if (logf(u) < rhs) {
+        res = logf(d) + 3.0f * log1pf(t);
+        break;
+      }
+      continue;
+    }
     float v = 1.0f + c * x;
     decide(v, 0.0f);
     if (v <= 0.0f) continue;
@@ -423,6 +447,40 @@ static double normal_interval_mass_d(double lo, double hi) {
   if (lo > 0.0) return 0.5 * (erfc(lo * r) - erfc(hi * r));
   return 0.5 * (erfc(-hi * r) - erfc(-lo * r));
 }
+/* log of the standard normal's upper tail Q(z), z >= 0, in double: log(erfc) while erfc is a normal number, the asymptotic series
+ * of Mills' ratio beyond (at z = 25 its sixth term is 2e-13) */
+static double log_normal_tail_d(double z) {
+  if (z < 25.0) return log(0.5 * erfc(z * 0.70710678118654752440));
+  const double r = 1.0 / (z * z);
+  return -0.5 * z * z - log(z) - 0.91893853320467274178 + log(1.0 + r * (-1.0 + r * (3.0 + r * (-15.0 + r * (105.0 - r * 945.0)))));
+}
+/* a window [lo, hi] of the standard normal that lies wholly in one tail, 2 or more units out: everything goes through the log of
+ * the tail mass (tests/test_samplers_cpu.py: in float32 Phi(hi) - Phi(lo) is 0 from 13 units out, and 2 q - 1 rounds to +-1 from 5.4) */
+#define TN_TAIL_FROM 2.0f
+static int tn_tail_window(float lo, float hi) { return lo >= TN_TAIL_FROM || hi <= -TN_TAIL_FROM; }
+/* log(Phi(hi) - Phi(lo)) of such a window: log Q(near) + log(1 - Q(far) / Q(near)) */
+static double tn_tail_log_mass_d(double lo, double hi) {
+  const double n = lo > 0.0 ? lo : -hi, f = lo > 0.0 ? hi : -lo;
+  const double gn = log_normal_tail_d(n);
+  return gn + log(-expm1(log_normal_tail_d(f) - gn));
+}
+/* the inverse CDF inside such a window, u in [0, 1): in the upper tail Q(z) = Q(lo) (1 - u (1 - rho)), rho = Q(hi) / Q(lo), solved for z on
+ * the log scale: start at sqrt(lo^2 - 2 log s) (exact for a tail e^(-z^2 / 2); the true root lies just below), then Newton on the concave
+ * log Q — from the right of the root it converges monotonically, three steps leave 1e-10.  The lower tail mirrors the upper. */
+static float tn_tail_variate(float lo, float hi, float u) {
+  const int upper = lo > 0.0f;
+  const double n = upper ? lo : -hi, f = upper ? hi : -lo;
+  const double gn = log_normal_tail_d(n), omr = -expm1(log_normal_tail_d(f) - gn);
+  const double ls = log1p(-(upper ? (double)u : 1.0 - (double)u) * omr);      /* log of s = Q(z) / Q(near), s in [rho, 1] */
+  const double T = gn + ls;
+  double z = sqrt(n * n - 2.0 * ls);
+  for (int it = 0; it < 3; ++it) {
+    const double g = log_normal_tail_d(z);
+    z += (g - T) * exp(0.5 * z * z + 0.91893853320467274178 + g);                /* (g - T) / hazard, hazard = phi(z) / Q(z) */
+  }
+  z = z < n ? n : (z > f ? f : z);
+  return (float)(upper ? z : -z);
+}
 static int params_of(int kind) {
   return (kind == GJX_TRUNCATED_NORMAL || kind == GJX_TRUNCATED_CAUCHY) ? 4 : ((kind == GJX_STUDENT_T || kind == GJX_HALF_STUDENT_T) ? 3 : 2);
 }
@@ -502,7 +560,9 @@ static float elem_logpdf4(int kind, float xf, float af, float bf, float cf, floa
     case GJX_TRUNCATED_NORMAL: { /* tfd.TruncatedNormal(loc=a, scale=b, low=c, high=d) */
       if (x < c || x > d) return -INFINITY;
       double z = (x - a) / b;
-      return (float)(-0.5 * z * z - ((double)HALF_LOG_2PI + log(b)) - log(normal_interval_mass_d((c - a) / b, (d - a) / b)));
+      const double lo = (c - a) / b, hi = (d - a) / b;
+      const double lm = tn_tail_window((float)lo, (float)hi) ? tn_tail_log_mass_d(lo, hi) : log(normal_interval_mass_d(lo, hi));
+      return (float)(-0.5 * z * z - ((double)HALF_LOG_2PI + log(b)) - lm);
     }
     case GJX_POISSON: /* tfd.Poisson(rate=a) */
       return (x < 0.0 || x != floor(x)) ? -INFINITY : (float)(xlogy_d(x, a) - a - lgamma(x + 1.0));
@@ -600,6 +660,16 @@ static int draws_per_elem(int kind) {
 
 /* Poisson(lam): inversion by sequential search on one uniform below 10; Hormann's PTRS (1993) with a fixed
  * budget of tries above.  Element schedule: c for the inversion uniform, c+2+2t / c+3+2t for try t. */
+/* log of the Poisson mass, -lam + k log lam - lgamma(k + 1).  From rate 1000 on in the deviance form k (log1p(d) - d) - 1/2 log(2 pi k) - S(k),
+ * d = (lam - k) / k, S = Stirling's correction: the closed form subtracts terms of size k log lam (1.6e8 at rate 1e7, where float32 moves in
+ * steps of 16) to leave O(log k); tests/test_samplers_cpu.py: CDF off by 0.014 at rate 1e7.  Below, the form it always was. */
+#define POISSON_DEVIANCE_FROM 1000.0f
+static float poisson_log_mass(float k, float lam, float loglam) {
+  if (!(lam >= POISSON_DEVIANCE_FROM && k >= 8.0f)) return -lam + k * loglam - lgammaf(k + 1.0f);
+  const float d = (lam - k) / k, r = 1.0f / k;
+  const float l1m = fabsf(d) < 0.25f ? (float)(log1p((double)d) - (double)d) : log1pf(d) - d;
+  return k * l1m - 0.5f * logf(6.28318531f * k) - r * (0.0833333333f - r * r * (2.7777778e-3f - r * r * 7.9365079e-4f));
+}
 static float poisson_variate(const ostream* sk, uint32_t c, float lam) {
   if (lam < 10.0f) {
     float u = bits_to_unit(elem_bits(sk, c));
@@ -627,8 +697,9 @@ static float poisson_variate(const ostream* sk, uint32_t c, float lam) {
     if (us >= 0.07f && V <= vr) return k;
     decide(us, 0.013f); decide(V, us);
     if (k < 0.0f || (us < 0.013f && V > us)) continue;
-    decide(logf(V) + logf(inv_alpha) - logf(a / (us * us) + b), -lam + k * loglam - lgammaf(k + 1.0f));
-    if (logf(V) + logf(inv_alpha) - logf(a / (us * us) + b) <= -lam + k * loglam - lgammaf(k + 1.0f)) return k;
+    const float lpk = poisson_log_mass(k, lam, loglam);
+    decide(logf(V) + logf(inv_alpha) - logf(a / (us * us) + b), lpk);
+    if (logf(V) + logf(inv_alpha) - logf(a / (us * us) + b) <= lpk) return k;
   }
   return floorf(lam);
 }
@@ -643,8 +714,20 @@ static float elem_sample4(int kind, const ostream* sk, uint32_t c, float a, floa
       return b + (kind == GJX_HALF_STUDENT_T ? fabsf(t) : t);
     }
     case GJX_TRUNCATED_CAUCHY: { /* inverse CDF on the arctangent scale */
-      float lo = atanf((p3 - a) / b), hi = atanf((p4 - a) / b);
-      float x = a + b * tanf(lo + bits_to_unit(elem_bits(sk, c)) * (hi - lo));
+      const float zl = (p3 - a) / b, zh = (p4 - a) / b, u = bits_to_unit(elem_bits(sk, c));
+      float x;
+      if (zl >= 1.0f || zh <= -1.0f) {
+        /* a window wholly beyond one scale unit: atan z = pi / 2 - atan(1 / z), so the angle is uniform on the RECIPROCAL scale, where float32
+         * resolves it (atan(1e6) and atan(1.25e6) are two float32 steps apart: K-S distance 0.3); its width from atan's difference formula */
+        const int up = zl > 0.0f;
+        const float n = up ? zl : -zh, f = up ? zh : -zl;
+        const float phi = atanf(1.0f / n) - (up ? u : 1.0f - u) * atanf((f - n) / (n * f + 1.0f));
+        const float z = 1.0f / tanf(phi);
+        x = a + b * (up ? z : -z);
+      } else {
+        float lo = atanf(zl), hi = atanf(zh);
+        x = a + b * tanf(lo + u * (hi - lo));
+      }
       return x < p3 ? p3 : (x > p4 ? p4 : x);
     }
     case GJX_NEGATIVE_BINOMIAL: { /* a gamma(r, rate e^-l) mixture of Poissons */
@@ -654,33 +737,39 @@ static float elem_sample4(int kind, const ostream* sk, uint32_t c, float a, floa
     case GJX_VON_MISES: { /* Best & Fisher (1979), fixed budget of tries (elements 2 t, 2 t + 1; the sign: the last one) */
       if (b < 1e-6f) return a + 3.14159265f * (2.0f * bits_to_unit(elem_bits(sk, c)) - 1.0f);
       double kd = b, tau = 1.0 + sqrt(1.0 + 4.0 * kd * kd), rho = (tau - sqrt(2.0 * tau)) / (2.0 * kd);
-      float r = (float)((1.0 + rho * rho) / (2.0 * rho));
-      float f = 1.0f;
+      /* r - 1 = (1 - rho)^2 / (2 rho) from the double computation, 1 - z = 2 sin^2(pi u / 2), 1 + z = 2 cos^2(pi u / 2): then
+       * 1 - f = (r - 1)(1 - z) / (r + z) and 1 + f = (r + 1)(1 + z) / (r + z) carry no cancellation, kappa (r - f) = kappa ((r - 1) + (1 - f)), and
+       * the angle is 2 atan2(sqrt(1 - f), sqrt(1 + f)).  (r - f in float32 is a difference of two numbers next to 1 once kappa is large:
+       * K-S distance 0.1 at kappa = 1e6; acos(f) has steps of 3e-4 near f = -1.  tests/test_samplers_cpu.py) */
+      float r = (float)((1.0 + rho * rho) / (2.0 * rho)), rm1 = (float)((1.0 - rho) * (1.0 - rho) / (2.0 * rho));
+      float sh = 0.0f, ch = 1.0f;
       for (int t = 0; t < VON_MISES_TRIES; ++t) {
-        float z = cosf(3.14159265f * bits_to_unit(elem_bits(sk, c + 2 * t)));
+        const float hu = 0.5f * 3.14159265f * bits_to_unit(elem_bits(sk, c + 2 * t));
         float u2 = uniform_from_bits(elem_bits(sk, c + 2 * t + 1), F32_TINY, 1.0f);
-        f = (r * z + 1.0f) / (r + z);
-        float cc = b * (r - f);
+        sh = sinf(hu); ch = cosf(hu);
+        const float omz = 2.0f * sh * sh;                       /* 1 - z */
+        float cc = b * (rm1 + rm1 * omz / (rm1 + 2.0f * ch * ch));     /* r + z = (r - 1) + (1 + z) */
         decide(u2, cc * (2.0f - cc));
         if (u2 < cc * (2.0f - cc)) break;
         decide(logf(cc / u2) + 1.0f - cc, 0.0f);
         if (logf(cc / u2) + 1.0f - cc >= 0.0f) break;
       }
-      float th = acosf(f < -1.0f ? -1.0f : (f > 1.0f ? 1.0f : f));
+      float th = 2.0f * atan2f(sqrtf(rm1) * sh, sqrtf(r + 1.0f) * ch);
       float us = bits_to_unit(elem_bits(sk, c + 2 * VON_MISES_TRIES));
       decide(us, 0.5f);
       return a + (us < 0.5f ? -th : th);
     }
-    case GJX_CHI: return expf(0.5f * (0.69314718f + log_gamma_variate(sk, c, 0.5f * a)));
+    case GJX_CHI: return clamp_positive(expf(0.5f * (0.69314718f + log_gamma_variate(sk, c, 0.5f * a))));
     case GJX_EXP_GAMMA: return log_gamma_variate(sk, c, a) - logf(b);
     case GJX_EXP_INVERSE_GAMMA: return logf(b) - log_gamma_variate(sk, c, a);
     case GJX_KUMARASWAMY: { /* x = (1 - (1 - u)^(1 / b))^(1 / a) */
       float t = log1pf(-bits_to_unit(elem_bits(sk, c))) / b;
       float m = -expm1f(t);
-      return expf(logf(m) / a);
+      return clamp_unit(expf(logf(m) / a));
     }
     case GJX_MOYAL: { /* -log of a chi2(1) variate: loc - scale log(n^2) */
       float n = fabsf(stream_normal(sk, c));
+      if (n < F32_HALF_STEP) n = F32_HALF_STEP;      /* (a FLAT normal is exactly 0 once in 2^23 draws: -log 0) */
       return a - 2.0f * b * logf(n);
     }
     case GJX_DOUBLESIDED_MAXWELL: { /* a random sign times the root of a chi2(3) variate */
@@ -688,7 +777,9 @@ static float elem_sample4(int kind, const ostream* sk, uint32_t c, float a, floa
       decide(u, 0.5f);
       float sgn = u < 0.5f ? -1.0f : 1.0f;
       float r = expf(0.5f * (0.69314718f + log_gamma_variate(sk, c + 2, 1.5f)));
-      return a + b * sgn * r;
+      const float x = a + b * sgn * r;
+      /* the density is 0 AT loc: a draw that rounds onto it (scale below loc's float32 step) takes the neighbour on its own side */
+      return x != a ? x : nextafterf(a, sgn * INFINITY);
     }
     case GJX_INVERSE_GAUSSIAN: { /* Michael, Schucany & Haas (1976): a = mean, b = concentration */
       float n = stream_normal(sk, c);
@@ -703,28 +794,30 @@ static float elem_sample4(int kind, const ostream* sk, uint32_t c, float a, floa
       float lo = (p3 - a) / b, hi = (p4 - a) / b;
       float u = bits_to_unit(elem_bits(sk, c));
       float z;
-      if (lo > 0.0f) {
-        float q = std_normal_cdf(-lo) - u * (std_normal_cdf(-lo) - std_normal_cdf(-hi));
-        z = -1.41421356f * erfinv_f32(2.0f * q - 1.0f);
+      if (tn_tail_window(lo, hi)) {
+        z = tn_tail_variate(lo, hi, u);
       } else {
-        float q = std_normal_cdf(lo) + u * (std_normal_cdf(hi) - std_normal_cdf(lo));
-        z = 1.41421356f * erfinv_f32(2.0f * q - 1.0f);
+        /* every other window: 2 q - 1 = erf(lo / sqrt 2) + u (erf(hi / sqrt 2) - erf(lo / sqrt 2)) straight from erf, which keeps its RELATIVE precision
+         * around 0 — Phi(hi) - Phi(lo) of the window [-1e-3, 1e-3] is a difference of two numbers next to 1/2, and the device's erfc left 1e-3 of it
+         * (tests/test_gpu_samplers.py: CDF off by 9.8e-4, z 10.9) */
+        const float el = erff(lo * 0.70710678f), eh = erff(hi * 0.70710678f);
+        z = 1.41421356f * erfinv_f32(el + u * (eh - el));
       }
       float x = a + b * z;
       return x < p3 ? p3 : (x > p4 ? p4 : x);
     }
     case GJX_POISSON: return poisson_variate(sk, c, a);
     case GJX_GEOMETRIC: {
-      const float raw = logf(uniform_from_bits(elem_bits(sk, c), F32_TINY, 1.0f)) / log1pf(-a);
+      const float raw = logf(unit_open(elem_bits(sk, c))) / log1pf(-a);
       decide(raw, floorf(raw)); decide(raw, floorf(raw) + 1.0f);
       return floorf(raw);
     }
-    case GJX_GUMBEL: return a - b * logf(-logf(uniform_from_bits(elem_bits(sk, c), F32_TINY, 1.0f)));
+    case GJX_GUMBEL: return a - b * logf(-logf(unit_open(elem_bits(sk, c))));
     case GJX_HALF_CAUCHY: return a + b * tanf(0.5f * 3.14159265f * bits_to_unit(elem_bits(sk, c)));
-    case GJX_INVERSE_GAMMA: return b * expf(-log_gamma_variate(sk, c, a));
-    case GJX_WEIBULL: return b * expf(logf(-log1pf(-bits_to_unit(elem_bits(sk, c)))) / a);
-    case GJX_LOGIT_NORMAL: return sigmoidf_(a + b * stream_normal(sk, c));
-    case GJX_CHI2: return 2.0f * expf(log_gamma_variate(sk, c, 0.5f * a));
+    case GJX_INVERSE_GAMMA: return clamp_positive(b * expf(-log_gamma_variate(sk, c, a)));
+    case GJX_WEIBULL: return clamp_positive(b * expf(logf(-log1pf(-bits_to_unit(elem_bits(sk, c)))) / a));
+    case GJX_LOGIT_NORMAL: return clamp_unit(sigmoidf_(a + b * stream_normal(sk, c)));
+    case GJX_CHI2: return clamp_positive(2.0f * expf(log_gamma_variate(sk, c, 0.5f * a)));
     default: return NAN;
   }
 }
@@ -738,10 +831,10 @@ static float elem_sample(int kind, const ostream* sk, uint32_t c, float a, float
     case GJX_BETA: {
       float g1 = log_gamma_variate(sk, c, a);
       float g2 = log_gamma_variate(sk, c + GAMMA_NDRAW, b);
-      return sigmoidf_(g1 - g2);
+      return clamp_unit(sigmoidf_(g1 - g2));
     }
     case GJX_UNIFORM: return a + (b - a) * bits_to_unit(elem_bits(sk, c));
-    case GJX_EXPONENTIAL: return -logf(uniform_from_bits(elem_bits(sk, c), F32_TINY, 1.0f)) / a;
+    case GJX_EXPONENTIAL: return -logf(unit_open(elem_bits(sk, c))) / a;
     case GJX_HALF_NORMAL: return fabsf(stream_normal(sk, c)) * a;
     case GJX_LAPLACE: {
       float u = uniform_from_bits(elem_bits(sk, c), NEG1_PLUS_ULP, 1.0f);
@@ -750,7 +843,7 @@ static float elem_sample(int kind, const ostream* sk, uint32_t c, float a, float
     }
     case GJX_LOG_NORMAL: return expf(a + b * stream_normal(sk, c));
     case GJX_CAUCHY: return a + b * tanf(3.14159265f * (bits_to_unit(elem_bits(sk, c)) - 0.5f));
-    case GJX_GAMMA: return expf(log_gamma_variate(sk, c, a)) / b;
+    case GJX_GAMMA: return clamp_positive(expf(log_gamma_variate(sk, c, a)) / b);
     default: return NAN;
   }
 }
@@ -894,7 +987,7 @@ static float run_site(const gjx_program* prog, const gjx_site* s0, int inst, con
         if (x[d] > mx) mx = x[d];
       }
       for (int d = 0; d < n; ++d) se += expf(x[d] - mx);
-      for (int d = 0; d < n; ++d) x[d] = expf(x[d] - (mx + logf(se)));
+      for (int d = 0; d < n; ++d) x[d] = clamp_unit(expf(x[d] - (mx + logf(se))));
     } else {
       for (int d = 0; d < n; ++d) x[d] = mode == GJX_MODE_OBS_TAB ? tab[s->obs_off + d] : vals[s->slot + d];
     }

@@ -333,3 +333,205 @@ def bnn_model(N=64, DI=16, DH=8, seed=0, first_is_one=False):
         return (Y[:, None] * -np.logaddexp(0, -lg) + (1 - Y[:, None]) * -np.logaddexp(0, lg)).sum(0)
 
     return bnn, X, Y, loglik
+
+
+# ---------------------------------------------------------------------------------------------
+# the sampler grid (tests/golden/make_sampler_grid.py): exact CDFs at fixed edges, shared by tests/test_samplers_cpu.py and
+# tests/test_gpu_samplers.py
+# ---------------------------------------------------------------------------------------------
+SAMPLER_Z = 6.0      # a normal deviate of 2e-9 per edge: over ~260 edges x ~300 rows x 6 variants (oracle and two engines, two RNG layouts) < 1e-3
+
+
+@functools.lru_cache(maxsize=None)
+def sampler_grid():
+    """tests/golden/sampler_grid.json.gz: {"levels", "M", kind: record}, read once and left unchanged"""
+    with gzip.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sampler_grid.json.gz"), "rt") as f:
+        return json.load(f)
+
+
+def sampler_grid_program(kind: str, rng, rows=None):
+    """Particle i carries grid row i // M: a carrier site p_j ~ uniform(-1e37, 1e37) per parameter, MODE_OBS_SLOT (its value comes in with
+    the choices), and x ~ KIND(p_0, ...) left to be SAMPLED.  -> (program, choices [n_slots, rows * M], slot of x, index of x's site)"""
+    g = sampler_grid()
+    rec, M = g[kind], g["M"]
+    rws = rec["rows"] if rows is None else [rec["rows"][i] for i in rows]
+    n = NPAR[kind]
+    sl = SiteList()
+    for j in range(n):
+        sl.add(f"p{j}", A.UNIFORM, [-1e37, 1e37])
+    sl.add("x", KIND[kind], [Param.value(f"p{j}") for j in range(n)])
+    prog = PackedProgram(sl, {f"p{j}": A.MODE_OBS_SLOT for j in range(n)}, rng_mode=rng)
+    ch = np.zeros((max(prog.n_slots, 1), len(rws) * M), np.float32)
+    for j in range(n):
+        ch[prog.slot_of[f"p{j}"]] = np.repeat(np.asarray([r["p"][j] for r in rws], np.float32), M)
+    return prog, ch, prog.slot_of["x"], n
+
+
+def sampler_edges(g, rec, row):
+    """-> (edges as float64 values of float32 numbers, exact F there)"""
+    e = np.asarray(row["e"], np.float32).astype(np.float64)
+    if rec["discrete"]:
+        return e, np.asarray(row["F"], np.float64)
+    return e, np.asarray(g["levels"], np.float64)[row["lv"]] + np.asarray(row["dF"], np.float64)
+
+
+def sampler_edge_bound(F, M, z=SAMPLER_Z):
+    return z * np.sqrt(F * (1.0 - F) / M) + 1.0 / M
+
+
+def sampler_row_check(x, g, rec, row, integer=None):
+    """one row's draws x (any float array, judged in float64) -> (excess, text): excess = the largest |empirical - exact| / bound over
+    the row's edges, inf when a draw is not finite, outside the support, outside the guard quantiles or (discrete) no integer;
+    text says which.  Also -> the largest z-score, |empirical - exact - (+-1/M)| / sqrt(F (1 - F) / M), for the write-down."""
+    M = g["M"]
+    x = np.asarray(x, np.float64)
+    assert x.shape == (M,), x.shape
+    if not np.isfinite(x).all():
+        return np.inf, 0.0, f"{int((~np.isfinite(x)).sum())} draws are not finite"
+    if "wrap" in row:
+        x = x - row["wrap"]
+        x = x - 2.0 * np.pi * np.round(x / (2.0 * np.pi))
+    xs = np.sort(x)
+    lo, hi = row["lo"], row["hi"]
+    if lo is not None and (xs[0] < lo or (row["lo_open"] and xs[0] <= lo)):
+        return np.inf, 0.0, f"{int((xs <= lo).sum())} draws at or below the support's lower edge {lo} (smallest {xs[0]!r})"
+    if hi is not None and (xs[-1] > hi or (row["hi_open"] and xs[-1] >= hi)):
+        return np.inf, 0.0, f"{int((xs >= hi).sum())} draws at or above the support's upper edge {hi} (largest {xs[-1]!r})"
+    if row["x_lo"] is not None and xs[0] < row["x_lo"]:
+        return np.inf, 0.0, f"smallest draw {xs[0]!r} below the 1e-6/M quantile {row['x_lo']!r}"
+    if row["x_hi"] is not None and xs[-1] > row["x_hi"]:
+        return np.inf, 0.0, f"largest draw {xs[-1]!r} above the 1 - 1e-6/M quantile {row['x_hi']!r}"
+    if (rec["discrete"] if integer is None else integer) and (xs != np.floor(xs)).any():
+        return np.inf, 0.0, "non-integer draws of a discrete kind"
+    e, F = sampler_edges(g, rec, row)
+    if e.size == 0:
+        return 0.0, 0.0, "no edge"
+    emp = np.searchsorted(xs, e, side="right") / M          # mean(x <= e_j)
+    dev = np.abs(emp - F)
+    ex = dev / sampler_edge_bound(F, M)
+    zs = np.maximum(dev - 1.0 / M, 0.0) / np.sqrt(F * (1.0 - F) / M)
+    j = int(np.argmax(ex))
+    return float(ex[j]), float(zs.max()), f"edge {e[j]!r}: empirical {emp[j]:.6g}, exact {F[j]:.6g}, z {zs[j]:.2f} (largest |deviation| {dev.max():.3g})"
+
+
+def sampler_grid_check(x, rec, rows=None):
+    """x: [rows * M] draws of one kind's program (sampler_grid_program) -> (worst excess, worst z, [(row index, parameters, text)] of the
+    rows whose excess is over 1).  Works in float64."""
+    g = sampler_grid()
+    M = g["M"]
+    idx = list(range(len(rec["rows"]))) if rows is None else list(rows)
+    x = np.asarray(x).reshape(len(idx), M)
+    worst, worst_z, bad = 0.0, 0.0, []
+    for k, i in enumerate(idx):
+        ex, z, text = sampler_row_check(x[k], g, rec, rec["rows"][i])
+        worst, worst_z = max(worst, ex), max(worst_z, z)
+        if ex > 1.0:
+            bad.append((i, tuple(rec["rows"][i]["p"]), text))
+    return worst, worst_z, bad
+
+
+def one_vector_site(kind_code: int, params, dim=None, rng=A.RNG_FLAT):
+    """one sampled site "v" of a vector or categorical kind with constant parameters"""
+    sl = SiteList()
+    sl.add("v", kind_code, params, **({} if dim is None else {"dim": dim}))
+    return PackedProgram(sl, rng_mode=rng)
+
+
+def sampler_row_from_dist(dist, unit=False):
+    """a grid row made on the spot from a frozen scipy distribution (the components of the vector kinds: beta marginals of a
+    dirichlet, normal components), by make_sampler_grid.py's rules: the levels' quantiles rounded to float32, F exact AT the rounded
+    edge, kept when 0 < F < 1, float32-resolvable (the mass between the edge's float32 neighbours under a quarter of its bound) and,
+    for a unit-interval kind, strictly inside (1.17549435e-38, 1 - 2^-24).  -> (record, row) for sampler_row_check"""
+    g = sampler_grid()
+    M, lv = g["M"], np.asarray(g["levels"], np.float64)
+    with np.errstate(all="ignore"):
+        e = np.where(lv < 0.5, dist.ppf(lv), dist.isf(1.0 - lv)).astype(np.float32)
+        up, dn = np.nextafter(e, np.float32(np.inf)).astype(np.float64), np.nextafter(e, np.float32(-np.inf)).astype(np.float64)
+        e = e.astype(np.float64)
+        F = dist.cdf(e)
+        keep = np.isfinite(e) & (F > 0.0) & (F < 1.0) & (dist.cdf(up) - dist.cdf(dn) < 0.25 * sampler_edge_bound(F, M))
+    if unit:
+        keep &= (e > 1.17549435e-38) & (e < 1.0 - 2.0 ** -24)
+    rec = dict(discrete=1)          # (F stored whole, as the discrete kinds do)
+    q = 1e-6 / M
+    row = dict(e=[float(t) for t in e[keep]], F=[float(t) for t in F[keep]], lo=0.0 if unit else None, hi=1.0 if unit else None,
+               lo_open=1, hi_open=1, x_lo=None if unit else float(np.float32(dist.ppf(q)) - np.float32(abs(dist.ppf(q))) * 2.0 ** -22),
+               x_hi=None if unit else float(np.float32(dist.isf(q)) + np.float32(abs(dist.isf(q))) * 2.0 ** -22))
+    return rec, row
+
+
+def sampler_component_check(x, dist, unit=False):
+    """-> (excess, z, text) of one component's M draws against `dist` (sampler_row_check; integer test off)"""
+    rec, row = sampler_row_from_dist(dist, unit)
+    return sampler_row_check(x, sampler_grid(), rec, row, integer=False)
+
+
+DIRICHLET_ALPHAS = ([0.8, 2.0, 3.0], [0.05, 0.05, 0.05], [50.0, 1.0, 0.2])
+MVN_LOC = [0.0, 1e4, -2.0, 0.5, 3e2]
+MVN_SCALE = [1.0, 1e-3, 1e-6, 2.5, 30.0]
+
+
+def dirichlet_check(x, alpha):
+    """x [dim, M] draws of dirichlet(alpha): each component against beta(alpha_i, alpha_0 - alpha_i), rows sum to 1 within 1e-5, no
+    component exactly 0 or 1 (sampler_row_check's open support).  -> (worst excess, worst z, [failures])"""
+    import scipy.stats as st
+    x = np.asarray(x, np.float64)
+    a = np.asarray(np.asarray(alpha, np.float32), np.float64)
+    worst, wz, bad = 0.0, 0.0, []
+    s = np.abs(x.sum(0) - 1.0).max()
+    if not s <= 1e-5:
+        bad.append(("sum", float(s)))
+    for i in range(len(a)):
+        ex, z, text = sampler_component_check(x[i], st.beta(a[i], a.sum() - a[i]), unit=True)
+        worst, wz = max(worst, ex), max(wz, z)
+        if ex > 1.0:
+            bad.append((i, text))
+    return worst, wz, bad
+
+
+def mvn_check(x, loc=MVN_LOC, scale=MVN_SCALE):
+    import scipy.stats as st
+    x = np.asarray(x, np.float64)
+    worst, wz, bad = 0.0, 0.0, []
+    for i in range(len(loc)):
+        ex, z, text = sampler_component_check(x[i], st.norm(float(np.float32(loc[i])), float(np.float32(scale[i]))))
+        worst, wz = max(worst, ex), max(wz, z)
+        if ex > 1.0:
+            bad.append((i, text))
+    return worst, wz, bad
+
+
+def categorical_case(n, probs: bool):
+    """-> (float32 parameter vector, exact float64 probabilities): n categories, a logit spread of 60 (n > 3), category 1 impossible
+    (a -inf logit / a 0 probability)"""
+    rs = np.random.default_rng(n)
+    lg = (rs.random(n) * 6.0 - 3.0).astype(np.float32)
+    lg[0] = 3.0
+    if n > 3:
+        lg[n - 1] = -57.0          # (with 3 categories, one of them impossible, a spread of 60 would leave a single outcome)
+    if probs:
+        par = np.exp(lg.astype(np.float64))
+        par[1] = 0.0
+        par = (par / par.sum() * 0.5).astype(np.float32)          # (unnormalised on purpose: the kernel normalises)
+        p = par.astype(np.float64)
+    else:
+        lg[1] = -np.inf
+        par = lg
+        with np.errstate(all="ignore"):
+            p = np.exp(lg.astype(np.float64) - 3.0)
+    return par, p / p.sum()
+
+
+def categorical_check(v, p):
+    """v: M category draws -> (worst excess, [failures]): per category |count / M - p| <= 6 sqrt(p (1 - p) / M) + 1 / M; a category of
+    probability 0 has count exactly 0; every draw an integer in range"""
+    M = sampler_grid()["M"]
+    v = np.asarray(v, np.float64)
+    assert v.shape == (M,)
+    if not (np.isfinite(v).all() and (v == np.floor(v)).all() and v.min() >= 0 and v.max() < len(p)):
+        return np.inf, ["draws outside 0 .. n - 1"]
+    cnt = np.bincount(v.astype(np.int64), minlength=len(p))
+    ex = np.abs(cnt / M - p) / sampler_edge_bound(p, M)
+    bad = [(int(c), int(cnt[c]), float(p[c])) for c in np.nonzero(ex > 1.0)[0]]
+    bad += [(int(c), int(cnt[c]), 0.0) for c in np.nonzero((p == 0.0) & (cnt > 0))[0]]
+    return float(ex.max()), bad
