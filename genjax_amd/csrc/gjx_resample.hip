@@ -6,6 +6,7 @@
 // thresholds are one IEEE double multiply + truncation per output slot.  HBM traffic per
 // particle: pick 4 B read; cumsum 2x4 B read + 8 B write; search 4 B write (+ L2-resident
 // binary-search probes); gather 4 B read + 4 B write per row.
+#include <limits.h>
 #include <math.h>
 #include <string.h>
 
@@ -326,9 +327,12 @@ __global__ __launch_bounds__(256) void k_resample_fused(const float* __restrict_
 // the ancestors never written to memory unless asked for.  Block b scans its own tile of 256 ITEMS fixed-point weights,
 // the tile totals are all-gathered (the one rendezvous, as in k_resample_fused), and then the block is the CONSUMER of
 // the output slots [b TILE, (b+1) TILE): each lane takes ITEMS consecutive slots, computes their comb thresholds T_j,
-// finds the source tile of each by binary search in the prefix of the tile totals (LDS), and the block re-scans the few
-// distinct source tiles its thresholds fall into (log-weights from L2, the next tile's loads in flight while the current
-// one is searched); ancestor = first particle of the tile with inclusive cumulative weight > T_j.  Same ancestors as
+// and finds the source tile of each among the eight tiles around its own, whose boundaries are the weight below them (summed
+// while the totals are gathered) plus a serial prefix of eight totals; the cumulative weights of tiles b - 1 .. b + 1 are in
+// LDS by then, and a lane searches its first slot and counts the others off in a short window (rank_in_tiles_sorted).  Only a
+// block whose slots leave those windows (collapsed or drifting weights) makes the full prefix of the totals, descends in it,
+// and re-scans the few distinct source tiles its thresholds fall into (log-weights from L2, the next tile's loads in flight
+// while the current one is searched); ancestor = first particle of the tile with inclusive cumulative weight > T_j.  Same ancestors as
 // the slot-run expansion: particle i owns slot j  <=>  cum_excl(i) <= T_j < cum_incl(i).  Then the rows are copied,
 // ITEMS slots per lane (16-byte stores at ITEMS = 4).  Balanced whatever the weights are; a window that touches many
 // source tiles (collapsed weights) just loops longer.
@@ -348,9 +352,10 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
   constexpr int TILE = 256 * ITEMS;
   __shared__ float fred[8];
   __shared__ uint64_t wsum[4];
-  __shared__ uint64_t P[kGatherMaxTiles + 1];   // P[t] = total weight of tiles < t; P[nb] = grand total
+  __shared__ uint64_t s_sums[8];                // wave sums of the totals: below the window [4], all [4]
+  __shared__ uint64_t P[kGatherMaxTiles + 1];   // P[b + 1] = total of tile b; on the re-scan branch their prefix: P[t] = total weight of tiles < t
   constexpr int CH = 3;                          // source tiles re-scanned per round
-  __shared__ uint64_t cumL[CH * TILE];          // inclusive cumulative weights (absolute) of the tiles being searched
+  __shared__ __align__(16) uint64_t cumL[CH * TILE];   // inclusive cumulative weights of the tiles being searched, relative to each tile's start (16-byte reads)
   __shared__ uint64_t s_wtot[CH][4];
   __shared__ int s_range[2];                    // first and last source tile of this block's slots
   unsigned epoch;
@@ -423,13 +428,24 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
       for (int k = 0; k < ITEMS; ++k) cumL[c * TILE + threadIdx.x * ITEMS + k] = base + (c == 1 ? qown[k] : qn[c >> 1][k]);
     }
   }
-  grid_gather(agg, tag, ctrl, [&](int b, unsigned long long val) { P[b + 1] = val; });
+  // the totals land in P[1 .. nb] as they are; what the usual case needs of their prefix — the grand total and the weight below the
+  // nine-boundary window of source_tiles — is summed on the way (u64 adds: the same bits in any order).  The prefix itself is
+  // made only by a block whose slots leave that window (below)
+  const int wlo = source_window_start(nb, (int)blockIdx.x);
+  uint64_t below = 0, total = 0;
+  grid_gather(agg, tag, ctrl, [&](int b, unsigned long long val) {
+    P[b + 1] = val;
+    total += val;
+    below += b < wlo ? val : 0;
+  });
+  below = wave_sum_u64(below);
+  total = wave_sum_u64(total);
+  if (lane == 0) { s_sums[wid] = below; s_sums[4 + wid] = total; }
   if (threadIdx.x == 0) P[0] = 0;
   __syncthreads();
+  below = sum_partials<4>(s_sums);
+  total = sum_partials<4>(s_sums + 4);
   GJX_STAMP(2);
-  prefix_in_place<256>(P, nb, wsum, NoShift{});   // (the publish above read wsum before the barrier behind the gather)
-  const uint64_t total = P[nb];
-  GJX_STAMP(6);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     __hip_atomic_store(&ctrl[0], epoch + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (total == 0) __hip_atomic_fetch_or(&ctrl[2], kStatusZeroTotal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -448,29 +464,58 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
       const int64_t j = (i0 + k < K) ? i0 + k : K - 1;
       T[k] = comb_threshold(j, u, step, total);
     }
-    source_tiles<ITEMS>(P, nb, (int)blockIdx.x, T, tile);        // thresholds are non-decreasing in the slot index
+    // the nine boundaries of the window around the own tile: the weight below it plus a serial prefix of eight totals (the same
+    // addresses in every lane), and the tile and residual of every slot counted off against them — what source_tiles does on a
+    // finished prefix.  Thresholds do not decrease with the slot index, so the block's slots all lie inside the window if its
+    // first and its last one do; the tile index does not decrease either, so the block's source tiles are the range between the
+    // first and the last slot's tile — no list to build, the two ends (or "outside") travel through LDS behind one barrier
+    uint64_t Tr[ITEMS];                             // residual of every slot in its source tile
+    uint64_t Pw[9];
+    Pw[0] = below;
+#pragma unroll
+    for (int w = 1; w < 9; ++w) Pw[w] = Pw[w - 1] + (wlo + w <= nb ? P[wlo + w] : 0);
+    GJX_STAMP(6);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+      tile[k] = wlo;
+      uint64_t lo = Pw[0];
+#pragma unroll
+      for (int w = 1; w < 8; ++w) {
+        const bool past = Pw[w] <= T[k];
+        tile[k] += past ? 1 : 0;
+        lo = past ? Pw[w] : lo;
+      }
+      Tr[k] = T[k] - lo;
+    }
     if (timeline) { asm volatile("" :: "v"(tile[0]), "v"(tile[ITEMS - 1])); GJX_STAMP(7); }
-    // the block's source tiles: the tile index is non-decreasing in the slot index, so they are the range between the
-    // first and the last slot's tile — no list to build, the two ends travel through LDS behind one barrier.  A round
-    // starts at a tile that has weight (block-uniform skip; the range's last tile always has), so collapsed weights far
-    // apart cost as many rounds as there are live tiles
-    if (threadIdx.x == 0) s_range[0] = tile[0];
-    if (threadIdx.x == 255) s_range[1] = tile[ITEMS - 1];
+    if (threadIdx.x == 0) s_range[0] = T[0] >= Pw[0] ? tile[0] : INT_MIN;
+    if (threadIdx.x == 255) s_range[1] = T[ITEMS - 1] < Pw[8] ? tile[ITEMS - 1] : INT_MAX;
     __syncthreads();
-    const int tmin = s_range[0], ntiles = s_range[1] - tmin + 1;
+    int tmin = s_range[0], tmax = s_range[1];
+    const bool windowed = tmin >= w0 && tmax <= w0 + 2;   // block-uniform: every source tile is in the prefetched window (w0 >= -1)
     int pos[ITEMS];
     const uint64_t* cm[ITEMS];
-    uint64_t Tr[ITEMS];                             // residual of every slot in its source tile
-#pragma unroll
-    for (int k = 0; k < ITEMS; ++k) Tr[k] = T[k] - P[tile[k]];
-    if (tmin >= w0 && s_range[1] <= w0 + 2) {       // block-uniform: every source tile is in the prefetched window
+    if (windowed) {
       GJX_STAMP(3);
 #pragma unroll
       for (int k = 0; k < ITEMS; ++k) cm[k] = cumL + (tile[k] - w0) * TILE;
-      rank_in_tiles<TILE, ITEMS>(cm, Tr, pos);
+      if constexpr (ITEMS > 1) rank_in_tiles_sorted<TILE, ITEMS>(cm, Tr, pos);
+      else rank_in_tiles<TILE, ITEMS>(cm, Tr, pos);
 #pragma unroll
       for (int k = 0; k < ITEMS; ++k) anc[k] = (int32_t)((int64_t)tile[k] * TILE + pos[k]);
     } else {
+    // collapsed or strongly drifting weights: the full prefix of the totals, the source tiles by descent, and the re-scan.  A round
+    // starts at a tile that has weight (block-uniform skip; the range's last tile always has), so collapsed weights far
+    // apart cost as many rounds as there are live tiles
+    prefix_in_place<256>(P, nb, wsum, NoShift{});   // (every lane read s_range before the barrier inside; the publish read wsum long ago)
+    source_tiles<ITEMS>(P, nb, (int)blockIdx.x, T, tile);
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) Tr[k] = T[k] - P[tile[k]];
+    if (threadIdx.x == 0) s_range[0] = tile[0];
+    if (threadIdx.x == 255) s_range[1] = tile[ITEMS - 1];
+    __syncthreads();
+    tmin = s_range[0]; tmax = s_range[1];
+    const int ntiles = tmax - tmin + 1;
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) kpos[k] = tile[k] - tmin;
     auto next_live = [&](int at) { while (at < ntiles && P[tmin + at + 1] == P[tmin + at]) ++at; return at; };
@@ -493,14 +538,16 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
         if (nidx + c < ntiles) load_tile((int64_t)(tmin + nidx + c) * TILE + o, nv[c]);   // next round, in flight
         return on;
       }, [] {});
-      // first particle p of the slot's tile with cum_incl(p) > T (a slot of another round searches the round's first tile for nothing)
+      // first particle p of the slot's tile with cum_incl(p) > T (a slot of another round is left out; with one slot per lane it
+      // searches the round's first tile for nothing)
       bool mine[ITEMS];
 #pragma unroll
       for (int k = 0; k < ITEMS; ++k) {
         mine[k] = kpos[k] >= idx && kpos[k] < idx + CH;
         cm[k] = cumL + (mine[k] ? (kpos[k] - idx) * TILE : 0);
       }
-      rank_in_tiles<TILE, ITEMS>(cm, Tr, pos);
+      if constexpr (ITEMS > 1) rank_in_tiles_sorted<TILE, ITEMS>(cm, Tr, mine, pos);
+      else rank_in_tiles<TILE, ITEMS>(cm, Tr, pos);
 #pragma unroll
       for (int k = 0; k < ITEMS; ++k)
         if (mine[k]) anc[k] = (int32_t)((int64_t)tile[k] * TILE + pos[k]);

@@ -250,9 +250,12 @@ GJX_DEV uint64_t block_scan_chunked(int n, uint64_t* wsum, Val val, Out out) {
 // that window descends: fixed trip count from the largest power of two <= n (nine dependent reads at n = 256), the first and the
 // last slot together (independent reads per round); the slots between them are in the same tile unless the lane straddles a tile
 // boundary (then they are searched too).
+GJX_DEV int source_window_start(int n, int own) {   // first of the eight tiles around `own` (n < 8: all of them)
+  return own - 4 < 0 ? 0 : (own - 4 > n - 8 ? (n - 8 < 0 ? 0 : n - 8) : own - 4);
+}
 template <int ITEMS>
 GJX_DEV void source_tiles(const uint64_t* P, int n, int own, const uint64_t (&T)[ITEMS], int (&tile)[ITEMS]) {
-  const int wlo = own - 4 < 0 ? 0 : (own - 4 > n - 8 ? (n - 8 < 0 ? 0 : n - 8) : own - 4);
+  const int wlo = source_window_start(n, own);
   uint64_t Pw[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) Pw[k] = P[wlo + k < n ? wlo + k : n];
@@ -294,8 +297,11 @@ GJX_DEV int source_tile(const uint64_t* P, int n, int own, uint64_t T) {
 }
 
 // Ranks of N residuals in tiles of TILE inclusive cumulative weights: pos[k] = number of entries of cm[k] that are <= r[k] = the first
-// particle whose cumulative weight exceeds it.  4-ary: three independent probes per level and slot, 5 LDS latencies for 1024 entries
-// instead of 10; the probes of different slots are interleaved level by level, so they are independent too.
+// particle whose cumulative weight exceeds it.  4-ary: three independent probes per level and slot, so the dependent chain is 5 LDS
+// reads for 1024 entries instead of 10, and the probes of different slots are interleaved level by level.  The chain is not what a
+// search costs a full CU, though: it is 15 8-byte reads per slot, the last three levels at scattered addresses, and 16 waves of
+// four slots per lane keep the LDS busy for 2.3 - 2.5 us (k_resample_gather, K = 2^20) against 0.3 us of latency.  Callers with
+// several slots per lane whose residuals do not decrease use rank_in_tiles_sorted (below), which searches once per lane.
 template <int TILE, int N>
 GJX_DEV void rank_in_tiles(const uint64_t* (&cm)[N], const uint64_t (&r)[N], int (&pos)[N]) {
 #pragma unroll
@@ -316,6 +322,64 @@ GJX_DEV int rank_in_tile(const uint64_t* cm, uint64_t r) {
   int pos[1];
   rank_in_tiles<TILE, 1>(cm1, r1, pos);
   return pos[0];
+}
+// The same ranks for the N > 1 slots of a lane when the residuals of slots that share a tile do not decrease with the slot index
+// (consecutive comb thresholds): slot 0 is searched as above and anchors a window of kRankWalk entries, from the even index at or
+// below its rank (16-byte reads; moved down where it would leave the tile), read ONCE for all the slots that follow in the same
+// tile: pos[k] = window start + the number of its entries that are <= r[k].  Exact: every entry below the anchor's rank is <= the
+// anchor's residual <= r[k] and the entries do not decrease, so those that are <= r[k] are a prefix of the window.  A window that
+// is <= r[k] throughout and does not reach the tile's end says nothing about what follows: that slot is searched 4-ary and becomes
+// the anchor of the slots behind it, as does a slot in another tile than the anchor's (a lane that straddles two source tiles).
+// on[k] == false leaves slot k out (pos[k] = 0, nothing is read for it).  cm[k] 16-byte aligned.
+// kRankWalk = 12: with the mixture model's weights at K = 2^20 (log-weights of sd 1.04; keys (0,1), (0,2), u = 0.37, 0.5) the fourth
+// slot of a lane lies at most 14 entries above the even index below the first, and the share of waves (64 lanes x 4 slots) with a
+// slot outside the window is 78 % for 8 entries, 0.4 - 0.55 % for 12, none for 16: 12 is the smallest below 1 %.  (Consecutive
+// slots are at most 8 apart: a window per slot, anchored at its predecessor, needs 8 entries for the same share — 0.15 - 0.35 % —
+// which is twice the reads for three slots and three dependent reads instead of one.)
+constexpr int kRankWalk = 12;
+template <int TILE, int N>
+GJX_DEV void rank_in_tiles_sorted(const uint64_t* (&cm)[N], const uint64_t (&r)[N], const bool (&on)[N], int (&pos)[N]) {
+  typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+  constexpr int W = kRankWalk;
+  static_assert(N > 1 && W % 2 == 0 && W <= TILE && TILE % 2 == 0, "an even window inside the tile");
+  const uint64_t* acm = cm[0];        // the anchor: its tile, whether it has one, its window
+  bool aon = on[0];
+  int base = 0;
+  u64x2 win[W / 2] = {};
+  auto anchor_at = [&](int at) {      // (at <= TILE: the reads stay inside the tile)
+    const int even = at & ~1;
+    base = even > TILE - W ? TILE - W : even;
+#pragma unroll
+    for (int j = 0; j < W / 2; ++j) win[j] = ((const u64x2*)(acm + base))[j];
+  };
+  pos[0] = 0;
+  if (on[0]) {
+    pos[0] = rank_in_tile<TILE>(cm[0], r[0]);
+    anchor_at(pos[0]);
+  }
+#pragma unroll
+  for (int k = 1; k < N; ++k) {
+    bool full = on[k];
+    pos[k] = 0;
+    if (on[k] && aon && cm[k] == acm) {
+      int cnt = 0;
+#pragma unroll
+      for (int j = 0; j < W / 2; ++j) cnt += (win[j].x <= r[k] ? 1 : 0) + (win[j].y <= r[k] ? 1 : 0);
+      pos[k] = base + cnt;
+      full = cnt == W && base + W < TILE;
+    }
+    if (full) {
+      pos[k] = rank_in_tile<TILE>(cm[k], r[k]);
+      if (k + 1 < N) { acm = cm[k]; aon = true; anchor_at(pos[k]); }
+    }
+  }
+}
+template <int TILE, int N>
+GJX_DEV void rank_in_tiles_sorted(const uint64_t* (&cm)[N], const uint64_t (&r)[N], int (&pos)[N]) {
+  bool on[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) on[k] = true;
+  rank_in_tiles_sorted<TILE, N>(cm, r, on, pos);
 }
 
 // One round of the re-scan: the inclusive cumulative fixed-point weights of up to THREADS / 64 / (TILE / (64 ITEMS)) * CPT source tiles,
@@ -393,7 +457,7 @@ GJX_DEV int64_t tiled_lookup(const uint64_t* P, const int32_t* sh, const uint64_
 struct TiledSearchShared {
   float fred[8];
   uint64_t wsum[4];
-  uint64_t cumL[3 * 1024];                                     // cumulative q of the tiles being searched, relative to the tile's start
+  alignas(16) uint64_t cumL[3 * 1024];                         // cumulative q of the tiles being searched, relative to the tile's start (16-byte reads)
   uint64_t s_wtot[3][4];
   int s_range[2];
 };
@@ -526,8 +590,13 @@ GJX_DEV void tiled_search_tile(const float* __restrict__ x, int64_t K, const uin
         for (int k = 0; k < ITEMS; ++k) q[k] = tile_q(xw[c][k], Eb[tc]);
         return true;
       }, [] {});
+      const uint64_t* cm[ITEMS];
+      int pos[ITEMS];
 #pragma unroll
-      for (int k = 0; k < ITEMS; ++k) anc[k] = (int32_t)((int64_t)tile[k] * TILE + rank_in_tile<TILE>(sh.cumL + (tile[k] - w0) * TILE, Tr[k]));
+      for (int k = 0; k < ITEMS; ++k) cm[k] = sh.cumL + (tile[k] - w0) * TILE;
+      rank_in_tiles_sorted<TILE, ITEMS>(cm, Tr, pos);          // (the residuals of slots in one tile do not decrease: same start, same shift)
+#pragma unroll
+      for (int k = 0; k < ITEMS; ++k) anc[k] = (int32_t)((int64_t)tile[k] * TILE + pos[k]);
     } else {
       // collapsed or strongly drifting weights: re-scan the source tiles CH at a time (tiles without weight are skipped)
       const int ntiles = tmax - tmin + 1;
@@ -544,11 +613,19 @@ GJX_DEV void tiled_search_tile(const float* __restrict__ x, int64_t K, const uin
           for (int k = 0; k < ITEMS; ++k) q[k] = tile_q(nv[k], Eb[tsrc]);
           return true;
         }, [] {});
+        const uint64_t* cm[ITEMS];
+        bool mine[ITEMS];
+        int pos[ITEMS];
 #pragma unroll
         for (int k = 0; k < ITEMS; ++k) {
           const int kp = tile[k] - tmin;
-          if (kp >= idx && kp < idx + CH) anc[k] = (int32_t)((int64_t)tile[k] * TILE + rank_in_tile<TILE>(sh.cumL + (kp - idx) * TILE, Tr[k]));
+          mine[k] = kp >= idx && kp < idx + CH;
+          cm[k] = sh.cumL + (mine[k] ? (kp - idx) * TILE : 0);   // (a slot of another round is left out)
         }
+        rank_in_tiles_sorted<TILE, ITEMS>(cm, Tr, mine, pos);
+#pragma unroll
+        for (int k = 0; k < ITEMS; ++k)
+          if (mine[k]) anc[k] = (int32_t)((int64_t)tile[k] * TILE + pos[k]);
         idx = nidx;
       }
     }
