@@ -208,6 +208,8 @@ PROTOTYPES = {
     "gjx_weighted_histogram": (C.c_int, [vp, i64, i32, vp, i64, i64, f32, f32, i32, vp, vp, vp, C.c_size_t, vp]),
     "gjx_lineage_weights_workspace_bytes": (C.c_size_t, [i32, i64]),
     "gjx_lineage_weights": (C.c_int, [vp, i64, i32, i64, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "gjx_pareto_smooth_workspace_bytes": (C.c_size_t, [i64, i64]),
+    "gjx_pareto_smooth": (C.c_int, [vp, i64, i64, vp, vp, vp, C.c_size_t, vp]),
     "gjx_program_filter_source": (i64, [PP, i32, C.c_char_p, i64]),
     "gjx_program_filter_precompile": (C.c_int, [PP, i32]),
     "gjx_resample_indices_tiled": (C.c_int, [vp, i64, f64, i64, vp, vp, vp, vp, vp, C.c_size_t, vp]),

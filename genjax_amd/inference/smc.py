@@ -204,6 +204,13 @@ def _probabilities_of(trace: Trace, log_weights, addr, n_segments: int = 1, lead
     return mass[..., 1:ncat + 1]
 
 
+def pareto_k_threshold(K: int) -> float:
+    """min(1 - 1 / log10(K), 0.7): the k-hat below which K importance draws give a reliable estimate (the sample-size-dependent
+    threshold of the PSIS paper; 0.7 from K = 2200 up)"""
+    import math
+    return min(1.0 - 1.0 / math.log10(K), 0.7)
+
+
 class ParticleCollection:
     """Weighted particles (smc.py:76-109): a batched Trace + log-weights, all on the device."""
 
@@ -305,6 +312,28 @@ class ParticleCollection:
         """the posterior probabilities of a discrete site: f32[2] for a flip, f32[ncat] for a categorical (ValueError for any other)"""
         return _probabilities_of(self.particles, self.log_weights, addr)
 
+    def _pareto(self) -> dict:
+        """ONE gjx_pareto_smooth call for pareto_k() and pareto_smoothed(), kept"""
+        if getattr(self, "_psis", None) is None:
+            from .. import kernels
+            if self.K_total != len(self):
+                raise NotImplementedError("Pareto smoothing of a shard of a larger collection: the tail is that of the whole collection")
+            self._psis = kernels.pareto_smooth(self.log_weights)
+        return self._psis
+
+    def pareto_k(self):
+        """the Pareto k-hat diagnostic of the weights: the shape of the generalised Pareto distribution fitted to the largest
+        min(K / 5, 3 sqrt K) of them (gjx_pareto_smooth), a 0-d device tensor.  Below about 0.5 the estimates are reliable, above
+        ``inference.pareto_k_threshold(K)`` (0.7 for large K) they are not, whatever the effective sample size says; NaN where there
+        is no tail to fit (equal weights, fewer than 25 particles)."""
+        return self._pareto()["k"]
+
+    def pareto_smoothed(self) -> "ParticleCollection":
+        """the same particles under Pareto-smoothed weights: the largest weights replaced by the quantiles of the fitted distribution
+        (a small bias for a large cut in variance).  ``mean``, ``quantile``, ``effective_sample_size`` and the log-ML estimate of the
+        result run on the smoothed weights."""
+        return ParticleCollection(self.particles, self._pareto()["logw"], self.is_valid, None, self.offset, self.K_total)
+
     def lse_partials(self):
         """kernels.RunPartials of the producing run if still valid (for ``inference.pf.resample(..., collection=)``)"""
         p = self._partials
@@ -363,6 +392,24 @@ class TrialCollections:
     def probabilities(self, addr):
         """per-trial posterior probabilities of a discrete site: f32[n_trials][2 | ncat] (one call with n_segments = n_trials)"""
         return _probabilities_of(self.particles, self.log_weights, addr, self.n_trials, 1)
+
+    def _pareto(self) -> dict:
+        """ONE gjx_pareto_smooth call with n_segments = n_trials for pareto_k() and pareto_smoothed(), kept"""
+        if getattr(self, "_psis", None) is None:
+            from .. import kernels
+            p = kernels.pareto_smooth(self.log_weights, self.n_trials)
+            if self.n_trials == 1:                        # (the kernel wrapper drops a segment axis of 1)
+                p = dict(p, k=p["k"][None], sigma=p["sigma"][None], cutoff=p["cutoff"][None])
+            self._psis = p
+        return self._psis
+
+    def pareto_k(self):
+        """f32[n_trials]: the Pareto k-hat diagnostic of every trial's weights (``ParticleCollection.pareto_k`` per trial)"""
+        return self._pareto()["k"]
+
+    def pareto_smoothed(self) -> "TrialCollections":
+        """the same particles under every trial's Pareto-smoothed weights"""
+        return TrialCollections(self.particles, self._pareto()["logw"], self.n_trials, self.K)
 
     def get_log_marginal_likelihood_estimates(self):
         """f32[n_trials]: logsumexp(log_weights of the trial) - log K  (smc.py:96-97 per trial)"""

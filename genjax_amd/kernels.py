@@ -592,6 +592,55 @@ def lineage_weights(ancestors: torch.Tensor, logw=None, ws=None) -> dict:
     return {"w": w, "survivors": survivors, "stats": stats, "n_bad": n_bad}
 
 
+PSIS_MAX_SEGMENT = 1 << 22          # gjx_pareto_smooth: particles per segment at most
+
+
+def pareto_tail(n: int) -> int:
+    """M = min(floor(n / 5), ceil(3 sqrt(n))): the number of largest weights gjx_pareto_smooth fits and smooths in a segment of n"""
+    import math
+    return min(n // 5, math.isqrt(9 * n - 1) + 1) if n > 0 else 0
+
+
+def pareto_smooth(logw: torch.Tensor, n_segments: int = 1, ws=None, out=None) -> dict:
+    """gjx_pareto_smooth: log-weights f32[K] -> dict(logw f32[K], k f32[S], sigma f32[S], cutoff f32[S], tail int), the tensors on the
+    device, nothing read back.  Per segment a generalised Pareto distribution is fitted to the ``tail`` = min(n / 5, ceil(3 sqrt n))
+    largest weights: ``k`` is its shape, the k-hat diagnostic (below about 0.5 the weights are reliable, above 0.7 not; see
+    ``inference.pareto_k_threshold``), ``sigma`` its scale in units of the largest weight, ``cutoff`` the log-weight just below the
+    tail, and ``logw`` the log-weights with the tail replaced by the fitted quantiles (never above the largest raw weight; everything
+    else copied bit for bit).  Where there is no tail to fit (fewer than 25 particles, equal weights, no more than ``tail`` live
+    particles) ``k`` and ``sigma`` are NaN and ``logw`` is a copy.  ``n_segments`` > 1: that many consecutive segments, each on its
+    own; for one segment the segment axis is dropped.  ``out``: where the smoothed log-weights go (a contiguous f32[K]; ``logw`` itself
+    smooths in place).  A radix select, no sort of the particles; bit-reproducible."""
+    if logw.dtype != torch.float32:
+        raise ValueError("pareto_smooth: logw must be f32[K]")
+    K, S = int(logw.numel()), int(n_segments)
+    if S <= 0 or K <= 0 or K % S:
+        raise ValueError(f"pareto_smooth: {S} segments do not divide {K} particles")
+    if K // S > PSIS_MAX_SEGMENT:
+        raise ValueError(f"pareto_smooth: a segment takes at most 2^22 particles, not {K // S}")
+    logw = logw.reshape(-1)
+    if K > 1 and logw.stride(0) != 1:
+        logw = logw.contiguous()
+    dev = logw.device
+    need = load().gjx_pareto_smooth_workspace_bytes(K, S)
+    if need == 0:
+        raise ValueError(f"pareto_smooth: {S} segments are more than one call takes")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)        # the library zeroes what it needs
+    if out is None:
+        out = torch.empty(K, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.numel() != K or not out.is_contiguous() or out.device != dev:
+        raise ValueError("pareto_smooth: out must be a contiguous f32[K] on the device of logw")
+    fit = torch.empty((S, 4), dtype=torch.float32, device=dev)
+    check(load().gjx_pareto_smooth(_ptr(logw), K, S, _ptr(out), _ptr(fit), _ptr(ws), ws.numel(), _stream()), "gjx_pareto_smooth")
+    res = {"k": fit[:, 0], "sigma": fit[:, 1], "cutoff": fit[:, 2]}
+    if S == 1:
+        res = {k: v[0] for k, v in res.items()}
+    res["logw"] = out
+    res["tail"] = pareto_tail(K // S)
+    return res
+
+
 def resample_sorted_multinomial_tiled(logw: torch.Tensor, key, N: int | None = None, anc=None, cum=None, ws=None, want_q=False):
     """gjx_resample_sorted_multinomial_tiled: log-weights -> MULTINOMIAL ancestors (sorted uniforms from exponential spacings under
     `key`, tile-scaled fixed point), non-decreasing.  -> ancestors int32[N], or (ancestors, q, e) with want_q"""

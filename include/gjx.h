@@ -1004,6 +1004,47 @@ int gjx_lineage_weights(const int32_t* ancestors /* i32[T-1][anc_stride], may be
                         int32_t T, int64_t K, const float* logw /* f32[K] of the LAST step; NULL: equal weights */,
                         float* stats /* f32[4] as gjx_ess */, float* w /* f32[T][K] */, int32_t* survivors /* i32[T] */,
                         int32_t* n_bad /* i32[1] */, void* workspace, size_t workspace_bytes, void* stream);
+/* Pareto-smoothed importance weights and the k-hat diagnostic (PSIS: Vehtari, Simpson, Gelman, Yao, Gabry): whether the weights of a
+ * collection can be trusted, which the effective sample size does not tell.  A generalised Pareto distribution is fitted to the
+ * largest weights; its shape k-hat is reported (below about 0.5 reliable, above 0.7 not) and those weights are replaced by the
+ * fitted quantiles.  The reference has no counterpart: its users read raw log_weights.  Segments as in gjx_weighted_moments: S =
+ * n_segments consecutive segments of n = K / S particles, each treated on its own; a segment's outputs are those of a call on that
+ * segment alone.  Per segment:
+ * Order.  A particle whose log-weight is -inf or NaN is dead.  Particles are ordered ascending by the pair (key, particle index),
+ *   key the order-preserving key of gjx_weighted_quantiles of the log-weight (-0.0 folded onto +0.0) for a live particle and 0, below
+ *   every live key, for a dead one.  The pairs are distinct: the order is total, and it is NumPy's stable argsort of the keys.
+ * Tail.  M = min(floor(n / 5), ceil(3 sqrt(n))).  The tail is the last M particles of that order, the cutoff c the log-weight of
+ *   the particle just below it (NaN if that particle is dead; the largest particle's when M == 0), Mx the largest log-weight.
+ * No estimate: M < 5, or the segment has M or fewer live particles, or x at the quartile index below is not > 0 (equal weights fall
+ *   here: no tail to fit — "no weight, no estimate").  Then logw_out is a bit-for-bit copy of logw and fit = {NaN, NaN, c, M}.
+ * Fit (Zhang & Stephens 2009 with the priors of the PSIS paper), all in float64.  For the tail particle of rank i = 0 .. M-1
+ *   (ascending):  x_i = exp((double)lw_i - (double)Mx) - exp((double)c - (double)Mx).   m = 30 + floor(sqrt(M)),
+ *   x_q = x[floor(M / 4 + 0.5) - 1].   For j = 1 .. m:
+ *     b_j = (1 - sqrt(m / (j - 0.5))) / (3 x_q) + 1 / x_{M-1},   k_j = mean_i log1p(-b_j x_i),   L_j = M (log(-b_j / k_j) - k_j - 1)
+ *   w = softmax(L) (w_j = exp(L_j - max L) / sum over the finite L; a candidate whose L_j is not finite gets w_j = 0),
+ *   b = sum_j w_j b_j,   k0 = mean_i log1p(-b x_i),   sigma = -k0 / b,   k-hat = (M k0 + 5) / (M + 10).
+ * Smoothing.  p_i = (i + 0.5) / M;  q_i = sigma expm1(-k-hat log1p(-p_i)) / k-hat, or -sigma log1p(-p_i) when k-hat == 0.  The tail
+ *   particle of rank i receives logw_out = (float)(min(log(q_i + exp(c - Mx)), 0) + Mx), rounded to float once (a NaN stays a NaN):
+ *   never above the largest raw weight, and on the input's scale, so the log-ML estimate stays meaningful.  Every other particle,
+ *   dead ones and NaN included, is copied bit for bit.
+ *   logw_out  f32[K]; may be logw itself (in place)
+ *   fit       f32[S][4] = {(float)k-hat, (float)sigma, c, (float)M}; sigma is in units of the segment's largest weight
+ * Device work.  The M + 1 largest of n particles are found without a sort: a most-significant-digit radix select on the composite
+ * (key << ib) | index (ib the bits of n - 1), 11 bits per pass, at most 5 passes, finds the (M + 1)-th largest composite, a unique
+ * threshold.  Per pass one launch counts the digit (integer counts: an LDS histogram, then the block's non-zero bins into the
+ * workspace with integer atomics; the first pass also copies logw to logw_out) and one small launch picks the digit; once the
+ * chosen bin is taken whole the later passes return at once.  One launch compacts the M + 1 composites at or above the threshold
+ * into the workspace (slot order free); one block per segment sorts them in LDS; one block per (segment, candidate) evaluates L_j;
+ * one block per segment finishes the fit and scatters the M smoothed values.  Floating-point sums run in an order fixed by M: the
+ * outputs are bit-reproducible.  Plain launches on `stream`, nothing read back, no block waits for another, no particle-sized
+ * temporary beyond logw_out.  Tail indices come from the call's own compaction: in range by construction.
+ * GJX_EINVAL: a NULL logw, logw_out, fit or workspace; K <= 0, n_segments <= 0 or not dividing K; n_segments (30 + floor(sqrt(M)))
+ * >= 2^31.  GJX_EUNSUPPORTED: n > 2^22 (the filter kernels' own limit on K; it keeps M <= 6144, which one block sorts in LDS).
+ * GJX_EWORKSPACE: less than gjx_pareto_smooth_workspace_bytes(K, n_segments) (0 for arguments the call refuses).  The workspace
+ * needs no initialisation: the call zeroes what it needs on `stream`.  Nothing is launched on a refusal. */
+size_t gjx_pareto_smooth_workspace_bytes(int64_t K, int64_t n_segments);
+int gjx_pareto_smooth(const float* logw, int64_t K, int64_t n_segments, float* logw_out /* f32[K] */, float* fit /* f32[S][4] */,
+                      void* workspace, size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
