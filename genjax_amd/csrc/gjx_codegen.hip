@@ -2197,6 +2197,9 @@ void hmc_emit_element(Emit& o, const gjx_program* prog, const HmcPlan& hp, int j
         if (!ri.enode_dtab[k].empty()) e.da = ri.enode_dtab[k][i];
         const std::string gi = AD(i);
         auto add = [&](int to, const std::string& term) { if (live[to]) o.f("%s    %s += %s;\n", ind, AD(to).c_str(), term.c_str()); };
+        // gjx.h "zero adjoint": a node whose adjoint is exactly 0 contributes nothing to its operands (the interpreter skips it).  Where
+        // the local factor depends on values — it may be inf or NaN at a guarded point, 0 * inf = NaN — the term is a select on the adjoint
+        auto nz = [&](const std::string& term) { return "(" + gi + " == 0.0f ? 0.0f : " + term + ")"; };
         switch (e.op) {
           case GJX_E_VALUE: o.f("%s    %s[%d] += %s;\n", ind, acc, hp.sel_of_slot[expr_leaf_reg(g_expr_prog, q, ri, k, i, 0)], gi.c_str()); break;
           case GJX_E_LINV:
@@ -2207,17 +2210,18 @@ void hmc_emit_element(Emit& o, const gjx_program* prog, const HmcPlan& hp, int j
             break;
           case GJX_E_ADD: add(e.a, gi); add(e.b, gi); break;
           case GJX_E_SUB: add(e.a, gi); add(e.b, "-" + gi); break;
-          case GJX_E_MUL: add(e.a, gi + " * " + N(e.b)); add(e.b, gi + " * " + N(e.a)); break;
-          case GJX_E_DIV: add(e.a, gi + " * fast_rcp(" + N(e.b) + ")"); add(e.b, "-" + gi + " * " + N(i) + " * fast_rcp(" + N(e.b) + ")"); break;
+          case GJX_E_MUL: add(e.a, nz(gi + " * " + N(e.b))); add(e.b, nz(gi + " * " + N(e.a))); break;
+          case GJX_E_DIV: add(e.a, nz(gi + " * fast_rcp(" + N(e.b) + ")")); add(e.b, nz("-" + gi + " * " + N(i) + " * fast_rcp(" + N(e.b) + ")")); break;
           case GJX_E_MAX: add(e.a, N(e.a) + " >= " + N(e.b) + " ? " + gi + " : 0.0f"); add(e.b, N(e.a) + " >= " + N(e.b) + " ? 0.0f : " + gi); break;
           case GJX_E_MIN: add(e.a, N(e.a) + " <= " + N(e.b) + " ? " + gi + " : 0.0f"); add(e.b, N(e.a) + " <= " + N(e.b) + " ? 0.0f : " + gi); break;
           case GJX_E_WHERE: add(e.b, N(e.a) + " != 0.0f ? " + gi + " : 0.0f"); add(e.c, N(e.a) + " != 0.0f ? 0.0f : " + gi); break;
           case GJX_E_LINN: for (int t = 0; t < e.c; ++t) add(e.b + t, gi + " * TAB(" + toff(e.a, e.da) + " + " + std::to_string(1 + t) + ")"); break;
           case GJX_E_LSEN:
-            for (int t = 0; t < e.c; ++t) add(e.b + t, N(i) + " == -INFINITY ? 0.0f : " + gi + " * fast_exp(" + N(e.b + t) + " - " + N(i) + ")");
+            for (int t = 0; t < e.c; ++t) add(e.b + t, nz(N(i) + " == -INFINITY ? 0.0f : " + gi + " * fast_exp(" + N(e.b + t) + " - " + N(i) + ")"));
             break;
           case GJX_E_CONST: case GJX_E_GT: break;
-          default: add(e.a, gi + " * expr_unary_deriv(" + std::to_string(e.op) + ", " + N(e.a) + ", " + N(i) + ")"); break;
+          case GJX_E_NEG: add(e.a, "-" + gi); break;
+          default: add(e.a, nz(gi + " * expr_unary_deriv(" + std::to_string(e.op) + ", " + N(e.a) + ", " + N(i) + ")")); break;
         }
       }
       o.f("%s  }\n", ind);

@@ -421,14 +421,13 @@ def lower(outs: Sequence[tuple], leaf_place: Callable, push: Callable) -> tuple[
                     continue
             rest.append((m, w))
         lat.sort()
-        # runs of consecutive slots -> LINV (choices read straight from registers / rows); small gaps are bridged with zero weights
+        # runs of consecutive slots -> LINV (choices read straight from registers / rows).  A gap is never bridged with a zero weight:
+        # the device would read a row the expression did not name, and 0 * inf = NaN (include/gjx.h GJX_E_LINV)
         runs: list = []
         j = 0
         while j < len(lat):
             run = [lat[j]]
-            while j + 1 < len(lat) and 0 < lat[j + 1][0] - run[-1][0] <= 2 and (lat[j + 1][0] - run[0][0]) < 64:
-                for g in range(run[-1][0] + 1, lat[j + 1][0]):
-                    run.append((g, 0.0))
+            while j + 1 < len(lat) and lat[j + 1][0] - run[-1][0] == 1 and len(run) < 64:
                 run.append(lat[j + 1])
                 j += 1
             j += 1

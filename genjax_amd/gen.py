@@ -152,9 +152,21 @@ class Sym:
             return _eun("sqrt", self)
         if k == -1.0:
             return _eun("recip", self)
-        if k == 3.0:
-            return _ebin("mul", _eun("square", self), self)
-        return _eun("exp", _ebin("mul", _eun("log", self), k))
+        if k.is_integer():
+            # an integer power is defined on the whole line (jnp's integer_pow): repeated squaring from SQUARE and MUL, at most
+            # 2 log2|k| + 1 nodes, RECIP for a negative exponent; x ** 0 is the constant 1 (also at x = 0)
+            n = int(k) if k > 0 else -int(k)            # (abs is this module's expression function)
+            if n == 0:
+                return Expr([E.const(1.0)] * _to_expr(self).dim)
+            acc, base = None, self
+            while n:
+                if n & 1:
+                    acc = base if acc is None else _ebin("mul", base, acc)
+                n >>= 1
+                if n:
+                    base = _eun("square", base)
+            return _eun("recip", acc) if k < 0 else acc
+        return _eun("exp", _ebin("mul", _eun("log", self), k))      # non-integer: NaN on a negative base, as jnp.power
 
     # comparisons give 0 / 1 values (for where(...)); no gradient flows through them (jax.grad of a comparison)
     def __gt__(self, o): return _ebin("gt", self, o)

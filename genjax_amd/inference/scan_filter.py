@@ -259,8 +259,7 @@ class ScanBootstrapFilter:
         if c.get("sk") == sk and c.get("dk") != dk:
             fresh = self.step_programs(constraint, args)
             old = c["progs"]
-            if len(fresh) == len(old) and all(a.sites_bytes() == b_.sites_bytes() and a.tab.size == b_.tab.size and a.n_slots == b_.n_slots
-                                              for a, b_ in zip(fresh, old)):
+            if same_structure(fresh, old):
                 for a, b_ in zip(fresh, old):
                     b_.tab[:] = a.tab
                     b_.site_list, b_.modes, b_.filter_obs = a.site_list, a.modes, a.filter_obs
@@ -622,6 +621,15 @@ def _leaves(x):
             yield from _leaves(x[k])
     else:
         yield x
+
+
+def same_structure(fresh, old) -> bool:
+    """may the tables of the step programs `fresh` be copied into the cached programs `old` (same ids, same generated kernels)?  Only
+    if everything a kernel bakes in agrees: the site records AND the node blocks of the expression parameters
+    (PackedProgram.structure_bytes) — folding known values, where() on scanned arguments and constant folding turn DATA into node
+    ops, and the library keys its generated kernels per program id."""
+    return len(fresh) == len(old) and all(a.structure_bytes() == b_.structure_bytes() and a.tab.size == b_.tab.size and a.n_slots == b_.n_slots
+                                          for a, b_ in zip(fresh, old))
 
 
 def _run_keys(constraint, args, dev):

@@ -935,6 +935,18 @@ class PackedProgram:
     def sites_bytes(self) -> bytes:
         return bytes(self.c_sites)[: self.n_sites * C.sizeof(A.GjxSite)]
 
+    def structure_bytes(self) -> bytes:
+        """everything a generated kernel bakes in: the site records AND the node block tab[off : off + 6 n] of every GJX_P_EXPR
+        parameter (ops, operand indices, table offsets, strides).  Folding known values, where() on data and constant folding turn
+        data into nodes, so two programs may agree in sites_bytes(), table size and slot count and still need different kernels."""
+        parts = [self.sites_bytes()]
+        for j in range(self.n_sites):
+            for k in range(A.MAX_PARAMS):
+                cp = self.c_sites[j].p[k]
+                if cp.op == A.P_EXPR:
+                    parts.append(self.tab[cp.off:cp.off + A.EXPR_NODE_FLOATS * cp.n].tobytes())
+        return b"".join(parts)
+
     def c_program(self, device=None) -> A.GjxProgram:
         """Struct for a call.  With ``device`` (a torch device) the *_dev pointers are filled."""
         p = A.GjxProgram()

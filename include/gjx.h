@@ -130,7 +130,18 @@ enum {
  * tab[a + i da ...] and its slots from b + i db; LINN its [bias, weights] at tab[a + i da ...] — per-instance data (the covariates of a
  * regression with a nonlinear link, vmapped over the observations) and per-instance latents, with ONE node list for the plate.
  * Reverse mode (gjx_hmc, gjx_score_grad): the adjoint of the output flows back through the block to its VALUE leaves; CONST leaves,
- * comparisons and the condition of a WHERE carry no gradient (jax.grad of jnp.where / lax.select, comparisons). */
+ * comparisons and the condition of a WHERE carry no gradient (jax.grad of jnp.where / lax.select, comparisons).
+ * Rules every engine and the oracle follow:
+ *   ties and kinks: MAX and MIN send the gradient to a at a tie (+0 and -0 tie); abs'(0) = 0; GT passes no gradient; WHERE sends the
+ *     gradient to the selected branch only, whatever the other branch holds (inf, NaN).
+ *   zero adjoint: a node whose adjoint is exactly zero contributes nothing to its operands — where(x > 0, sqrt(x), 0) has gradient
+ *     0 at x = 0, not 0 * inf.  The interpreters skip such a node; generated reverse sweeps select on the adjoint.
+ *   integer powers are built by the host from SQUARE, MUL and RECIP (defined for a negative base); exp(k log x) only for non-integer k.
+ *   LINV reads exactly the c rows it names: the host never bridges a gap between named rows with a zero weight.  (This holds for
+ *     expression blocks; the closed GJX_P_AFFINE form over several sites still packs one dense weight row over slot .. slot + n - 1.)
+ *   domain: arguments and results in float32's normal range, |x| in [2^-126, 2^126] or exactly 0; beyond it the device's reciprocal
+ *     and logarithm flush (v_rcp_f32, v_log_f32).  SIN and COS are held to float64 for |x| <= 50 only: a float32 argument beyond
+ *     that carries an error of its own that moves the result by more than the tests' tolerance.  Overflow gives +-inf, 1 / +-0 = +-inf, log 0 = -inf, 0 / 0 = NaN, on every engine. */
 enum {
   GJX_E_CONST = 0,    /* tab[a + inst * da]                                                             */
   GJX_E_VALUE = 1,    /* choices[a + inst * da][i]                                                      */

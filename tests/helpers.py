@@ -535,3 +535,56 @@ def categorical_check(v, p):
     bad = [(int(c), int(cnt[c]), float(p[c])) for c in np.nonzero(ex > 1.0)[0]]
     bad += [(int(c), int(cnt[c]), 0.0) for c in np.nonzero((p == 0.0) & (cnt > 0))[0]]
     return float(ex.max()), bad
+
+
+# ---- the float64 grid harness of the expression tests (tests/test_gpu_tracer_surface.py, tests/test_gpu_expr_ops.py, tests/test_expr_ops_cpu.py):
+# host-made grids supplied as the values of constrained sites (no sampler), a float64 NumPy restatement of the per-site scores
+GRID_K = 4099                 # columns for scores: neither a multiple of the wave nor of the block
+GRID_N_GRAD = 384             # columns for gradients and HMC
+GRID_RT, GRID_AT = 2e-4, 2e-4           # scores; gradients rtol / atol 2e-3, engine against engine after one HMC move 3e-3
+HALF_LOG_2PI = 0.5 * np.log(2.0 * np.pi)
+
+
+def nlp(x, mu, sig):
+    """float64 log-density of normal(mu, sig) at x"""
+    x, mu, sig = np.asarray(x, np.float64), np.asarray(mu, np.float64), np.asarray(sig, np.float64)
+    return -0.5 * ((x - mu) / sig) ** 2 - np.log(sig) - HALF_LOG_2PI
+
+
+def grid_offsets(n, width=1.5):
+    """where an observation sits relative to its mean: a fixed pattern within +- width standard deviations"""
+    return width * np.sin(1.0 + 0.7 * np.arange(n))
+
+
+def well_conditioned(spec, vals32, edges=False):
+    """the float64 reference under inputs a few float32 ulps away moves by less than half the tolerance, at EVERY grid point.
+    ``edges``: the grid holds points whose reference is +-inf or NaN (an overflow, a pole, 0 / 0): there the reference under the
+    moved inputs must be the SAME infinity (or NaN); every other point is held to the bound as before"""
+    v = {k: x.astype(np.float64) for k, x in vals32.items()}
+    with np.errstate(all="ignore"):
+        s0 = np.stack(spec["scores"](v))
+        s1 = np.stack(spec["scores"]({k: x * (1.0 + 2e-6) for k, x in v.items()}))
+    if not edges:
+        assert not np.isnan(s0).any() and not np.isinf(s0).any()
+    for p, q in ((s0, s1), (s0.sum(0), s1.sum(0))):
+        fin = np.isfinite(p)
+        assert (np.isnan(p) == np.isnan(q)).all() and (p[np.isinf(p)] == q[np.isinf(p)]).all()
+        p, q = p[fin], q[fin]
+        assert (np.abs(q - p) < 0.5 * (GRID_AT + GRID_RT * np.abs(p))).all(), float((np.abs(q - p) / (GRID_AT + GRID_RT * np.abs(p))).max())
+    return s0
+
+
+def float32_range(want):
+    """a float64 score beyond the largest float32 is what the device can only return as -inf (the density of a value 1e30 standard
+    deviations out): the reference is compared as that infinity, every other value as it is"""
+    with np.errstate(invalid="ignore"):
+        big = np.abs(want) > float(np.finfo(np.float32).max)
+    return np.where(big, np.copysign(np.inf, want), want)
+
+
+def grid_rows(prog, spec, vals):
+    ch = np.zeros((prog.n_slots, next(iter(vals.values())).shape[1]), np.float32)
+    for addr, d in spec["sites"]:
+        if addr in vals and prog.slot_of.get(addr, -1) >= 0:
+            ch[prog.slot_of[addr]:prog.slot_of[addr] + d] = vals[addr]
+    return ch

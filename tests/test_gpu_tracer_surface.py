@@ -24,11 +24,8 @@ import genjax_amd as genjax               # noqa: E402
 from genjax_amd import C                  # noqa: E402
 from genjax_amd import _abi as A          # noqa: E402
 from genjax_amd.program import PackedProgram      # noqa: E402
-
-K = 4099
-N_GRAD = 384
-RT, AT = 2e-4, 2e-4
-HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+from helpers import GRID_AT as AT, GRID_K as K, GRID_N_GRAD as N_GRAD, GRID_RT as RT      # noqa: E402
+from helpers import float32_range as _float32_range, grid_offsets as _offsets, grid_rows as _rows, nlp, well_conditioned as _well_conditioned      # noqa: E402
 
 
 def _np(t):
@@ -39,17 +36,6 @@ def _np(t):
 def K_():
     from genjax_amd import kernels
     return kernels
-
-
-def nlp(x, mu, sig):
-    """float64 log-density of normal(mu, sig) at x"""
-    x, mu, sig = np.asarray(x, np.float64), np.asarray(mu, np.float64), np.asarray(sig, np.float64)
-    return -0.5 * ((x - mu) / sig) ** 2 - np.log(sig) - HALF_LOG_2PI
-
-
-def _offsets(n, width=1.5):
-    """where an observation sits relative to its mean: a fixed pattern within +- width standard deviations"""
-    return width * np.sin(1.0 + 0.7 * np.arange(n))
 
 
 # ---- the models: (the @gen function, its sites in order with their dims, the float64 restatement of the per-site scores, a grid) ----
@@ -152,32 +138,6 @@ SPECS["logsumexp"] = dict(model=lse_model, sites=[("a", 1), ("b", 1), ("x", 8), 
                           obs={"y": 0.3, "z": 0.9}, grad_grid=lambda n: _lse_grid(n, x_max=3.0, extreme=False))
 SPECS["reductions"] = dict(model=reduce_model, sites=[("x", 4), ("y", 1), ("z", 1)], grid=_reduce_grid, scores=_reduce_scores,
                            obs={"y": 2.0, "z": 0.8}, grad_grid=_reduce_grid)
-
-
-def _well_conditioned(spec, vals32):
-    """the float64 reference under inputs a few float32 ulps away moves by less than half the tolerance, at EVERY grid point"""
-    v = {k: x.astype(np.float64) for k, x in vals32.items()}
-    s0 = np.stack(spec["scores"](v))
-    s1 = np.stack(spec["scores"]({k: x * (1.0 + 2e-6) for k, x in v.items()}))
-    assert not np.isnan(s0).any() and not np.isinf(s0).any()
-    for p, q in ((s0, s1), (s0.sum(0), s1.sum(0))):
-        assert (np.abs(q - p) < 0.5 * (AT + RT * np.abs(p))).all(), float((np.abs(q - p) / (AT + RT * np.abs(p))).max())
-    return s0
-
-
-def _float32_range(want):
-    """a float64 score beyond the largest float32 is what the device can only return as -inf (the density of a value 1e30 standard
-    deviations out): the reference is compared as that infinity, every other value as it is"""
-    big = np.abs(want) > float(np.finfo(np.float32).max)
-    return np.where(big, np.copysign(np.inf, want), want)
-
-
-def _rows(prog, spec, vals):
-    ch = np.zeros((prog.n_slots, next(iter(vals.values())).shape[1]), np.float32)
-    for addr, d in spec["sites"]:
-        if addr in vals and prog.slot_of.get(addr, -1) >= 0:
-            ch[prog.slot_of[addr]:prog.slot_of[addr] + d] = vals[addr]
-    return ch
 
 
 @pytest.mark.parametrize("which", list(SPECS))
