@@ -202,6 +202,8 @@ PROTOTYPES = {
     "gjx_ess": (C.c_int, [vp, i64, vp, vp, C.c_size_t, vp]),
     "gjx_weighted_moments_workspace_bytes": (C.c_size_t, [i32, i64, i64, i32]),
     "gjx_weighted_moments": (C.c_int, [vp, i64, i32, vp, i64, i64, i32, vp, vp, vp, vp, C.c_size_t, vp]),
+    "gjx_weighted_cross_moments_workspace_bytes": (C.c_size_t, [i32, i32, i64]),
+    "gjx_weighted_cross_moments": (C.c_int, [vp, i64, i32, vp, i64, i32, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "gjx_weighted_quantiles_workspace_bytes": (C.c_size_t, [i32, i64, i64, i32]),
     "gjx_weighted_quantiles": (C.c_int, [vp, i64, i32, vp, i64, i64, vp, i32, vp, vp, vp, C.c_size_t, vp]),
     "gjx_weighted_histogram_workspace_bytes": (C.c_size_t, [i32, i64, i64, i32]),

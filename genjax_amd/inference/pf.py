@@ -207,6 +207,12 @@ class ParticleHistory(LineageSmoothing):
         """quantiles of x_t | y_{1:T} for every step: f32[T][dx][n_levels], one gjx_weighted_quantiles call per step"""
         return self._smoothed_quantiles(None, q)
 
+    def smoothed_pair_moments(self) -> dict:
+        """the lag-one smoothing expectations for t = 1 .. T-1: dict(mean f32[T-1][dx] = E[x_t], mean_prev f32[T-1][dx] = E[x_{t-1}],
+        cross f32[T-1][dx][dx] = Cov[x_t, x_{t-1}] (centred), ess f32[T-1]) given y_{1:T}: one gjx_weighted_cross_moments call per
+        pair, step t-1's stored particles read through the ancestors of step t.  At most 16 components."""
+        return self._smoothed_pair_moments(None)
+
 
 class BootstrapFilter:
     """SMC with the prior as proposal and systematic resampling before every propagate step.

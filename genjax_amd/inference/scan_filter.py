@@ -607,6 +607,14 @@ class ScanHistory(LineageSmoothing):
         gjx_weighted_quantiles call per step; every result is the value of a particle of that step that has a descendant"""
         return self._smoothed_quantiles(name, q)
 
+    def smoothed_pair_moments(self, name) -> dict:
+        """the lag-one smoothing expectations that EM's M-step needs, for t = 1 .. T-1: dict(mean f32[T-1][dim] = E[x_t], mean_prev
+        f32[T-1][dim] = E[x_{t-1}], cross f32[T-1][dim][dim] = Cov[x_t, x_{t-1}] (centred: E[x_t x_{t-1}^T] = cross + mean mean_prev^T),
+        ess f32[T-1]), all given y_{1:T}.  One gjx_weighted_cross_moments call per pair: the parents are read through the ancestors
+        where they lie (with resample-move: the moved carry at the child's index), nothing is gathered into a temporary.  At most 16
+        components; T == 1 gives empty outputs."""
+        return self._smoothed_pair_moments(name)
+
 
 def _name(addr):
     return addr[0] if isinstance(addr, tuple) and len(addr) == 2 and isinstance(addr[1], (int, np.integer)) else addr

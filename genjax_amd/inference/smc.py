@@ -283,6 +283,30 @@ class ParticleCollection:
             return torch.zeros((s.dim, s.dim), dtype=torch.float32, device=self.log_weights.device)
         return kernels.weighted_moments(tr.choices[slot:slot + s.dim], self.log_weights, "cov")["cov"]
 
+    def cross_covariance(self, addr_a, addr_b):
+        """f32[dim_a][dim_b]: the weighted covariance between the components of TWO sites, sum w (a - E a)(b - E b)^T (population
+        form), from one gjx_weighted_cross_moments call over their rows (no index: both sites of one particle).
+        ``cross_covariance(a, a)`` is ``covariance(a)`` up to rounding.  A site constrained to one shared value has no spread: zeros.
+        Trials (TrialCollections) and segments are out of scope: the call takes one collection."""
+        import torch
+        from .. import _abi as A
+        from .. import kernels
+        from ..core import key_of
+        tr = self.particles
+        sl = tr.prog.site_list
+        keys = [addr if addr in sl else key_of(addr) for addr in (addr_a, addr_b)]
+        for addr, k in zip((addr_a, addr_b), keys):
+            if k not in sl:
+                raise KeyError(addr)
+        sa, sb = sl[keys[0]], sl[keys[1]]
+        for addr, s in ((addr_a, sa), (addr_b, sb)):
+            if s.dim > A.MOMENTS_MAX_COV_ROWS:
+                raise ValueError(f"cross_covariance({addr!r}): the site has {s.dim} components, a side takes at most {A.MOMENTS_MAX_COV_ROWS}")
+        slot_a, slot_b = tr.prog.slot_of[sa.addr], tr.prog.slot_of[sb.addr]
+        if slot_a < 0 or slot_b < 0:                      # one shared value: no spread
+            return torch.zeros((sa.dim, sb.dim), dtype=torch.float32, device=self.log_weights.device)
+        return kernels.weighted_cross_moments(tr.choices[slot_a:slot_a + sa.dim], tr.choices[slot_b:slot_b + sb.dim], self.log_weights)["cross"]
+
     def quantile(self, addr, q):
         """the weighted quantile(s) of a site at the level(s) ``q`` in [0, 1] (NumPy's "inverted_cdf" under the self-normalised weights:
         always the value of a live particle; one gjx_weighted_quantiles call, a radix select — no sort): 0-d for a scalar site and a

@@ -49,6 +49,32 @@ class LineageSmoothing:
         self._lineage()
         return {"mean": m["mean"], want: m[want], "ess": m["stats"][:, 3]}
 
+    def _smoothed_pair_moments(self, name) -> dict:
+        """the lag-one pair (x_t, x_{t-1}) of every surviving path, t = 1 .. T-1, in one gjx_weighted_cross_moments call per pair.
+        x_t and x_{t-1} are the rows ``_smoothing_rows`` gives steps t and t-1 — the values ``paths`` gives a trajectory —, so the two
+        marginals of entry t-1 are ``smoothed_moments`` at t and t-1.  The pair stands under the weights of x_t's rows; where x_{t-1}'s
+        rows stand under the step before (an ordinary history: step t-1's own rows), they are read through that step's ancestors;
+        where both stand under one step (resample-move: the moved carry in the child's INPUT rows, at the child's index), there is
+        no index."""
+        from .. import kernels
+        lw = self._smoothing_logw()
+        T, dev = int(lw.shape[0]), lw.device
+        rows = [self._smoothing_rows(t, name) for t in range(T)]
+        d = int(rows[0][0].shape[0])
+        if T == 1:
+            self._lineage()
+            e = lambda *s: torch.empty((0,) + s, dtype=torch.float32, device=dev)
+            return {"mean": e(d), "mean_prev": e(d), "cross": e(d, d), "ess": e()}
+        anc = self._ancestor_table()
+        steps = []
+        for t in range(1, T):
+            (ra, ta), (rb, tb) = rows[t], rows[t - 1]
+            assert tb in (ta, ta - 1)
+            steps.append((ra, rb, None if tb == ta else anc[tb], ta))
+        m = kernels.weighted_cross_moments_steps(steps, lw)
+        self._lineage()
+        return {"mean": m["mean_a"], "mean_prev": m["mean_b"], "cross": m["cross"], "ess": m["stats"][:, 3]}
+
     def _smoothed_quantiles(self, name, q) -> torch.Tensor:
         from .. import kernels
         lw = self._smoothing_logw()

@@ -473,6 +473,108 @@ def weighted_moments_steps(steps, logw: torch.Tensor, want: str = "var") -> dict
     return {"stats": stats, "mean": mean, want: second}
 
 
+def _cross_rows(name: str, what: str, rows: torch.Tensor):
+    """one row set of weighted_cross_moments, checked as weighted_moments checks its rows -> rows [n][K], row stride, n, K"""
+    if rows.dim() == 1:
+        rows = rows.unsqueeze(0)
+    if rows.dim() != 2 or rows.dtype != torch.float32:
+        raise ValueError(f"{name}: {what} must be f32[n_rows][K]")
+    n, K = int(rows.shape[0]), int(rows.shape[1])
+    if K > 1 and rows.stride(1) != 1:
+        raise ValueError(f"{name}: the particles of a row of {what} must be contiguous (column stride 1)")
+    stride = int(rows.stride(0)) if n > 1 else K
+    if stride < K:
+        raise ValueError(f"{name}: {what} overlap (row stride < K)")
+    if n <= 0 or K <= 0:
+        raise ValueError(f"{name}: {what} are empty")
+    if n > A.MOMENTS_MAX_COV_ROWS:
+        raise ValueError(f"{name}: each side takes at most {A.MOMENTS_MAX_COV_ROWS} rows, not {n}")
+    return rows, stride, n, K
+
+
+def _cross_index(name: str, index, K: int, K_b: int, dev):
+    if index is None:
+        if K_b < K:
+            raise ValueError(f"{name}: without an index rows_b must have at least the {K} particles of rows_a, not {K_b}")
+        return None
+    if index.dtype != torch.int32 or index.dim() != 1 or int(index.numel()) != K or not index.is_contiguous() or index.device != dev:
+        raise ValueError(f"{name}: index must be a contiguous i32[K] on the device of the rows")
+    return index
+
+
+def weighted_cross_moments(rows_a: torch.Tensor, rows_b: torch.Tensor, logw=None, index=None, ws=None) -> dict:
+    """gjx_weighted_cross_moments: rows_a f32[n_a][K] and rows_b f32[n_b][K_b] (views are fine as long as their column stride is 1, at
+    most 16 rows each), log-weights f32[K] (None: equal weights) and index i32[K] (None: the identity, K_b >= K) -> dict(stats f32[4]
+    = {max, sum e, sum e^2, ESS}, mean_a f32[n_a], mean_b f32[n_b], cross f32[n_a][n_b], n_bad i32[1]), all on the device, nothing
+    read back.  Particle i is the pair (rows_a[:, i], rows_b[:, index[i]]); cross is the centred population cross-covariance
+    sum w (a - mean_a)(b - mean_b)^T under the self-normalised weights (the raw moment is cross + mean_a mean_b^T); dead particles
+    (weight -inf / NaN) are left out.  n_bad counts the live particles whose index is outside [0, K_b): they are left out too, and
+    the index is never used as an address.  Two launches, bit-reproducible."""
+    name = "weighted_cross_moments"
+    rows_a, stride_a, n_a, K = _cross_rows(name, "rows_a", rows_a)
+    rows_b, stride_b, n_b, K_b = _cross_rows(name, "rows_b", rows_b)
+    dev = rows_a.device
+    if rows_b.device != dev:
+        raise ValueError(f"{name}: rows_a and rows_b must be on one device")
+    if logw is not None:
+        if logw.dtype != torch.float32 or logw.numel() != K:
+            raise ValueError(f"{name}: logw must be f32[K]")
+        logw = logw.reshape(-1)
+        if K > 1 and logw.stride(0) != 1:
+            logw = logw.contiguous()
+    index = _cross_index(name, index, K, K_b, dev)
+    need = load().gjx_weighted_cross_moments_workspace_bytes(n_a, n_b, K)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)        # partials only: needs no initialisation
+    stats = torch.empty(4, dtype=torch.float32, device=dev)
+    mean_a = torch.empty(n_a, dtype=torch.float32, device=dev)
+    mean_b = torch.empty(n_b, dtype=torch.float32, device=dev)
+    cross = torch.empty((n_a, n_b), dtype=torch.float32, device=dev)
+    n_bad = torch.empty(1, dtype=torch.int32, device=dev)
+    check(load().gjx_weighted_cross_moments(_ptr(rows_a), stride_a, n_a, _ptr(rows_b), stride_b, n_b, K_b, _ptr(index), _ptr(logw), K,
+                                            _ptr(stats), _ptr(mean_a), _ptr(mean_b), _ptr(cross), _ptr(n_bad), _ptr(ws), ws.numel(),
+                                            _stream()), "gjx_weighted_cross_moments")
+    return {"stats": stats, "mean_a": mean_a, "mean_b": mean_b, "cross": cross, "n_bad": n_bad}
+
+
+def weighted_cross_moments_steps(steps, logw: torch.Tensor) -> dict:
+    """gjx_weighted_cross_moments once per pair of steps of a history, into one set of outputs: ``steps`` is a sequence of T tuples
+    (rows_a f32[n_a][K], rows_b f32[n_b][K_b] — views of one shape each, column stride 1 —, index i32[K] or None, the row of ``logw``
+    f32[n][K] the pair stands under) -> dict(stats f32[T][4], mean_a f32[T][n_a], mean_b f32[T][n_b], cross f32[T][n_a][n_b], n_bad
+    i32[T]).  Entry t is bitwise ``weighted_cross_moments(rows_a, rows_b, logw[row], index)``: the same library call on the same
+    arguments; outputs and workspace are allocated once."""
+    name = "weighted_cross_moments_steps"
+    T = len(steps)
+    if T == 0:
+        raise ValueError(f"{name}: no step")
+    _, _, n_a, K = _cross_rows(name, "rows_a", steps[0][0])
+    _, _, n_b, K_b = _cross_rows(name, "rows_b", steps[0][1])
+    if logw.dim() != 2 or logw.dtype != torch.float32 or int(logw.shape[1]) != K or not logw.is_contiguous():
+        raise ValueError(f"{name}: logw must be a contiguous f32[n][K]")
+    dev = logw.device
+    ws = torch.empty(load().gjx_weighted_cross_moments_workspace_bytes(n_a, n_b, K), dtype=torch.uint8, device=dev)
+    stats = torch.empty((T, 4), dtype=torch.float32, device=dev)
+    mean_a = torch.empty((T, n_a), dtype=torch.float32, device=dev)
+    mean_b = torch.empty((T, n_b), dtype=torch.float32, device=dev)
+    cross = torch.empty((T, n_a, n_b), dtype=torch.float32, device=dev)
+    n_bad = torch.empty(T, dtype=torch.int32, device=dev)
+    call, st, p_ws, n_ws = load().gjx_weighted_cross_moments, _stream(), _ptr(ws), ws.numel()
+    p_lw, p_stats, p_a, p_b, p_cross, p_bad = (t.data_ptr() for t in (logw, stats, mean_a, mean_b, cross, n_bad))
+    for t, (ra, rb, index, tw) in enumerate(steps):
+        for rows, shape in ((ra, (n_a, K)), (rb, (n_b, K_b))):
+            if rows.dtype != torch.float32 or tuple(rows.shape) != shape or (shape[1] > 1 and rows.stride(1) != 1) or rows.device != dev:
+                raise ValueError(f"{name}: every step's rows must be f32 views of one shape with column stride 1")
+        stride_a, stride_b = int(ra.stride(0)) if n_a > 1 else K, int(rb.stride(0)) if n_b > 1 else K_b
+        if stride_a < K or stride_b < K_b or not 0 <= int(tw) < int(logw.shape[0]):
+            raise ValueError(f"{name}: rows overlap (row stride < K), or a weight row outside logw")
+        index = _cross_index(name, index, K, K_b, dev)
+        check(call(C.c_void_p(ra.data_ptr()), stride_a, n_a, C.c_void_p(rb.data_ptr()), stride_b, n_b, K_b, _ptr(index),
+                   C.c_void_p(p_lw + 4 * K * int(tw)), K, C.c_void_p(p_stats + 16 * t), C.c_void_p(p_a + 4 * n_a * t),
+                   C.c_void_p(p_b + 4 * n_b * t), C.c_void_p(p_cross + 4 * n_a * n_b * t), C.c_void_p(p_bad + 4 * t), p_ws, n_ws, st),
+              "gjx_weighted_cross_moments")
+    return {"stats": stats, "mean_a": mean_a, "mean_b": mean_b, "cross": cross, "n_bad": n_bad}
+
+
 def _weighted_rows(name: str, rows: torch.Tensor, logw, n_segments):
     """the arguments gjx_weighted_quantiles / gjx_weighted_histogram share with weighted_moments, checked the same way
     -> rows [n_rows][K], row stride, n_rows, K, logw, S"""

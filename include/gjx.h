@@ -937,6 +937,39 @@ enum { GJX_MOMENTS_MEAN = 0, GJX_MOMENTS_VAR = 1, GJX_MOMENTS_COV = 2 };
 size_t gjx_weighted_moments_workspace_bytes(int32_t n_rows, int64_t K, int64_t n_segments, int32_t want);
 int gjx_weighted_moments(const float* rows, int64_t row_stride, int32_t n_rows, const float* logw, int64_t K, int64_t n_segments,
                          int32_t want, float* stats, float* mean, float* second, void* workspace, size_t workspace_bytes, void* stream);
+/* Weighted cross-moments of PAIRS of particles: the covariance between two sites of a collection, and — with an index — between
+ * every particle and its parent, the lag-one smoothing expectation E[x_t x_{t-1}^T | y_{1:T}] that EM's M-step for a transition
+ * matrix needs (rows_a: step t, rows_b: step t-1, index: ancestors[t-1], logw: the log of step t's descendant weights,
+ * gjx_lineage_weights).  The reference has no counterpart: its traces carry whole trajectories.
+ *   rows_a  SoA f32[n_a][stride_a], stride_a >= K;   rows_b  SoA f32[n_b][stride_b], stride_b >= K_b
+ *   index   i32[K], or NULL for the identity (K_b >= K is then required);   logw  f32[K], or NULL for equal weights
+ * Particle i is the pair (a_i, b_i) = (rows_a[:, i], rows_b[:, index[i]]) under the self-normalised weight w_i ~ exp(logw_i); a
+ * particle whose weight is -inf or NaN is dead and left out whatever its values and its index, as in gjx_weighted_moments.
+ *   stats   f32[4] = {max, sum e, sum e^2, ESS} — bitwise what gjx_weighted_moments writes for the same weights
+ *   mean_a  f32[n_a] = sum w a;   mean_b  f32[n_b] = sum w b
+ *   cross   f32[n_a][n_b] = sum w (a - mean_a)(b - mean_b)^T, the centred POPULATION form; the raw moment is cross + mean_a mean_b^T
+ *   n_bad   i32[1]: the live particles whose index[i] is outside [0, K_b).  Such a particle is made dead before anything is summed
+ *           (stats are those of the rest), and its index is never used as an address: one compare stands in front of the gather.
+ *           Zeroed by the call on `stream`.
+ * A collection without a live particle: stats {-inf, 0, 0, 0}, NaN means and cross-moments.
+ * The scheme and the numerics of gjx_weighted_moments(GJX_MOMENTS_COV): one block per 1024-particle tile gathers the n_b parent
+ * values of its LIVE particles only (a coalesced lineage: almost none; resampled ancestors are non-decreasing, so a live wave
+ * touches few cache lines), keeps them in registers centred on the tile's mean, and streams the a rows through once, centred the
+ * same way; one block per a row merges the tiles pairwise (Chan, Golub and LeVeque) in an order that depends on K alone.  Two
+ * launches and a 4-byte memset; no float atomics (the only atomic is the integer n_bad, one per block with a non-zero count), no
+ * block waits for another: the outputs are bit-reproducible.
+ * Traffic: 4 B per particle for the weights, 4 B for the index, 4 n_a B for a, each read once, and 4 n_b B gathered per LIVE
+ * particle; nothing particle-sized is written.
+ * GJX_EINVAL: a NULL rows_a, rows_b, stats, mean_a, mean_b, cross, n_bad or workspace; n_a, n_b, K or K_b <= 0; stride_a < K,
+ * stride_b < K_b; K_b < K with a NULL index; K_b >= 2^31 with an index.  GJX_EUNSUPPORTED: n_a or n_b > GJX_MOMENTS_MAX_COV_ROWS.
+ * GJX_EWORKSPACE: less than gjx_weighted_cross_moments_workspace_bytes(n_a, n_b, K) (0 for arguments the call refuses); the
+ * workspace needs no initialisation.  Nothing is launched on a refusal. */
+size_t gjx_weighted_cross_moments_workspace_bytes(int32_t n_a, int32_t n_b, int64_t K);
+int gjx_weighted_cross_moments(const float* rows_a, int64_t stride_a, int32_t n_a, const float* rows_b, int64_t stride_b, int32_t n_b,
+                               int64_t K_b, const int32_t* index /* i32[K] or NULL */, const float* logw /* f32[K] or NULL */,
+                               int64_t K, float* stats /* f32[4] */, float* mean_a /* f32[n_a] */, float* mean_b /* f32[n_b] */,
+                               float* cross /* f32[n_a][n_b] */, int32_t* n_bad /* i32[1] */, void* workspace, size_t workspace_bytes,
+                               void* stream);
 /* Weighted quantiles and histograms of a particle collection: the median, a credible interval, the marginal of a site, the posterior
  * probabilities of a discrete site.  The reference has no counterpart: its users write jnp.quantile on resampled particles.  rows,
  * row_stride, logw (NULL: equal weights), K and n_segments are those of gjx_weighted_moments, so the three calls compose.
