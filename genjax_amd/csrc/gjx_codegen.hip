@@ -744,13 +744,13 @@ std::vector<char> emit_expr_nodes(Emit& o, const gjx_program* prog, const gjx_pa
         for (int t = 0; t < e.c; ++t) r = "fmaf(" + T(e.a, e.da, 1 + t) + ", " + N(e.b + t) + ", " + r + ")";
         break;
       }
-      case GJX_E_LSEN: {      // the maximum (an fmaxf chain), the sum of exp(x - m), m + log(sum); every operand -inf: -inf
+      case GJX_E_LSEN: {      // the maximum (an fmaxf chain), the sum of exp(x - m), m + log(sum); a maximum of -inf or +inf is the result
         const std::string m = N(i) + "_m";
         std::string mx = N(e.b), sum;
         for (int t = 1; t < e.c; ++t) mx = "fmaxf(" + mx + ", " + N(e.b + t) + ")";
         for (int t = 0; t < e.c; ++t) sum += (t ? " + " : "") + ("fast_exp(" + N(e.b + t) + " - " + m + ")");
         o.f("%sconst float %s = %s;\n", ind, m.c_str(), mx.c_str());
-        r = m + " == -INFINITY ? " + m + " : " + m + " + fast_log(" + sum + ")";
+        r = "fabsf(" + m + ") == INFINITY ? " + m + " : " + m + " + fast_log(" + sum + ")";
         break;
       }
       default: r = "expr_unary(" + std::to_string(e.op) + ", " + A + ")"; break;

@@ -495,12 +495,12 @@ GJX_DEV void expr_forward(const gjx_param& p, const float* __restrict__ tab, Val
       case GJX_E_WHERE: r = ev[a] != 0.0f ? ev[b] : ev[c]; break;
       case GJX_E_LINV: { r = tab[a]; for (int e = 0; e < c; ++e) r = fmaf(tab[a + 1 + e], val(b + e), r); break; }
       case GJX_E_LINN: { r = tab[a]; for (int e = 0; e < c; ++e) r = fmaf(tab[a + 1 + e], ev[b + e], r); break; }
-      case GJX_E_LSEN: {      // the maximum first; every operand -inf: -inf, not NaN
+      case GJX_E_LSEN: {      // the maximum first; a maximum of -inf (every operand -inf) or +inf (an overflowed operand) IS the result, not NaN
         float m = ev[b];
         for (int e = 1; e < c; ++e) m = fmaxf(m, ev[b + e]);
         float s = 0.0f;
         for (int e = 0; e < c; ++e) s += fast_exp(ev[b + e] - m);
-        r = m == -INFINITY ? m : m + fast_log(s);
+        r = fabsf(m) == INFINITY ? m : m + fast_log(s);
         break;
       }
       default: r = expr_unary(op, ev[a]); break;

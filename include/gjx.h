@@ -159,11 +159,17 @@ enum {
   GJX_E_LINV = 23,    /* tab[a] + sum_{e < c} tab[a + 1 + e] * choices[b + e][i]: bias and weights contiguous in the table */
   GJX_E_LINN = 24,    /* tab[a] + sum_{e < c} tab[a + 1 + e] * node (b + e)                              */
   GJX_E_ERF = 25,     /* erf(node a)          gradient 2/sqrt(pi) exp(-a^2); any real a                  */
-  GJX_E_ERFC = 26,    /* 1 - erf(node a)      gradient -2/sqrt(pi) exp(-a^2); any real a                 */
-  GJX_E_LGAMMA = 27,  /* log|Gamma(node a)|   gradient digamma(a) (a < 0: by reflection); a not 0, -1, -2, ... */
-  GJX_E_EXPM1 = 28,   /* exp(node a) - 1      gradient exp(a), accurate near 0; any real a               */
-  GJX_E_LSEN = 29,    /* log sum_{e < c} exp(node (b + e)), 1 <= c <= 64, a unused; -inf if every operand is -inf;
-                         gradient to node (b + e): exp(node (b + e) - result), 0 where the result is -inf */
+  GJX_E_ERFC = 26,    /* erfc(node a), the complementary error function itself (erfcf on the device, erfc in the oracle), NOT formed as
+                         1 - erf: relative accuracy down to float32's smallest normal, erfc(9.19) = 1.2e-38; gradient -2/sqrt(pi) exp(-a^2) */
+  GJX_E_LGAMMA = 27,  /* log|Gamma(node a)|   gradient digamma(a) (a <= 0: by reflection, psi(a) = psi(1 - a) - pi / tan(pi a)).  +inf at the
+                         poles 0, -1, -2, ... — every float32 below -2^23 is one; the gradient there is +-inf or NaN, never a finite number */
+  GJX_E_EXPM1 = 28,   /* expm1(node a): relative accuracy near 0 (not exp(a) - 1), -1 below -17, +inf above 88.72; gradient exp(a) */
+  GJX_E_LSEN = 29,    /* log sum_{e < c} exp(node (b + e)), 1 <= c <= 64, a unused.  The maximum m of the operands is taken out first:
+                         m + log sum exp(node - m).  A maximum that is not finite IS the result: -inf when every operand is -inf, +inf
+                         when an operand overflowed to +inf (exp(a * a) at a = 10), as NumPy and scipy give — not exp(inf - inf) = NaN.
+                         Gradient to node (b + e): exp(node (b + e) - result): ties at the maximum share it evenly (unlike MAX), an
+                         operand 104 nats behind gets exactly 0; nothing flows where the result is -inf or the adjoint is zero.  Where
+                         the result is +inf the gradient is not defined (NaN to the operand at +inf) and no engine is held to it */
   GJX_E_OP_MAX = 30
 };
 #define GJX_EXPR_MAX_NODES 96

@@ -107,6 +107,12 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _check(rc, what):
+    """a refused call (GJX_EINVAL: a malformed program, an expression node op the oracle does not know) is an error, never a result"""
+    if rc != 0:
+        raise ValueError(f"{what}: the oracle refused the program (status {rc})")
+
+
 def threefry2x32(k0, k1, c0, c1):
     out = np.zeros(2, np.uint32)
     lib().gjxo_threefry2x32(k0, k1, c0, c1, _p(out))
@@ -154,7 +160,7 @@ def run_program(prog: PackedProgram, key, K, offset=0, choices=None, logw_in=Non
     finally:
         if want_margin:
             lib().gjxo_set_margin_buffer(None, 0)
-    assert rc == 0, rc
+    _check(rc, "gjxo_run_program")
     out = dict(choices=ch, score=score, weight=weight, logw=logw, lse=lse)
     if margin is not None:
         out["margin"] = margin
@@ -310,7 +316,7 @@ def score_grad(prog: PackedProgram, choices):
     score = np.zeros(n, np.float32)
     grad = np.zeros_like(ch)
     cp = prog.c_program(None)
-    lib().gjxo_score_grad(C.byref(cp), n, _p(ch), _p(score), _p(grad))
+    _check(lib().gjxo_score_grad(C.byref(cp), n, _p(ch), _p(score), _p(grad)), "gjxo_score_grad")
     return score, grad
 
 
@@ -330,11 +336,12 @@ def hmc(prog: PackedProgram, key, choices, eps, L, stale=False, accept=False, of
     cp = prog.c_program(None)
     lib().gjxo_set_margin_buffer(_p(margin), n)
     try:
-        lib().gjxo_hmc(C.byref(cp), key[0], key[1], n, int(offset), float(eps), int(L), int(stale), int(accept),
-                       _p(ch), _p(score), _p(alpha), _p(acc))
+        rc = lib().gjxo_hmc(C.byref(cp), key[0], key[1], n, int(offset), float(eps), int(L), int(stale), int(accept),
+                            _p(ch), _p(score), _p(alpha), _p(acc))
     finally:
         lib().gjxo_set_margin_buffer(None, 0)
         lib().gjxo_set_momenta_buffer(None, 0)
+    _check(rc, "gjxo_hmc")
     out = dict(choices=ch, score=score, alpha=alpha, accepted=acc, margin=margin)
     if want_momenta:
         out["momenta"] = mom

@@ -323,8 +323,20 @@ static double expr_unary_d(int op, double x) {
     case GJX_E_SIN: return sin(x);
     case GJX_E_COS: return cos(x);
     case GJX_E_LOG1P: return log1p(x);
-    default: return 1.0 / x; /* GJX_E_RECIP */
+    case GJX_E_RECIP: return 1.0 / x;
+    case GJX_E_ERF: return erf(x);
+    case GJX_E_ERFC: return erfc(x);
+    case GJX_E_LGAMMA: return lgamma(x);   /* log |Gamma(x)|; +inf at 0, -1, -2, ... */
+    case GJX_E_EXPM1: return expm1(x);
+    default: return NAN;                   /* (expr_ops_known refuses the program before any node is evaluated) */
   }
+}
+static double digamma_d(double x);
+/* digamma on the whole line: at x <= 0 by reflection, psi(x) = psi(1 - x) - pi / tan(pi x), the argument of tan reduced to [-1/2, 1/2]
+ * (exact in double); the poles 0, -1, -2, ... give +-inf */
+static double digamma_real_d(double x) {
+  if (x > 0.0) return digamma_d(x);
+  return digamma_d(1.0 - x) - 3.14159265358979323846 / tan(3.14159265358979323846 * (x - rint(x)));
 }
 static double expr_unary_deriv_d(int op, double x, double y) {
   switch (op) {
@@ -340,8 +352,29 @@ static double expr_unary_deriv_d(int op, double x, double y) {
     case GJX_E_SIN: return cos(x);
     case GJX_E_COS: return -sin(x);
     case GJX_E_LOG1P: return 1.0 / (1.0 + x);
-    default: return -y * y; /* GJX_E_RECIP */
+    case GJX_E_RECIP: return -y * y;
+    case GJX_E_ERF: return 1.1283791670955126 * exp(-x * x);      /* 2 / sqrt(pi) */
+    case GJX_E_ERFC: return -1.1283791670955126 * exp(-x * x);
+    case GJX_E_LGAMMA: return digamma_real_d(x);
+    case GJX_E_EXPM1: return exp(x);
+    default: return NAN;
   }
+}
+/* every node op of every expression block is one this file evaluates: an op it does not know is GJX_EINVAL at the entry points
+ * (gjxo_run_program, gjxo_score_grad, gjxo_hmc), never a silent stand-in */
+static int expr_ops_known(const gjx_program* prog) {
+  for (int j = 0; j < prog->n_sites; ++j)
+    for (int k = 0; k < GJX_MAX_PARAMS; ++k) {
+      const gjx_param* p = &prog->sites[j].p[k];
+      if (p->op != GJX_P_EXPR) continue;
+      if (p->n < 1 || p->n > GJX_EXPR_MAX_NODES) return 0;
+      for (int i = 0; i < p->n; ++i) {
+        const int op = (int)prog->tab[p->off + GJX_EXPR_NODE_FLOATS * i];
+        if (op < 0 || op >= GJX_E_OP_MAX) return 0;
+        if (op == GJX_E_LSEN) { const int c = (int)prog->tab[p->off + GJX_EXPR_NODE_FLOATS * i + 3]; if (c < 1 || c > 64) return 0; }
+      }
+    }
+  return 1;
 }
 static void expr_forward(const gjx_param* p, const float* tab, const float* vals, float* ev) {
   const float* nd = tab + p->off;
@@ -364,6 +397,13 @@ static void expr_forward(const gjx_param* p, const float* tab, const float* vals
       case GJX_E_WHERE: r = ev[a] != 0.0f ? ev[b] : ev[c]; break;
       case GJX_E_LINV: r = tab[a]; for (int e = 0; e < c; ++e) r += (double)tab[a + 1 + e] * vals[b + e]; break;
       case GJX_E_LINN: r = tab[a]; for (int e = 0; e < c; ++e) r += (double)tab[a + 1 + e] * ev[b + e]; break;
+      case GJX_E_LSEN: {   /* the maximum first; a maximum of -inf (every operand -inf) or of +inf (an overflowed operand) IS the result */
+        double m = ev[b], s = 0.0;
+        for (int e = 1; e < c; ++e) m = fmax(m, ev[b + e]);
+        for (int e = 0; e < c; ++e) s += exp((double)ev[b + e] - m);
+        r = isinf(m) ? m : m + log(s);
+        break;
+      }
       default: r = expr_unary_d(op, ev[a]); break;
     }
     ev[i] = (float)r;
@@ -397,6 +437,7 @@ static void expr_backward(const gjx_param* p, int d, float g, const float* tab, 
       case GJX_E_WHERE: if (ev[a] != 0.0f) ad[b] += gi; else ad[c] += gi; break;
       case GJX_E_LINV: for (int e = 0; e < c; ++e) grad[b + e] += (float)(gi * tab[a + 1 + e]); break;
       case GJX_E_LINN: for (int e = 0; e < c; ++e) ad[b + e] += gi * tab[a + 1 + e]; break;
+      case GJX_E_LSEN: if (ev[i] != -INFINITY) for (int e = 0; e < c; ++e) ad[b + e] += gi * exp((double)ev[b + e] - ev[i]); break;
       default: ad[a] += gi * expr_unary_deriv_d(op, ev[a], ev[i]); break;
     }
   }
@@ -1113,7 +1154,7 @@ int gjxo_run_program(const gjx_program* prog, uint32_t key0, uint32_t key1, int6
                      int64_t particle_offset, float* choices, float* score, float* weight,
                      float* logw, const float* logw_in, const float* sub, float* site_scores,
                      float* lse, int64_t K_total) {
-  if (!prog || K < 0) return GJX_EINVAL;
+  if (!prog || K < 0 || !expr_ops_known(prog)) return GJX_EINVAL;
   const okey key = {key0, key1};
   const int ns = prog->n_slots;
 #pragma omp parallel
@@ -1826,6 +1867,7 @@ static float score_and_grad(const gjx_program* prog, const float* vals, float* g
 
 int gjxo_score_grad(const gjx_program* prog, int64_t n, const float* choices, float* score,
                     float* grad) {
+  if (!prog || !expr_ops_known(prog)) return GJX_EINVAL;
   const int ns = prog->n_slots;
   char* sel = (char*)calloc((size_t)ns + 1, 1);
   for (int j = 0; j < prog->n_sites; ++j)
@@ -1854,6 +1896,7 @@ int gjxo_score_grad(const gjx_program* prog, int64_t n, const float* choices, fl
 int gjxo_hmc(const gjx_program* prog, uint32_t key0, uint32_t key1, int64_t n, int64_t chain_offset,
              float eps, int32_t L, int32_t stale_grad_compat, int32_t accept, float* choices,
              float* score, float* alpha, float* accepted) {
+  if (!prog || !expr_ops_known(prog)) return GJX_EINVAL;
   const int ns = prog->n_slots;
   const okey key = {key0, key1};
   int* selslot = (int*)malloc(sizeof(int) * (size_t)(ns + 1));

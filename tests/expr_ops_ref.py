@@ -1,5 +1,6 @@
-"""The 25 older expression node ops (include/gjx.h GJX_E_CONST .. GJX_E_LINN) at their edges: the programs, their grids and a
-float64 NumPy restatement, shared by tests/test_gpu_expr_ops.py (generated kernels, site interpreter) and tests/test_expr_ops_cpu.py
+"""The expression node ops (include/gjx.h GJX_E_CONST .. GJX_E_LSEN) at their edges — the 25 older ones in programs 1 to 5, erf, erfc,
+lgamma, expm1, log-sum-exp and the reductions in programs 6 to 8: the programs, their grids and a
+float64 NumPy / scipy.special restatement, shared by tests/test_gpu_expr_ops.py (generated kernels, site interpreter) and tests/test_expr_ops_cpu.py
 (the CPU oracle, expr.evaluate).
 
 A program is a list of scalar latents a ~ normal(0, sd) (or one 64-vector) and a list of OP SITES, one per op and edge family:
@@ -377,6 +378,271 @@ LIN_SITES += [
 LIN_OPS = [A.E_LINV, A.E_LINN, A.E_VALUE]
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 6. the special functions: erf, erfc, lgamma, expm1 as general nodes, each as a mean (absolute error) and as a scale (relative error).
+#    The float64 side is scipy.special / np.expm1.  Two lgamma edges are REACHED EXACTLY, none is masked:
+#      * close approaches to the poles: lgamma(u - k), k = 0 .. 4, over a latent u that is a multiple of 2^-20 (2^-m, 4 <= m <= 20, among
+#        them): u - k is exact in float32 and the reference is conditioned in u (a relative move of -k + 2^-20 itself would move the
+#        distance to the pole by twice its size)
+#      * the poles -1 .. -4 and a negative beyond 2^23 (every float32 there is an integer): u = 0 in some columns — 0 stays 0 under the
+#        conditioning check's relative move, a pole written as a latent -1 would leave the pole.  The far one sits in the unselected
+#        branch's place of a WHERE decided by u > 0
+# ---------------------------------------------------------------------------------------------------------------------------------
+import scipy.special as _sp           # noqa: E402
+
+TINY32, MAX32 = float(np.finfo(F32).tiny), float(np.finfo(F32).max)
+
+
+def _last_f32(ok, lo, hi):
+    """the largest float32 x in [lo, hi] with ok(float64(x)) (ok holds at lo, fails at hi, changes once), by bisection on float64"""
+    lo, hi = float(F32(lo)), float(F32(hi))
+    assert ok(lo) and not ok(hi)
+    while float(F32(0.5 * (lo + hi))) not in (lo, hi):
+        mid = float(F32(0.5 * (lo + hi)))
+        lo, hi = (mid, hi) if ok(mid) else (lo, mid)
+    return lo
+
+
+ERFC_LAST = _last_f32(lambda t: _sp.erfc(t) >= TINY32, 9.0, 9.5)                  # about 9.1945: beyond it erfc(x) is no normal float32
+EXPM1_OVER = float(np.log(MAX32))                                                # 88.7228: expm1 overflows
+LGAMMA_OVER = _last_f32(lambda t: _sp.gammaln(t) <= MAX32, 1e36, 1e37)           # about 4.085e36: x log x overflows
+FAR_NEG = 2.0 ** 24
+SP_SHIFTS = (0, 1, 2, 3, 4)
+SP_LAT = [("xfm", 1e20), ("xfs", 10.0), ("xcm", 1e20), ("xcs", 10.0), ("xem", 1e20), ("xes", 100.0), ("xgm", 10.0), ("u", 10.0), ("xgg", 1e20),
+          ("xgs", 1e20)]
+_NEAR = [-k + s * 0.05 for k in (0, 1, 2) for s in (-1, 1)] + [-k + s * 0.2 for k in range(3, 11) for s in (-1, 1)]       # -k +- delta
+
+
+def _neg_between_poles(n, rs, margin):
+    """n negatives -k - frac, k = 0 .. 10, frac in [margin, 1 - margin]: no closer to a pole than margin"""
+    return -(rs.integers(0, 11, n) + rs.uniform(margin, 1.0 - margin, n))
+
+
+def _dyadic(n, rs, lo_exp, edges=()):
+    """n multiples of 2^-20 in [2^lo_exp, 1/2], log-uniform, after the edges"""
+    j = np.floor(2.0 ** rs.uniform(lo_exp + 20, 19, n - len(edges)))
+    x = np.concatenate([np.asarray(edges, np.float64), j * 2.0 ** -20])
+    return x[rs.permutation(n)].astype(F32)
+
+
+def _sp_grid(n):
+    rs = np.random.default_rng(71)
+    tiny = POW2(range(1, 100, 3))                                                # +-2^-k down to 1.6e-30
+    far = [s * t for t in (3.9, 4.0, 5.0, 10.0, 1e10, 1e30) for s in (1.0, -1.0)]
+    pos_g = _fill([1e-12, 0.5, 1.0, 2.0, 1.4616321, 14.0] + [0.5 * k for k in range(3, 28)], 1e-12, 14.0, n - n // 3, log=True, seed=77)
+    neg_g = np.concatenate([_NEAR, _neg_between_poles(n // 3 - len(_NEAR), rs, 0.2)]).astype(F32)
+    return dict(
+        xfm=_fill(np.concatenate([[0.0, -0.0], tiny, far]), -4.0, 4.0, n, seed=72),                         # erf as a mean
+        xfs=_fill([1e-30, 20.0, 1.0], 1e-30, 20.0, n, log=True, seed=73),                                    # as a scale: relative accuracy near 0
+        xcm=_fill([0.0, 1e30, -1e30, 30.0, -30.0, 1e10, -1e10], -30.0, 30.0, n, seed=74),                   # erfc as a mean: 0 or 2 far out
+        xcs=_fill([ERFC_LAST, -6.0, 0.0, 9.0], -6.0, ERFC_LAST, n, seed=75),                                 # as a scale: down to float32's smallest normal
+        xem=_fill(np.concatenate([[0.0], tiny, [-17.0, -88.0, -104.0, -200.0, -1e30, 3.4]]), -20.0, 3.4, n, seed=76),      # expm1 as a mean
+        xes=_fill([1e-30, 69.0, 88.7, 88.8, 1.0], 1e-30, 69.0, n, log=True, seed=78),                        # as a scale; 88.8: +inf
+        xgm=np.concatenate([pos_g, neg_g])[rs.permutation(n)].astype(F32),                                   # lgamma as a mean, either side of 0
+        u=_dyadic(n, rs, -20, [0.0] * 6 + [2.0 ** -m for m in range(4, 21)]),                                # lgamma(u - k): exact approaches, and the poles
+        xgg=_fill([0.0, -0.0, -1.0, -2.0, -1e7] * 3, 0.05, 9.0, n, both_signs=True, seed=79),                # the guarded lgamma
+        xgs=np.concatenate([_fill([3.0, 1e28, 0.99 * LGAMMA_OVER, 1.01 * LGAMMA_OVER], 3.0, 1e28, n - n // 2, log=True, seed=80),
+                            _fill([1e-37, 0.5], 1e-37, 0.5, n // 2, log=True, seed=81)])[rs.permutation(n)].astype(F32))       # lgamma as a scale
+
+
+def _sp_grad_grid(n):
+    rs = np.random.default_rng(82)
+    sat = [s * t for t in (5.0, 10.0, 30.0, 100.0) for s in (1.0, -1.0)]
+    n_neg = n // 2                                                               # (at least a third of the lgamma columns: the reflection)
+    return dict(
+        xfm=_fill(np.concatenate([[0.0], POW2(range(4, 21, 4)), sat]), -3.0, 3.0, n, seed=83),
+        xfs=_fill([], 0.01, 4.0, n, log=True, seed=84),
+        xcm=_fill([0.0, 6.0, -6.0, 30.0, -30.0], -4.0, 4.0, n, seed=85),
+        xcs=_fill([9.0, -3.0], -3.0, 9.0, n, seed=86),
+        xem=_fill(np.concatenate([[0.0], POW2(range(4, 21, 4)), [-17.0, -20.0]]), -5.0, 3.0, n, seed=87),
+        xes=_fill([], 0.01, 30.0, n, log=True, seed=88),
+        xgm=np.concatenate([_fill([0.5, 1.0, 2.0, 1.4616321], 0.05, 14.0, n - n_neg, log=True, seed=89),
+                            _neg_between_poles(n_neg, rs, 0.1)])[rs.permutation(n)].astype(F32),
+        u=_dyadic(n, rs, -4),
+        xgg=_fill([0.0, -0.0, -1.0, -2.0] * 3, 0.05, 9.0, n, both_signs=True, seed=90),
+        xgs=np.concatenate([_fill([], 3.0, 50.0, n - n // 2, log=True, seed=91), _fill([], 0.01, 0.5, n // 2, log=True, seed=92)])[rs.permutation(n)].astype(F32))
+
+
+def _lgamma_shift_site(k):
+    return (f"lgamma_u_{k}", "mean", lambda L: genjax.lgamma(L["u"] - float(k)), lambda v, d: _sp.gammaln(v["u"][0] - float(k)))
+
+
+SP_SITES = [
+    ("erf_m", "mean", lambda L: genjax.erf(_e(L["xfm"])), lambda v, d: _sp.erf(v["xfm"][0])),
+    ("erf_s", "scale", lambda L: genjax.erf(_e(L["xfs"])), lambda v, d: _sp.erf(v["xfs"][0])),
+    ("erfc_m", "mean", lambda L: genjax.erfc(_e(L["xcm"])), lambda v, d: _sp.erfc(v["xcm"][0])),
+    ("erfc_s", "scale", lambda L: genjax.erfc(_e(L["xcs"])), lambda v, d: _sp.erfc(v["xcs"][0])),       # (1 - erf: 0 from x = 4 on, a scale of 0)
+    ("expm1_m", "mean", lambda L: genjax.expm1(_e(L["xem"])), lambda v, d: np.expm1(v["xem"][0])),
+    ("expm1_s", "scale", lambda L: genjax.expm1(_e(L["xes"])), lambda v, d: np.expm1(v["xes"][0])),     # (exp(x) - 1: 0 below 6e-8, a scale of 0)
+    ("lgamma_m", "mean", lambda L: genjax.lgamma(_e(L["xgm"])), lambda v, d: _sp.gammaln(v["xgm"][0])),
+] + [_lgamma_shift_site(k) for k in SP_SHIFTS] + [
+    ("lgamma_far", "mean", lambda L: genjax.where(L["u"] > 0, genjax.lgamma(L["u"] + 3.0), genjax.lgamma(L["u"] - FAR_NEG)),
+     lambda v, d: _sel(d["u"][0] > 0, _sp.gammaln(v["u"][0] + 3.0), _sp.gammaln(np.where(d["u"][0] > 0, -0.5, v["u"][0] - FAR_NEG)))),
+    ("lgamma_pos", "mean", lambda L: genjax.where(L["xgg"] > 0, genjax.lgamma(L["xgg"]), 0.0),
+     lambda v, d: _guarded(d["xgg"][0] > 0, _sp.gammaln, v["xgg"][0], 0.0)),
+    ("lgamma_s", "scale", lambda L: genjax.lgamma(_e(L["xgs"])), lambda v, d: _sp.gammaln(v["xgs"][0])),
+]
+SP_OPS = [A.E_ERF, A.E_ERFC, A.E_LGAMMA, A.E_EXPM1, A.E_WHERE, A.E_GT, A.E_LINV]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 7. log-sum-exp: genjax.logsumexp over 2, 3, 63, 64, 65 and 93 elements of vector latents (93 operands pack into exactly 96 nodes; 65
+#    lower to a 64-operand node, a one-operand node and a node over both), np.logaddexp, lists of general expressions, a nested and a
+#    constant-carrying one.  The operand patterns sit in the first columns of the grid: all equal; ties at the maximum; one operand
+#    ahead by more than 104 nats (the others underflow); all at -1e30; all -inf; some -inf; and one operand overflowed to +inf
+#    (exp(a * a) at a = 10: the result is +inf, include/gjx.h).  The float64 side is scipy.special.logsumexp.
+# ---------------------------------------------------------------------------------------------------------------------------------
+LSE_ARITIES = (2, 3, 63, 64, 65, 93)
+LSE_LAT = [("x", 1e20, 32), ("x2", 1e20, 32), ("x3", 1e20, 32), ("a", 10.0), ("b", 10.0), ("c", 10.0), ("w", 10.0, 3)]
+LSE_AHEAD = (0, 1, 2, 62, 63, 64, 92)         # where the operand far ahead sits: in and across the 64-operand chunks
+
+
+def _lse_rows(v):
+    return np.concatenate([v["x"], v["x2"], v["x3"]])
+
+
+def _lse64(rows):
+    with np.errstate(all="ignore"):
+        return _sp.logsumexp(np.asarray(rows, np.float64), axis=0)
+
+
+def _lse_grid(n, edges=True):
+    rs = np.random.default_rng(101)
+    x = rs.uniform(-3.0, 3.0, (96, n))
+    a, b, c = (rs.uniform(-1.5, 1.5, n) for _ in range(3))
+    w = rs.uniform(0.05, 3.0, (3, n))
+    pat = np.arange(n) % 7
+    head = np.arange(n) < (28 * 7 if edges else 12 * 3)
+    for i in np.nonzero(head)[0]:
+        k = i // 7 if edges else i // 3
+        p_ = pat[i] if edges else i % 3
+        if p_ == 0:                                        # all equal
+            x[:, i] = rs.uniform(-20.0, 20.0)
+        elif p_ == 1:                                      # ties at the maximum: two or three positions
+            top = rs.uniform(0.0, 4.0)
+            x[:, i] = top - rs.uniform(0.5, 5.0, 96)
+            x[rs.choice(96, 2 + k % 2, replace=False), i] = top
+            x[[0, 1, 2][:2 + k % 2], i] = top              # (and among the first operands, for the small arities)
+        elif p_ == 2:                                      # one operand ahead by more than 104 nats
+            x[:, i] = -50.0 - rs.uniform(0.0, 3.0, 96)
+            x[LSE_AHEAD[k % len(LSE_AHEAD)], i] = 60.0
+        elif p_ == 3:
+            x[:, i] = -1e30
+        elif p_ == 4:
+            x[:, i] = -np.inf
+            w[:, i] = 0.0                                  # log 0 three times: every operand of the list is -inf too
+        elif p_ == 5:                                      # some -inf, the first operand among them
+            x[rs.random(96) < 0.5, i] = -np.inf
+            x[0, i], x[1, i] = -np.inf, rs.uniform(-3.0, 3.0)
+            w[k % 3, i] = 0.0
+        else:
+            a[i] = 10.0 if k % 2 == 0 else -10.0           # exp(a * a) = exp(100): +inf in float32
+    return dict(x=x[:32].astype(F32), x2=x[32:64].astype(F32), x3=x[64:].astype(F32), a=a.astype(F32), b=b.astype(F32), c=c.astype(F32),
+                w=w.astype(F32))
+
+
+def _lse_arity_site(k):
+    def build(L):
+        el = [L["x"][j] for j in range(32)] + [L["x2"][j] for j in range(32)] + [L["x3"][j] for j in range(32)]
+        return genjax.logsumexp(el[:k])
+    return (f"lse_{k}", "mean", build, lambda v, d: _lse64(_lse_rows(v)[:k]))
+
+
+LSE_SITES = [_lse_arity_site(k) for k in LSE_ARITIES] + [
+    ("logaddexp", "mean", lambda L: np.logaddexp(L["a"], L["b"]), lambda v, d: np.logaddexp(v["a"][0], v["b"][0])),
+    ("lse_list", "mean", lambda L: genjax.logsumexp([2.0 * L["a"], L["b"] * L["b"], genjax.tanh(L["c"])]),
+     lambda v, d: _lse64([2.0 * v["a"][0], v["b"][0] ** 2, np.tanh(v["c"][0])])),
+    ("lse_log", "mean", lambda L: genjax.logsumexp(genjax.log(_e(L["w"]))), lambda v, d: np.log(v["w"].sum(0))),
+    ("lse_scale", "scale", lambda L: genjax.exp(genjax.logsumexp([20.0 * L["b"], 20.0 * L["c"], L["a"] * L["c"]])),
+     lambda v, d: np.exp(_lse64([20.0 * v["b"][0], 20.0 * v["c"][0], v["a"][0] * v["c"][0]]))),
+    ("lse_nested", "mean", lambda L: genjax.logsumexp([genjax.logsumexp([L["b"], L["c"] * L["c"]]), np.logaddexp(L["c"], 0.5), 1.5]),
+     lambda v, d: _lse64([v["b"][0], v["c"][0] ** 2, v["c"][0], np.full_like(v["c"][0], 0.5), np.full_like(v["c"][0], 1.5)])),
+    ("lse_inf", "mean", lambda L: genjax.logsumexp([genjax.exp(L["a"] * L["a"]), L["b"]]),
+     lambda v, d: _lse64([np.exp(v["a"][0] ** 2), v["b"][0]])),
+]
+LSE_OPS = [A.E_LSEN, A.E_VALUE, A.E_EXP, A.E_LOG, A.E_MUL]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 8. reductions: sum, mean, cumsum, prod, max, min over a plain latent vector (sums: the closed affine forms) and over a general
+#    expression vector (sums: LINN; prod / max / min: folds of MUL / MAX / MIN), at lengths 1, 2 and 30.  The first columns hold: a sum
+#    that cancels to a few ulps of its largest term (every partial sum exact in float32); a product with one zero, with two, with sign
+#    changes, one that overflows and one that underflows; max / min with ties at two and three positions (the gradient goes to the
+#    EARLIEST index: the fold and MAX's rule), 0.0 against -0.0, and +-inf elements
+# ---------------------------------------------------------------------------------------------------------------------------------
+RED_LENS = (1, 2, 30)
+RED_LAT = [("r", 100.0, 32), ("p", 1e10, 8), ("m", 10.0, 4)]
+
+
+def _red_grid(n, edges=True):
+    rs = np.random.default_rng(111)
+    r = rs.uniform(0.2, 1.5, (32, n)) * rs.choice([-1.0, 1.0], (32, n))
+    p = rs.uniform(0.7, 1.3, (8, n)) * rs.choice([-1.0, 1.0], (8, n))
+    m = rs.uniform(-2.0, 2.0, (4, n))
+    for i in range(8):                                     # cancellation: 8192 - 8192 + k / 1024, nothing else
+        r[:, i] = 0.0
+        r[0, i], r[1, i] = 8192.0, -8192.0 + (i + 1) / 1024.0
+    for i in range(8, 16):
+        p[i % 8, i] = 0.0                                  # one zero: the gradient goes to that element only
+    for i in range(16, 24):
+        p[[i % 8, (i + 3) % 8], i] = 0.0                   # two zeros: the gradient is all zero
+    for i in range(24, 48):                                # ties at two and at three positions; +0 against -0
+        j = rs.choice(4, 2 + i % 2, replace=False)
+        m[j, i] = m[:, i].max() + 0.25 if i % 4 < 2 else m[:, i].min() - 0.25
+    m[:, 48], m[:, 49], m[:, 50], m[:, 51] = [0.0, -0.0, -1.0, -0.0], [-0.0, 0.0, -1.0, -2.0], [0.0, -0.0, 1.0, 0.0], [-0.0, 0.0, 0.5, 1.0]
+    if edges:
+        p[2:, 52], p[2:, 53] = 1e8, -1e8                   # six factors of 1e8 (the first two stay of order 1): 1e48, +-inf by the signs
+        p[2:, 54] = 1e8 * np.array([1, -1, 1, 1, 1, 1.0])
+        p[2:, 55], p[2:, 56] = 1e-9, -1e-9                 # 1e-54: 0
+        m[:, 57], m[:, 58], m[:, 59] = [0.3, np.inf, -1.0, 0.1], [0.3, -np.inf, -1.0, 0.1], [np.inf, -np.inf, np.inf, 0.0]
+    return dict(r=r.astype(F32), p=p.astype(F32), m=m.astype(F32))
+
+
+def _gen(x):
+    return genjax.tanh(x)            # the general expression vector the reductions range over
+
+
+def _first(d, v, pick):
+    """the element of v at the EARLIEST index where d attains its maximum (pick = np.argmax) or minimum (np.argmin)"""
+    return np.take_along_axis(v, pick(d, axis=0)[None], 0)[0]
+
+
+def _red_sites():
+    out = []
+    for k in RED_LENS:
+        sl = (lambda k: lambda L: L["r"][:k])(k)
+        out += [
+            (f"sum_v_{k}", "mean", (lambda sl: lambda L: sl(L).sum())(sl), (lambda k: lambda v, d: v["r"][:k].sum(0))(k)),
+            (f"mean_v_{k}", "mean", (lambda sl: lambda L: np.mean(sl(L)))(sl), (lambda k: lambda v, d: v["r"][:k].mean(0))(k)),
+            (f"sum_g_{k}", "mean", (lambda sl: lambda L: _gen(sl(L)).sum())(sl), (lambda k: lambda v, d: np.tanh(v["r"][:k]).sum(0))(k)),
+            (f"mean_g_{k}", "mean", (lambda sl: lambda L: _gen(sl(L)).mean())(sl), (lambda k: lambda v, d: np.tanh(v["r"][:k]).mean(0))(k)),
+        ]
+        for at in sorted({k // 2, k - 1}):
+            out += [
+                (f"cumsum_v_{k}_{at}", "mean", (lambda sl, at: lambda L: sl(L).cumsum()[at])(sl, at),
+                 (lambda k, at: lambda v, d: v["r"][:at + 1].sum(0))(k, at)),
+                (f"cumsum_g_{k}_{at}", "mean", (lambda sl, at: lambda L: np.cumsum(_gen(sl(L)))[at])(sl, at),
+                 (lambda k, at: lambda v, d: np.tanh(v["r"][:at + 1]).sum(0))(k, at)),
+            ]
+    out += [
+        ("prod_v", "mean", lambda L: L["p"].prod(), lambda v, d: v["p"].prod(0)),
+        ("prod_g", "mean", lambda L: (1.5 * _gen(L["p"])).prod(), lambda v, d: (1.5 * np.tanh(v["p"])).prod(0)),
+        ("prod_2", "mean", lambda L: L["p"][:2].prod(), lambda v, d: v["p"][:2].prod(0)),
+        ("max_v", "mean", lambda L: L["m"].max(), lambda v, d: _first(d["m"], v["m"], np.argmax)),
+        ("min_v", "mean", lambda L: L["m"].min(), lambda v, d: _first(d["m"], v["m"], np.argmin)),
+        ("max_g", "mean", lambda L: np.max(_gen(L["m"])), lambda v, d: _first(np.tanh(d["m"]), np.tanh(v["m"]), np.argmax)),
+        ("min_g", "mean", lambda L: np.amin(_gen(L["m"])), lambda v, d: _first(np.tanh(d["m"]), np.tanh(v["m"]), np.argmin)),
+        ("max_1", "mean", lambda L: genjax.square(L["m"][:1].max()), lambda v, d: v["m"][0] ** 2),
+    ]
+    return out
+
+
+RED_SITES = _red_sites()
+# the sums over the PLAIN latent vector are closed affine forms (GJX_P_AFFINE / GJX_P_VALUE), not expression blocks: exactly these
+CLOSED_FORMS = {"reduce": {s[0] for s in RED_SITES if s[0].startswith(("sum_v_", "mean_v_", "cumsum_v_"))}}
+RED_OPS = [A.E_LINN, A.E_MUL, A.E_MAX, A.E_MIN, A.E_TANH, A.E_VALUE]
+
+
 def _grad_of(grid, **kw):
     return lambda n: grid(n, **kw)
 
@@ -387,6 +653,9 @@ SPECS = {
     "powers": Spec(POW_LAT, POW_SITES, _pow_grid, _pow_grid, POW_OPS),
     "guards": Spec(GUARD_LAT, GUARD_SITES, _guard_grid, _grad_of(_guard_grid, boundary=True), GUARD_OPS),
     "linear": Spec(LIN_LAT, LIN_SITES, _lin_grid, _grad_of(_lin_grid, gaps=True), LIN_OPS),
+    "special": Spec(SP_LAT, SP_SITES, _sp_grid, _sp_grad_grid, SP_OPS),
+    "lse": Spec(LSE_LAT, LSE_SITES, _lse_grid, _grad_of(_lse_grid, edges=False), LSE_OPS),
+    "reduce": Spec(RED_LAT, RED_SITES, _red_grid, _grad_of(_red_grid, edges=False), RED_OPS),
 }
 # the latents whose rows hold inf / NaN on purpose (unnamed gap rows): their own sites' scores are then NaN in the reference too; they
 # are not selected for gradients and HMC
@@ -466,6 +735,19 @@ def exact_zero_gradients(prog, ch):
     return out
 
 
+def exact_zero_gradients_special(prog, ch):
+    """the special program's erf latent far out (|x| >= 30: float64's exp(-x^2) is 0) and the guarded lgamma's latent where the guard is
+    closed (a <= 0, the poles 0, -1 and -2 among them: digamma there is +-inf or NaN and meets a zero adjoint); both priors have scale 1e20"""
+    x, y = ch[prog.slot_of["xfm"]].astype(np.float64), ch[prog.slot_of["erf_m"]].astype(np.float64)
+    far = np.nonzero((y - _sp.erf(x)) * np.exp(-x * x) == 0.0)[0]
+    closed = np.nonzero(ch[prog.slot_of["xgg"]] <= 0)[0]
+    assert len(far) >= 4 and len(closed) >= 12 and {0.0, -1.0, -2.0} <= set(ch[prog.slot_of["xgg"]][closed].tolist())
+    return [(prog.slot_of["xfm"], far), (prog.slot_of["xgg"], closed)]
+
+
+EXACT_ZERO = {"unary": exact_zero_gradients, "special": exact_zero_gradients_special}
+
+
 def selected_rows(spec, prog, which):
     return [prog.slot_of[a] + e for a, _, d in spec["latents"] if a not in UNSELECTED.get(which, ()) for e in range(d)]
 
@@ -540,6 +822,88 @@ def structural_scan():
         with np.errstate(all="ignore"):
             m = mean(xp, zp, np.where, lambda t: np.sqrt(np.where(t > 0, t, 1.0)), np.tanh)
         prior = (nlp(x, m, 0.5) + nlp(g, 0.0, 1.0) + nlp(z, 0.5 * zp, 0.5)).sum(0)
+        return nlp(ys[:, None].astype(np.float64), x + z, 1.0).sum(0), prior
+    return prog, restate
+
+
+def special_plate(n):
+    """-> (program, rows f32[n_slots][n], scores(rows64) -> float64[n_sites][n]).  16 instances, ONE plate site y ~ normal(lgamma(x0 a + b),
+    erfc(x1 c + d)): the instance's covariates are data (per-instance table rows), a, b, c, d latent, the observations per column (rows).
+    lgamma's argument runs to the edges of the special program's mean site: down to 1e-12 towards the pole at 0, between the negative
+    poles to -10.8, up to 14.5.  erfc's runs from -6 (where it is 2) to 1.05 only: the site's mean is a float32 of size 1 to 30, known
+    to 1e-7 at best, so a scale much below 0.1 would turn that error into more than the tolerance — the float64 restatement itself
+    is not conditioned there (erfc as a scale down to 1.2e-38 is the special program's erfc_s, whose mean is exactly 0)"""
+    rs = np.random.default_rng(63)
+    X = np.stack([rs.uniform(0.5, 2.0, N_PLATE), rs.uniform(0.25, 0.95, N_PLATE)], 1).astype(F32)
+
+    @genjax.gen
+    def kern(x_row, a, b, c, d):
+        return genjax.normal(genjax.lgamma(x_row[0] * a + b), genjax.erfc(x_row[1] * c + d)) @ "y"
+
+    @genjax.gen
+    def model():
+        a = genjax.normal(0.0, 10.0) @ "a"
+        b = genjax.normal(0.0, 10.0) @ "b"
+        c = genjax.normal(0.0, 10.0) @ "c"
+        d = genjax.normal(0.0, 10.0) @ "d"
+        kern.vmap(in_axes=(0, None, None, None, None))(X, a, b, c, d) @ "obs"
+
+    sl, _ = model.site_list(())
+    ys = tuple(s.addr for s in sl.sites[4:])
+    from genjax_amd.core import ChoiceMap
+    prog, _, _ = model.pack((), ChoiceMap.empty(), False, per_particle=("a", "b", "c", "d") + ys, rng_mode=A.RNG_FLAT)
+    y0 = prog.slot_of[ys[0]]
+    assert [prog.slot_of[k] for k in "abcd"] == [0, 1, 2, 3] and [prog.slot_of[k] for k in ys] == list(range(y0, y0 + N_PLATE))
+    rows = np.zeros((prog.n_slots, n), np.float32)
+    rows[0], rows[1] = rs.uniform(1.0, 4.0, n), rs.uniform(0.0, 0.5, n)                 # lgamma's argument: 0.5 .. 8.5
+    rows[2], rows[3] = rs.uniform(-3.0, 1.0, n), rs.uniform(-0.1, 0.1, n)              # erfc's: -3 .. 1.05
+    q = n // 4
+    rows[2, :2 * q] = rs.uniform(-3.0, 0.0, 2 * q)                                      # (a mean of size 30 wants a scale of order 1)
+    rows[0, 3 * q::2] = rs.uniform(4.0, 7.0, len(rows[0, 3 * q::2]))                    # up to 14.5, with erfc's argument below 0
+    rows[2, 3 * q::2] = rs.uniform(-3.0, 0.0, len(rows[0, 3 * q::2]))
+    rows[0, :q], rows[1, :q] = 10.0 ** rs.uniform(-12.0, -1.0, q), 0.0                  # towards the pole at 0: down to 5e-13
+    rows[0, q:2 * q] = 0.0                                                              # between the negative poles, for EVERY instance
+    rows[1, q:2 * q] = -(rs.integers(0, 11, q) + rs.uniform(0.2, 0.8, q))
+    rows[2, 2 * q:3 * q], rows[3, 2 * q:3 * q] = 0.0, rs.uniform(-6.0, -3.0, q)         # erfc where it is 2 less a few ulps
+    r64 = rows.astype(np.float64)
+    X64 = X.astype(np.float64)
+    m, sg = _sp.gammaln(X64[:, :1] * r64[0] + r64[1]), _sp.erfc(X64[:, 1:] * r64[2] + r64[3])
+    rows[y0:] = m + sg * np.stack([np.roll(grid_offsets(n), 5 * i) for i in range(N_PLATE)])
+
+    def scores(r):
+        a, b, c, d = r[0], r[1], r[2], r[3]
+        with np.errstate(all="ignore"):
+            m, sg = _sp.gammaln(X64[:, :1] * a + b), _sp.erfc(X64[:, 1:] * c + d)
+            return np.stack([nlp(a, 0.0, 10.0), nlp(b, 0.0, 10.0), nlp(c, 0.0, 10.0), nlp(d, 0.0, 10.0), nlp(r[y0:], m, sg).sum(0)])
+    return prog, rows, scores
+
+
+def special_scan():
+    """-> (program, restate(prog, choices64) -> (likelihood, prior) float64[K]).  64 rolled steps; the body holds a 3-operand log-sum-exp (the
+    mean of x), an expm1 scale and a where-guarded lgamma (the mean of z).  The chain contracts (|x| stays below about 10 over 64 steps of
+    4099 particles) and is continuous with bounded slopes — the guard opens at 1, where lgamma is 0: the two engines draw the same
+    chain only up to the last bit of each step, and a slope like digamma's 1 / x at a guard opened at 0 turns that bit into 1e-3"""
+    from genjax_amd import C
+    ys = np.random.default_rng(64).standard_normal(T_SCAN).astype(F32)
+
+    @genjax.gen
+    def step(carry, _):
+        xp, zp = carry
+        x = genjax.normal(0.3 * genjax.logsumexp([xp, zp, -xp]), genjax.expm1(0.25 + 0.05 * genjax.square(zp))) @ "x"
+        z = genjax.normal(genjax.where(xp > 1, 0.2 * genjax.lgamma(xp), 0.0), 0.5) @ "z"
+        genjax.normal(x + z, 1.0) @ "y"
+        return (x, z), None
+
+    prog, _, _ = step.scan(n=T_SCAN).pack(((np.float32(0.4), np.float32(-0.2)), None), C["y"].set(ys), True, rng_mode=A.RNG_FLAT)
+
+    def restate(prog, ch):
+        x, z = (np.stack([ch[prog.slot_of[(k, t)]] for t in range(T_SCAN)]) for k in "xz")
+        xp = np.concatenate([np.full((1, x.shape[1]), np.float64(F32(0.4))), x[:-1]])
+        zp = np.concatenate([np.full((1, x.shape[1]), np.float64(F32(-0.2))), z[:-1]])
+        with np.errstate(all="ignore"):
+            mx, sx = 0.3 * _lse64([xp, zp, -xp]), np.expm1(0.25 + 0.05 * zp ** 2)
+            mz = np.where(xp > 1, 0.2 * _sp.gammaln(np.where(xp > 1, xp, 1.0)), 0.0)
+        prior = (nlp(x, mx, sx) + nlp(z, mz, 0.5)).sum(0)
         return nlp(ys[:, None].astype(np.float64), x + z, 1.0).sum(0), prior
     return prog, restate
 

@@ -246,10 +246,12 @@ def scan_chain(T, rng=A.RNG_FLAT, carry=True, observe=False, sigma=0.1, r=0.5, s
 # ---------------------------------------------------------------------------------------------
 # random general expressions (GJX_P_EXPR): shared by the CPU tests of the oracle and the GPU differential tests
 # ---------------------------------------------------------------------------------------------
-def random_expr_outs(rs, cont, dim, dom="real", depth=3):
+def random_expr_outs(rs, cont, dim, dom="real", depth=3, newer=False):
     """`dim` output nodes (genjax_amd/expr.py) of a random elementwise expression over the elements of the earlier continuous sites
     ``cont`` = [(addr, dim), ...] and constants.  Magnitudes stay bounded (every branch passes through tanh / sigmoid / sin or a
-    bounded rational form before it is combined), the final value lands in the domain the parameter needs: "real", "pos", "prob"."""
+    bounded rational form before it is combined), the final value lands in the domain the parameter needs: "real", "pos", "prob".
+    ``newer`` (off: every draw is what it was): a third of the inner nodes are erf, expm1 of a bounded subtree, lgamma(1.5 + sigmoid(.))
+    or a log-sum-exp of two or three subtrees."""
     from genjax_amd import expr as E
 
     def leaf():
@@ -271,6 +273,15 @@ def random_expr_outs(rs, cont, dim, dom="real", depth=3):
     def tree(d):
         if d == 0:
             return bounded(leaf())
+        if newer and rs.random() < 0.35:
+            r = rs.random()
+            if r < 0.25:
+                return E.unary("erf", tree(d - 1))
+            if r < 0.5:
+                return E.unary("expm1", bounded(tree(d - 1)))
+            if r < 0.75:
+                return E.unary("lgamma", E.lin(1.5, [(E.unary("sigmoid", tree(d - 1)), 1.0)]))
+            return E.lse([tree(d - 1) for _ in range(int(rs.integers(2, 4)))])
         r = rs.random()
         a = tree(d - 1)
         if r < 0.18:

@@ -29,11 +29,11 @@ def _blocks(prog):
 
 
 def _check_block(prog, nodes, n_out):
-    """the invariants include/gjx.h states: SSA order, operands in range, LINN operands consecutive and earlier, outputs last"""
+    """the invariants include/gjx.h states: SSA order, operands in range, LINN and LSEN operands consecutive and earlier, outputs last"""
     n = len(nodes)
     assert 1 <= n <= A.EXPR_MAX_NODES and 1 <= n_out <= n
     for i, (op, a, b, c, da, db) in enumerate(nodes):
-        assert 0 <= op < 25
+        assert 0 <= op < A.E_OP_MAX
         if op == A.E_CONST:
             assert 0 <= a < prog.tab.size and b == 0
         elif op == A.E_VALUE:
@@ -42,6 +42,8 @@ def _check_block(prog, nodes, n_out):
             assert 1 <= c <= 64 and a + 1 + c <= prog.tab.size and 0 <= b and b + c <= prog.n_slots
         elif op == A.E_LINN:
             assert 1 <= c <= 64 and a + 1 + c <= prog.tab.size and 0 <= b and b + c <= i
+        elif op == A.E_LSEN:
+            assert 1 <= c <= 64 and 0 <= b and b + c <= i
         elif op == A.E_WHERE:
             assert 0 <= a < i and 0 <= b < i and 0 <= c < i
         elif op in (A.E_ADD, A.E_SUB, A.E_MUL, A.E_DIV, A.E_MAX, A.E_MIN, A.E_GT):
@@ -123,7 +125,7 @@ def test_too_large_a_block_is_refused_with_a_message():
         PackedProgram(sl, {}, {})
 
 
-def _program_with_random_expressions(rs, n_latent=3):
+def _program_with_random_expressions(rs, n_latent=3, newer=False):
     sl = SiteList()
     cont = []
     for j in range(n_latent):
@@ -134,13 +136,13 @@ def _program_with_random_expressions(rs, n_latent=3):
             sl.add(f"x{j}", A.MVNORMAL_DIAG, [np.zeros(d, np.float32), np.ones(d, np.float32)], dim=d)
         cont.append((f"x{j}", d))
     d = int(rs.integers(1, 4))
-    loc = H.random_expr_outs(rs, cont, d if rs.random() < 0.6 else 1, "real")
-    sc = H.random_expr_outs(rs, cont, 1, "pos")
+    loc = H.random_expr_outs(rs, cont, d if rs.random() < 0.6 else 1, "real", newer=newer)
+    sc = H.random_expr_outs(rs, cont, 1, "pos", newer=newer)
     if d == 1:
         sl.add("y", A.NORMAL, [Param.expr(loc[:1]), Param.expr(sc)])
     else:
         sl.add("y", A.MVNORMAL_DIAG, [Param.expr(loc), Param.expr(sc)], dim=d)
-    pr = H.random_expr_outs(rs, cont, 1, "prob")
+    pr = H.random_expr_outs(rs, cont, 1, "prob", newer=newer)
     sl.add("f", A.FLIP, [Param.expr(pr)])
     return sl, cont, (loc, sc, pr, d)
 
@@ -158,11 +160,35 @@ def _score64(sl, cont, parts, vals):
     return tot + np.where(vals["f"][0] != 0, np.log(p), np.log1p(-p))
 
 
+NEWER_OPS = {A.E_ERF, A.E_EXPM1, A.E_LGAMMA, A.E_LSEN}
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_oracle_evaluates_blocks_with_the_newer_ops_like_float64_numpy_and_finite_differences(seed):
+    """the same check on random trees that also hold erf, expm1, lgamma and log-sum-exp nodes (helpers.random_expr_outs, newer=True);
+    the float64 side is expr.evaluate, which tests/test_expr_ops_cpu.py holds to scipy op by op"""
+    ops = _oracle_against_float64(np.random.default_rng(3000 + seed), newer=True)
+    assert ops & NEWER_OPS, sorted(ops)
+
+
+def test_the_newer_seeds_reach_every_newer_op():
+    ops = set()
+    for seed in range(6):
+        sl, cont, _ = _program_with_random_expressions(np.random.default_rng(3000 + seed), newer=True)
+        prog = PackedProgram(sl, {s.addr: A.MODE_OBS_SLOT for s in sl.sites}, {})
+        for _, _, nodes, _ in _blocks(prog):
+            ops |= set(nodes[:, 0].astype(int).tolist())
+    assert ops >= NEWER_OPS, sorted(NEWER_OPS - ops)
+
+
 @pytest.mark.parametrize("seed", range(12))
 def test_oracle_evaluates_blocks_like_float64_numpy_and_differentiates_them_like_finite_differences(seed):
+    _oracle_against_float64(np.random.default_rng(1000 + seed))
+
+
+def _oracle_against_float64(rs, newer=False):
     from oracle import cpu
-    rs = np.random.default_rng(1000 + seed)
-    sl, cont, parts = _program_with_random_expressions(rs)
+    sl, cont, parts = _program_with_random_expressions(rs, newer=newer)
     modes = {s.addr: A.MODE_OBS_SLOT for s in sl.sites}
     prog = PackedProgram(sl, modes, {}, selected=tuple(a for a, _ in cont) + ("y",))
     for j, k, nodes, n_out in _blocks(prog):
@@ -192,6 +218,7 @@ def test_oracle_evaluates_blocks_like_float64_numpy_and_differentiates_them_like
             smooth = np.abs(fd - fd_wide) < 1e-3 * (1.0 + np.abs(fd))
             assert smooth.mean() > 0.9
             np.testing.assert_allclose(g[prog.slot_of[a] + e][smooth], fd[smooth], rtol=2e-3, atol=2e-3)
+    return {int(o) for _, _, nodes, _ in _blocks(prog) for o in nodes[:, 0]}
 
 
 def test_a_vmapped_kernel_with_expressions_is_one_device_plate():

@@ -1,8 +1,9 @@
-"""The 25 older expression node ops on the device, op by op against float64 at their edges: ties, kinks, poles, overflow and guarded
+"""The expression node ops on the device, op by op against float64 at their edges: ties, kinks, poles, overflow and guarded
 branches (tests/expr_ops_ref.py holds the programs, the grids and the float64 restatement; tests/test_expr_ops_cpu.py runs the same
 grids on the CPU oracle and the host evaluator and checks that the restatement is well conditioned at EVERY grid point).
 
-Five programs — unary ops; binary ops, compare and select; integer powers; guards; linear layers with gaps — each on the generated
+Eight programs — unary ops; binary ops, compare and select; integer powers; guards; linear layers with gaps; the special functions
+erf, erfc, lgamma, expm1; log-sum-exp; the reductions — each on the generated
 kernels (asserted: engine 4) and on the site interpreter.  K = 4099 columns for scores, 384 for gradients and HMC.  Tolerances are the
 harness's (helpers.py): scores rtol 2e-4 / atol 2e-4; gradients rtol 2e-3 / atol 2e-3 against central differences of the restatement
 with the decisions frozen at the base point (the analytic gradient at ties, kinks and guard boundaries under include/gjx.h's rules);
@@ -24,7 +25,7 @@ import genjax_amd as genjax               # noqa: E402
 from genjax_amd import C                  # noqa: E402
 from genjax_amd import _abi as A          # noqa: E402
 from expr_ops_ref import (REFRESH_CS, REFRESH_YS, fd_gradient, packed, same_nonfinite, selected_rows,      # noqa: E402
-                               structural_plate, structural_scan, switching_filter)
+                               special_plate, special_scan, structural_plate, structural_scan, switching_filter)
 
 K, N_GRAD, RT, AT = H.GRID_K, H.GRID_N_GRAD, H.GRID_RT, H.GRID_AT
 
@@ -99,8 +100,8 @@ def test_gradients_and_one_hmc_move(K_, which, monkeypatch):
     for r in rows:
         assert np.isfinite(gg[r]).all(), (which, r)
         np.testing.assert_allclose(gg[r], fd[r], rtol=2e-3, atol=2e-3, err_msg=f"{which} row {r}")
-    if which == "unary":                  # tanh / sigmoid far out: exactly 0 where float64 rounds to 0
-        for r, cols in R.exact_zero_gradients(prog, ch):
+    if which in R.EXACT_ZERO:             # tanh / sigmoid / erf far out: exactly 0 where float64 rounds to 0; a closed guard over a pole
+        for r, cols in R.EXACT_ZERO[which](prog, ch):
             assert (np.abs(gg[r][cols]) <= 1e-37).all(), (r, gg[r][cols])
     moved = {}
     for eng in ("gen", "interp"):
@@ -114,12 +115,8 @@ def test_gradients_and_one_hmc_move(K_, which, monkeypatch):
     np.testing.assert_allclose(moved["gen"], moved["interp"], rtol=3e-3, atol=3e-3)
 
 
-def test_a_plate_with_a_guard_a_power_and_a_gapped_linear_form(K_, monkeypatch):
-    """16 instances of a vmapped kernel, ONE plate site: the leaf readers and the table strides that only plates use; the unnamed row
-    between the linear form's rows holds inf and NaN"""
+def _plate_on_both_engines(K_, monkeypatch, prog, rows, scores, what):
     import torch
-    prog, rows, scores = structural_plate(K)
-    assert prog.c_sites[prog.n_sites - 1].plate_n == 16 and prog.c_sites[prog.n_sites - 1].p[0].op == A.P_EXPR
     want = H.float32_range(scores(rows.astype(np.float64)))
     for eng in (None, "interp"):
         if eng is None:
@@ -130,14 +127,42 @@ def test_a_plate_with_a_guard_a_power_and_a_gapped_linear_form(K_, monkeypatch):
             assert K_.program_engine(prog) == 0
         g = K_.run_program(prog, (4, 5), K, choices=torch.as_tensor(rows).cuda(), want_site_scores=True)
         ss = _np(g["site_scores"]).astype(np.float64)
-        print(f"plate {eng or 'gen'}: max |site score error| / (atol + rtol |ref|) = {_worst(ss, want, RT, AT):.2e}")
-        fin = same_nonfinite(ss, want, f"plate {eng}")
+        print(f"{what} {eng or 'gen'}: max |site score error| / (atol + rtol |ref|) = {_worst(ss, want, RT, AT):.2e}")
+        fin = same_nonfinite(ss, want, f"{what} {eng}")
         np.testing.assert_allclose(ss[fin], want[fin], rtol=RT, atol=AT, err_msg=str(eng))
+
+
+def test_a_plate_with_a_guard_a_power_and_a_gapped_linear_form(K_, monkeypatch):
+    """16 instances of a vmapped kernel, ONE plate site: the leaf readers and the table strides that only plates use; the unnamed row
+    between the linear form's rows holds inf and NaN"""
+    prog, rows, scores = structural_plate(K)
+    assert prog.c_sites[prog.n_sites - 1].plate_n == 16 and prog.c_sites[prog.n_sites - 1].p[0].op == A.P_EXPR
+    _plate_on_both_engines(K_, monkeypatch, prog, rows, scores, "plate")
+
+
+def test_a_plate_whose_mean_is_lgamma_and_whose_scale_is_erfc(K_, monkeypatch):
+    """16 instances, ONE plate site y ~ normal(lgamma(x0 a + b), erfc(x1 c + d)) with per-instance covariates and per-column observations:
+    lgamma towards the pole at 0, between the negative poles and up to 14.5, erfc from 2 down to 0.14 (expr_ops_ref.special_plate)"""
+    prog, rows, scores = special_plate(K)
+    body = prog.c_sites[prog.n_sites - 1]
+    assert prog.n_sites == 5 and body.plate_n == 16 and body.p[0].op == A.P_EXPR and body.p[1].op == A.P_EXPR
+    assert {A.E_LGAMMA, A.E_ERFC} <= R.block_ops(prog)
+    _plate_on_both_engines(K_, monkeypatch, prog, rows, scores, "special plate")
 
 
 def test_a_rolled_scan_with_a_guard_a_power_and_a_gapped_linear_form(K_, monkeypatch):
     """64 steps of the same body: generated == interpreter, and the scores of the device's own draws == the float64 restatement"""
-    prog, restate = structural_scan()
+    _scan_on_both_engines(K_, monkeypatch, *structural_scan(), "scan")
+
+
+def test_a_rolled_scan_with_a_log_sum_exp_an_expm1_scale_and_a_guarded_lgamma(K_, monkeypatch):
+    """64 steps whose body holds a 3-operand log-sum-exp, an expm1 scale and a where-guarded lgamma (expr_ops_ref.special_scan)"""
+    prog, restate = special_scan()
+    assert prog.n_sites == 3 * R.T_SCAN and {A.E_LSEN, A.E_EXPM1, A.E_LGAMMA, A.E_WHERE} <= R.block_ops(prog)
+    _scan_on_both_engines(K_, monkeypatch, prog, restate, "special scan")
+
+
+def _scan_on_both_engines(K_, monkeypatch, prog, restate, what):
     monkeypatch.delenv("GJX_ENGINE", raising=False)
     assert K_.program_engine(prog) == 4
     out = {}
@@ -150,7 +175,7 @@ def test_a_rolled_scan_with_a_guard_a_power_and_a_gapped_linear_form(K_, monkeyp
         np.testing.assert_allclose(out["gen"][k], out["interp"][k], rtol=RT, atol=AT, err_msg=k)
     for eng in ("gen", "interp"):
         lik, prior = restate(prog, out[eng]["choices"])
-        print(f"scan {eng}: max |score error| / (atol + rtol |ref|) = {_worst(out[eng]['score'], lik + prior, RT, AT):.2e}")
+        print(f"{what} {eng}: max |score error| / (atol + rtol |ref|) = {_worst(out[eng]['score'], lik + prior, RT, AT):.2e}")
         np.testing.assert_allclose(out[eng]["logw"], lik, rtol=RT, atol=AT, err_msg=eng)
         np.testing.assert_allclose(out[eng]["score"], lik + prior, rtol=RT, atol=AT, err_msg=eng)
 

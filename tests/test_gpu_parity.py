@@ -1132,10 +1132,11 @@ def test_masked_constraints_parity(K_, oracle, rng):
     assert (gg["weight"] != 0).mean() > 0.8
 
 
-def _random_program(rs, rng_mode):
+def _random_program(rs, rng_mode, newer=False):
     """A random valid site program: every kind, parameters drawn from the six expression forms over earlier sites — the five closed
     forms and general expression blocks (GJX_P_EXPR) —
-    (positive / probability parameters go through exp / softplus / sigmoid), random constraint modes."""
+    (positive / probability parameters go through exp / softplus / sigmoid), random constraint modes.  ``newer`` (off: every draw is
+    what it was): half of the non-constant parameters are expression blocks whose trees also hold erf, expm1, lgamma and log-sum-exp."""
     POS, PROB, REAL = "pos", "prob", "real"
     spec = {  # kind -> parameter domains
         A.NORMAL: (REAL, POS), A.FLIP: (PROB,), A.BERNOULLI_LOGITS: (REAL,), A.BETA: (POS, POS), A.UNIFORM: None,
@@ -1169,6 +1170,8 @@ def _random_program(rs, rng_mode):
             if form < 0.35 or not cont:
                 v = {POS: np.abs(base) + 0.3, PROB: 1 / (1 + np.exp(-base)), REAL: base}[dom]
                 return Param.const(v.astype(np.float32))
+            if newer and rs.random() < 0.5:
+                return Param.expr(H.random_expr_outs(rs, cont, dim if rs.random() < 0.5 else 1, "real", depth=2, newer=True), xf=xf)
             vecs = [(a_, d_) for a_, d_ in cont if d_ >= 2]
             if form < 0.5 and cats and vecs:       # a row of an earlier vector-valued choice picked by an earlier categorical (GJX_P_VGATHER)
                 a, _ = cats[int(rs.integers(len(cats)))]
@@ -1199,21 +1202,38 @@ def test_random_programs_against_oracle(K_, oracle, rng, monkeypatch):
     constrained per particle (assess / importance semantics).  Device == oracle up to the stated tolerances.  Even trials
     run on the engine the library picks (a kernel generated for the program, compiled on the spot), odd trials on the site
     interpreter (which also halves the time the test spends in hipRTC)."""
+    _random_programs_against_oracle(K_, oracle, rng, monkeypatch, 77, 40, False)
+
+
+@pytest.mark.parametrize("rng", RNGS)
+def test_random_programs_with_the_newer_ops_against_oracle(K_, oracle, rng, monkeypatch):
+    """the same differential test, 8 programs whose expression blocks also hold erf, expm1, lgamma and log-sum-exp nodes (the oracle
+    evaluates them since it learned ops 25 .. 29): every one of the four is reached"""
+    ops = _random_programs_against_oracle(K_, oracle, rng, monkeypatch, 173, 8, True)
+    assert ops >= {A.E_ERF, A.E_EXPM1, A.E_LGAMMA, A.E_LSEN}, sorted(ops)
+
+
+def _random_programs_against_oracle(K_, oracle, rng, monkeypatch, seed, trials, newer):
     import torch
-    rs = np.random.default_rng(int(os.environ.get("GJX_FUZZ_SEED", "77")) + rng)
+    rs = np.random.default_rng(int(os.environ.get("GJX_FUZZ_SEED", str(seed))) + rng)
+    seen_ops = set()
     # campaign mode (profiles/fuzz.sh sets the seed): hundreds of programs reach float32 corner cases that no mask on the final
     # score sees — a scale of exp(70), a gradient alpha * (log(alpha) - digamma(alpha) + ...) at alpha = exp(11) whose bracket
     # carries 1e-6 of rounding (seeds 1001-1003: always 1-2 elements in thousands, device and oracle each wrong in their own
     # way).  There a trial may have 2 such particles / 0.1 % such gradient elements; a logic error fails whole columns.
     loose = "GJX_FUZZ_SEED" in os.environ
     K = 600
-    for trial in range(int(os.environ.get("GJX_FUZZ_TRIALS", "40"))):
+    for trial in range(int(os.environ.get("GJX_FUZZ_TRIALS", str(trials)))):
         if trial & 1:
             monkeypatch.setenv("GJX_ENGINE", "interp")
         else:
             monkeypatch.delenv("GJX_ENGINE", raising=False)
-        sl = _random_program(rs, rng)
+        sl = _random_program(rs, rng, newer) if newer else _random_program(rs, rng)
         prog = PackedProgram(sl, rng_mode=rng)
+        for j in range(prog.n_sites):
+            for cp in prog.c_sites[j].p:
+                if cp.op == A.P_EXPR:
+                    seen_ops |= set(prog.tab[cp.off:cp.off + A.EXPR_NODE_FLOATS * cp.n:A.EXPR_NODE_FLOATS].astype(int).tolist())
         key = (int(rs.integers(1 << 30)), int(rs.integers(1 << 30)))
         g, o = _run_both(K_, oracle, prog, key, K, want_site_scores=True)
         fin = np.isfinite(o["score"]) & (np.abs(o["score"]) < 1e4)
@@ -1305,3 +1325,4 @@ def test_random_programs_against_oracle(K_, oracle, rng, monkeypatch):
         for a in sub:
             s0 = prog2.slot_of[a]
             np.testing.assert_array_equal(_np(g2["choices"])[s0:s0 + sl[a].dim], ch[s0:s0 + sl[a].dim])
+    return seen_ops
