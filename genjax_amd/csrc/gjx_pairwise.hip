@@ -1,0 +1,257 @@
+// gjx_pairwise.hip — pairwise Gaussian log-sum-exp (gjx_pairwise_gauss_lse):
+//   out[r] = log sum_c exp(bias[c] - 1/2 p |q_r - k_c|^2),   r < n_q, c < n_k,
+// the n_q x n_k part of marginal backward smoothing (FFBSm), where both sets are a filter step's K particles.  Nothing of size
+// n_q x n_k is ever stored: the pairs are made 16 x 16 at a time on the matrix cores and consumed by a streaming log-sum-exp.
+//
+// Score.  With tildes for values minus `centre`:  score(r, c) = -1/2 p |q~_r|^2 + [bias_c - 1/2 p |k~_c|^2] + p q~_r . k~_c.
+// The first term is constant in c and is added at the very end (k_pw_merge); the bracket is a per-key number kb_c, computed when the
+// key is staged; the cross term is a matrix product.  Everything inside the loop is in units of log 2 (kb and the query fragment
+// are scaled by log2 e), so the exponential of a pair is one v_exp_f32 and nothing else.
+//
+// Matrix instruction.  v_mfma_f32_16x16x4_f32, inputs f32 (the expansion cancels: bf16 would not survive it).  d is padded with
+// zeros to DC = ceil(d / 4) chunks of 4.  Keys are the A operand (lane l holds key l % 16, component 4 c + l / 16), queries the B
+// operand (lane l holds query l % 16, component 4 c + l / 16), so D's rows are keys and its columns queries: lane l's four
+// accumulators are keys 4 (l / 16) .. + 3 for the ONE query l % 16.  The running (max, sum) of a query is therefore lane-local for
+// the whole key loop; the four lanes l % 16 + {0, 16, 32, 48} of a query are combined once, after the loop.  kb_c enters as the
+// C operand of the first MFMA of a tile (a 16-byte LDS read per 16 keys), so the accumulator comes out as the score.
+//
+// Block.  256 threads, 4 waves.  A wave keeps 4 groups of 16 queries as B fragments in registers (4 DC VGPRs, scaled by p log2 e)
+// for the whole kernel: 64 queries per wave, 256 per block, and every A fragment read from LDS feeds 4 MFMAs.  Keys are staged 64 at a
+// time through LDS, double-buffered: the global loads of tile n + 1 are issued before the MFMAs of tile n and stored after them,
+// one barrier per tile.  Staging: thread t takes key t / 4 and the components 4 c + t % 4 (dword loads, so no alignment is asked
+// of the rows), subtracts the centre, sums the squares over its quad of lanes, and writes the centred coordinates (row stride 80
+// floats: the four component rows a wave reads together fall on disjoint banks) and kb.  A dead key (bias -inf or NaN), a key past
+// n_k, and a live key whose centred norm is not finite are staged as ZERO coordinates with kb = -inf (dead, tail) or NaN (the last):
+// what the matrix cores see is always finite.
+//
+// Online rescaling, once per staged tile: the 16 scores of a (lane, group) give the tile's maximum, the running sum is rescaled by
+// one exponential, the 16 pairs cost one exponential each.
+//
+// Grid: (query blocks) x (key splits).  The number of splits is a function of (n_q, n_k) alone: enough to offer the device about
+// 1024 blocks, never less than 2 tiles per split.  Block (x, y) writes the (max, sum) of its 256 queries over its keys to
+// part[y][query]; k_pw_merge, one thread per query, folds the splits in index order, adds -1/2 p |q~|^2 and writes out.  No
+// atomics, no block waits for another, every sum in an order fixed by the shape: the output is bit-reproducible.
+#include <math.h>
+#include <string.h>
+
+#include "gjx_device.h"
+#include "gjx_host.h"
+
+namespace gjx {
+
+typedef float pw_v4f __attribute__((ext_vector_type(4)));
+
+constexpr int kPwThreads = 256;
+constexpr int kPwGroups = 4;                          // 16-query groups per wave
+constexpr int kPwBlockQ = 4 * 16 * kPwGroups;         // queries per block
+constexpr int kPwTile = 64;                           // keys per staged tile
+constexpr int kPwLd = kPwTile + 16;                   // floats between component rows in LDS
+constexpr int kPwMinTiles = 2;                        // tiles per key split at least
+constexpr int kPwTargetBlocks = 1024;
+constexpr float kPwLog2e = 1.44269504f, kPwLn2 = 0.693147181f;
+
+struct PwArgs {
+  const float* q;
+  const float* k;
+  const float* bias;       // or NULL
+  const float* centre;     // or NULL
+  float* out;
+  float2* part;            // [n_splits][n_q] = {max, sum} in units of log 2, without the query's own term
+  int64_t stride_q, stride_k;
+  int32_t n_q, n_k, d;
+  int32_t n_tiles, tiles_per_split, n_splits;
+  float p;
+};
+
+// (m, s) <- (m, s) + (om, os) where a pair stands for s 2^m; (-inf, 0) is the empty sum
+GJX_DEV void pw_fold(float& m, float& s, float om, float os) {
+  const float M = fmaxf(m, om), Ms = M > -INFINITY ? M : 0.0f;
+  s = s * __builtin_amdgcn_exp2f(m - Ms) + os * __builtin_amdgcn_exp2f(om - Ms);
+  m = M;
+}
+
+template <int DC>
+__global__ __launch_bounds__(kPwThreads) void k_pw_lse(const PwArgs a) {
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sb[2][kPwTile];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;            // the MFMA's view of the lane
+  const int skey = tid >> 2, spart = tid & 3;             // the staging's view: key of the tile, components 4 c + spart
+
+  // the wave's query fragments, for the whole kernel
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  const float ps = a.p * kPwLog2e;
+  float qf[kPwGroups][DC];
+  float scen[DC];
+#pragma unroll
+  for (int c = 0; c < DC; ++c) {
+    const int dq = 4 * c + quad, ds = 4 * c + spart;
+    const float cen = (a.centre && dq < a.d) ? a.centre[dq] : 0.0f;
+    scen[c] = (a.centre && ds < a.d) ? a.centre[ds] : 0.0f;
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      const int qi = q0 + 16 * g + col;
+      qf[g][c] = (dq < a.d && qi < a.n_q) ? (a.q[(int64_t)dq * a.stride_q + qi] - cen) * ps : 0.0f;
+    }
+  }
+
+  float v[DC], b;
+  auto load = [&](int tile) {
+    const int key = tile * kPwTile + skey;
+    const bool in = key < a.n_k;
+    b = in ? (a.bias ? a.bias[key] : 0.0f) : -INFINITY;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int ds = 4 * c + spart;
+      v[c] = (in && ds < a.d) ? a.k[(int64_t)ds * a.stride_k + key] - scen[c] : 0.0f;
+    }
+  };
+  auto store = [&](int buf) {
+    float k2 = 0.0f;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) k2 = fmaf(v[c], v[c], k2);
+    k2 = quad_sum(k2);
+    const bool dead = !(b > -INFINITY);                   // -inf or NaN
+    const bool zero = dead || !(k2 < INFINITY);
+#pragma unroll
+    for (int c = 0; c < DC; ++c) sk[buf][(4 * c + spart) * kPwLd + skey] = zero ? 0.0f : v[c];
+    if (spart == 0) sb[buf][skey] = dead ? -INFINITY : (zero ? NAN : (b - 0.5f * a.p * k2) * kPwLog2e);
+  };
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  float m[kPwGroups], s[kPwGroups];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) { m[g] = -INFINITY; s[g] = 0.0f; }
+
+  load(t0);
+  store(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) load(t + 1);
+    float af[4][DC];
+    pw_v4f seed[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {                         // the tile's four 16-key subtiles
+      seed[u] = *reinterpret_cast<const pw_v4f*>(&sb[buf][16 * u + 4 * quad]);
+#pragma unroll
+      for (int c = 0; c < DC; ++c) af[u][c] = sk[buf][(4 * c + quad) * kPwLd + 16 * u + col];
+    }
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      pw_v4f acc[4];
+      float mn = m[g];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc[u] = seed[u];
+#pragma unroll
+        for (int c = 0; c < DC; ++c) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][c], qf[g][c], acc[u], 0, 0, 0);
+        mn = fmaxf(fmaxf(mn, fmaxf(acc[u][0], acc[u][1])), fmaxf(acc[u][2], acc[u][3]));        // (fmaxf drops a NaN)
+      }
+      const float ms = mn > -INFINITY ? mn : 0.0f;
+      float e = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) e += __builtin_amdgcn_exp2f(acc[u][r] - ms);
+      s[g] = s[g] * __builtin_amdgcn_exp2f(m[g] - ms) + e;
+      m[g] = mn;
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+  }
+
+  // the four lanes of a query, then its partial
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {
+      const float om = __shfl_xor(m[g], off, 64), os = __shfl_xor(s[g], off, 64);
+      pw_fold(m[g], s[g], om, os);
+    }
+    const int qi = q0 + 16 * g + col;
+    if (quad == 0 && qi < a.n_q) a.part[(int64_t)blockIdx.y * a.n_q + qi] = make_float2(m[g], s[g]);
+  }
+}
+
+// one thread per query: the splits in index order, the query's own term, the answer in natural units
+__global__ __launch_bounds__(kPwThreads) void k_pw_merge(const PwArgs a) {
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  if (r >= a.n_q) return;
+  float q2 = 0.0f;
+  for (int i = 0; i < a.d; ++i) {
+    const float x = a.q[(int64_t)i * a.stride_q + r] - (a.centre ? a.centre[i] : 0.0f);
+    q2 = fmaf(x, x, q2);
+  }
+  float m = -INFINITY, s = 0.0f;
+  for (int y = 0; y < a.n_splits; ++y) {
+    const float2 p = a.part[(int64_t)y * a.n_q + r];
+    pw_fold(m, s, p.x, p.y);
+  }
+  // no live key: m = -inf, s = 0 -> -inf; a poisoned key: s = NaN -> NaN
+  a.out[r] = q2 < INFINITY ? (m + __builtin_amdgcn_logf(s)) * kPwLn2 - 0.5f * a.p * q2 : NAN;
+}
+
+// the split of the keys over blocks: a function of (n_q, n_k) alone.  false: a shape the call refuses
+static bool pw_plan(int64_t n_q, int64_t n_k, int32_t d, PwArgs* a) {
+  if (n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 || d > GJX_PAIRWISE_MAX_DIM) return false;
+  const int64_t n_qb = (n_q + kPwBlockQ - 1) / kPwBlockQ;
+  const int32_t n_tiles = (int32_t)((n_k + kPwTile - 1) / kPwTile);
+  int64_t want = (kPwTargetBlocks + n_qb - 1) / n_qb;
+  if (want > n_tiles / kPwMinTiles) want = n_tiles / kPwMinTiles;
+  if (want < 1) want = 1;
+  a->n_q = (int32_t)n_q; a->n_k = (int32_t)n_k; a->d = d;
+  a->n_tiles = n_tiles;
+  a->tiles_per_split = (int32_t)((n_tiles + want - 1) / want);
+  a->n_splits = (n_tiles + a->tiles_per_split - 1) / a->tiles_per_split;
+  return true;
+}
+
+template <int DC>
+static void pw_launch(const PwArgs& a, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL(k_pw_lse<DC>, grid, dim3(kPwThreads), 0, st, a);
+}
+
+}  // namespace gjx
+
+extern "C" size_t gjx_pairwise_gauss_lse_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
+  gjx::PwArgs a;
+  if (!gjx::pw_plan(n_q, n_k, d, &a)) return 0;
+  return 8 + sizeof(float2) * (size_t)a.n_splits * (size_t)n_q;          // (8: the alignment of any pointer)
+}
+
+extern "C" int gjx_pairwise_gauss_lse(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k,
+                                      int32_t d, const float* bias, float precision, const float* centre, float* out, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  using namespace gjx;
+  if (!q || !k || !out || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      stride_q < n_q || stride_k < n_k || !(precision > 0.0f) || !(precision < INFINITY))
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_gauss_lse: bad argument");
+  if (d > GJX_PAIRWISE_MAX_DIM) return gjx_fail(GJX_EUNSUPPORTED, "gjx_pairwise_gauss_lse: more than GJX_PAIRWISE_MAX_DIM components");
+  PwArgs a;
+  memset(&a, 0, sizeof(a));
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_gauss_lse_workspace_bytes(n_q, n_k, d))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_gauss_lse: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = out;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k; a.p = precision;
+  const dim3 grid((unsigned)((n_q + kPwBlockQ - 1) / kPwBlockQ), (unsigned)a.n_splits);
+  switch ((d + 3) / 4) {
+    case 1: pw_launch<1>(a, grid, st); break;
+    case 2: pw_launch<2>(a, grid, st); break;
+    case 3: pw_launch<3>(a, grid, st); break;
+    case 4: pw_launch<4>(a, grid, st); break;
+    case 5: pw_launch<5>(a, grid, st); break;
+    case 6: pw_launch<6>(a, grid, st); break;
+    case 7: pw_launch<7>(a, grid, st); break;
+    default: pw_launch<8>(a, grid, st); break;
+  }
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_lse(lse)");
+  hipLaunchKernelGGL(k_pw_merge, dim3((unsigned)((n_q + kPwThreads - 1) / kPwThreads)), dim3(kPwThreads), 0, st, a);
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_lse(merge)");
+  return GJX_OK;
+}

@@ -144,11 +144,16 @@ class ParticleHistory(LineageSmoothing):
         self.states: list = []      # x_t f32[dx][K], the particles as propagated at step t (before the next resampling)
         self.ancestors: list = []   # a_t i32[K] for t >= 1: particle i of step t descends from particle a_t[i] of step t-1
         self.logw = None            # log-weights of the last step
+        self.logw_steps: list = []  # the filtering log-weights f32[K] of every step's particles (when the filter recorded them)
+        self.ssm = None             # the LinearGaussianSSM the run filtered (ffbs_weights needs its transition)
+        self._moved = False         # replace_parents was called: a resample-move history
 
-    def append(self, x, anc):
+    def append(self, x, anc, logw=None):
         self.states.append(x.clone())
         if anc is not None:
             self.ancestors.append(anc.clone())
+        if logw is not None:
+            self.logw_steps.append(logw.clone())
 
     def replace_parents(self, x_moved, anc):
         """Resample-move: the particles of the current step descend from MOVED copies of the previous step's particles.
@@ -157,6 +162,7 @@ class ParticleHistory(LineageSmoothing):
         composed with ``anc`` (entry i now descends from what particle anc[i] descended from), and the current step is
         then appended with the identity as its ancestors."""
         from .. import kernels
+        self._moved = True
         self.states[-1] = x_moved.clone()
         if self.ancestors:
             a = self.ancestors[-1]
@@ -197,15 +203,44 @@ class ParticleHistory(LineageSmoothing):
     def _smoothing_rows(self, t, name=None):
         return self.states[t], t
 
-    def smoothed_moments(self, cov: bool = False) -> dict:
+    def ffbs_weights(self):
+        """f32[T][K]: the marginal backward-smoothing (FFBSm) weights of every step's stored particles, every row summing to 1 —
+        ``kernels.ffbs_weights`` with the model's transition: means[t] = A x_t (one torch.matmul per step, O(K dx^2)) and precision
+        1 / q^2.  All K particles of a step carry weight, so the early steps keep the effective sample size that ``smoothing_weights()``
+        loses to the genealogy (``survivors()``); the price is O(T K^2 dx) against O(T K).  Computed once and kept.  A resample-move
+        history raises NotImplementedError: its stored parents are moved copies, and the move is no Gaussian transition."""
+        import torch
+        from .. import kernels
+        if self._moved:
+            raise NotImplementedError("ffbs_weights: a resample-move history stores moved parents; its transition is not additive-Gaussian")
+        if self.ssm is None or len(self.logw_steps) != len(self.states):
+            raise ValueError("ffbs_weights: the history lacks the model or the per-step log-weights (BootstrapFilter.run records them)")
+        if getattr(self, "_ffbs_w", None) is None:
+            A_dev = torch.from_numpy(self.ssm.A).to(self.states[0].device)
+            means = [torch.matmul(A_dev, x) for x in self.states]
+            self._ffbs_w = kernels.ffbs_weights(self.states, self.logw_steps, means, 1.0 / (self.ssm.q * self.ssm.q))
+        return self._ffbs_w
+
+    def _smoothing_logw(self, method: str = "lineage"):
+        import torch
+        if method == "lineage":
+            return super()._smoothing_logw()
+        if method != "ffbs":
+            raise ValueError(f"smoothing method is 'lineage' or 'ffbs', not {method!r}")
+        if getattr(self, "_ffbs_logw", None) is None:
+            self._ffbs_logw = torch.log(self.ffbs_weights())
+        return self._ffbs_logw
+
+    def smoothed_moments(self, cov: bool = False, method: str = "lineage") -> dict:
         """E[x_t | y_{1:T}] and the spread about it for every step: dict(mean f32[T][dx], var f32[T][dx], ess f32[T]), or cov
         f32[T][dx][dx] in place of var with ``cov``: one gjx_weighted_moments call per step on the stored particles under the log
-        of ``smoothing_weights()``"""
-        return self._smoothed_moments(None, cov)
+        of ``smoothing_weights()`` (``method`` "lineage") or of ``ffbs_weights()`` ("ffbs")"""
+        return self._smoothed_moments(None, cov, method)
 
-    def smoothed_quantiles(self, q=(0.05, 0.5, 0.95)):
-        """quantiles of x_t | y_{1:T} for every step: f32[T][dx][n_levels], one gjx_weighted_quantiles call per step"""
-        return self._smoothed_quantiles(None, q)
+    def smoothed_quantiles(self, q=(0.05, 0.5, 0.95), method: str = "lineage"):
+        """quantiles of x_t | y_{1:T} for every step: f32[T][dx][n_levels], one gjx_weighted_quantiles call per step; ``method`` as
+        in ``smoothed_moments``"""
+        return self._smoothed_quantiles(None, q, method)
 
     def smoothed_pair_moments(self) -> dict:
         """the lag-one smoothing expectations for t = 1 .. T-1: dict(mean f32[T-1][dx] = E[x_t], mean_prev f32[T-1][dx] = E[x_{t-1}],
@@ -412,6 +447,8 @@ class BootstrapFilter:
             bt_buf = torch.empty(2, dtype=torch.int64, device=dev)
         x_prev, anc = None, None
         hist = ParticleHistory() if keep_history else None
+        if hist is not None:
+            hist.ssm = self.ssm
         k = key
         for t in range(T):
             k = fold_in(k, t)                      # chained step key (scan.py:268)
@@ -452,7 +489,7 @@ class BootstrapFilter:
                     rec = D.global_lse(lse, self.K)
             incs[t] = rec[3]
             if hist is not None:
-                hist.append(x_out, anc if t > 0 else None)
+                hist.append(x_out, anc if t > 0 else None, logw)
             if keep_means:
                 w = torch.exp(logw - rec[2])
                 m = (x_out * w).sum(dim=1)

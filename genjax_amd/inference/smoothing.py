@@ -42,11 +42,14 @@ class LineageSmoothing:
             self._lineage_logw = torch.log(self._lineage(check=False)["w"])
         return self._lineage_logw
 
-    def _smoothed_moments(self, name, cov: bool) -> dict:
+    def _smoothed_moments(self, name, cov: bool, method: str = "lineage") -> dict:
+        """``method`` other than "lineage": the record's own ``_smoothing_logw(method)`` supplies the table (ParticleHistory: "ffbs")"""
         from .. import kernels
-        lw, want = self._smoothing_logw(), "cov" if cov else "var"
+        lineage = method == "lineage"
+        lw, want = self._smoothing_logw() if lineage else self._smoothing_logw(method), "cov" if cov else "var"
         m = kernels.weighted_moments_steps([self._smoothing_rows(t, name) for t in range(lw.shape[0])], lw, want)
-        self._lineage()
+        if lineage:
+            self._lineage()
         return {"mean": m["mean"], want: m[want], "ess": m["stats"][:, 3]}
 
     def _smoothed_pair_moments(self, name) -> dict:
@@ -75,12 +78,14 @@ class LineageSmoothing:
         self._lineage()
         return {"mean": m["mean_a"], "mean_prev": m["mean_b"], "cross": m["cross"], "ess": m["stats"][:, 3]}
 
-    def _smoothed_quantiles(self, name, q) -> torch.Tensor:
+    def _smoothed_quantiles(self, name, q, method: str = "lineage") -> torch.Tensor:
         from .. import kernels
-        lw = self._smoothing_logw()
+        lineage = method == "lineage"
+        lw = self._smoothing_logw() if lineage else self._smoothing_logw(method)
         out = []
         for t in range(lw.shape[0]):
             rows, tw = self._smoothing_rows(t, name)
             out.append(kernels.weighted_quantiles(rows, lw[tw], q)["q"])
-        self._lineage()
+        if lineage:
+            self._lineage()
         return torch.stack(out)

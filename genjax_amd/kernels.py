@@ -694,7 +694,100 @@ def lineage_weights(ancestors: torch.Tensor, logw=None, ws=None) -> dict:
     return {"w": w, "survivors": survivors, "stats": stats, "n_bad": n_bad}
 
 
-PSIS_MAX_SEGMENT = 1 << 22          # gjx_pareto_smooth: particles per segment at most
+def _pairwise_rows(what: str, rows: torch.Tensor):
+    """one particle set of pairwise_gauss_lse -> rows [d][n], row stride, d, n"""
+    if rows.dim() == 1:
+        rows = rows.unsqueeze(0)
+    if rows.dim() != 2 or rows.dtype != torch.float32:
+        raise ValueError(f"pairwise_gauss_lse: {what} must be f32[d][n]")
+    d, n = int(rows.shape[0]), int(rows.shape[1])
+    if d <= 0 or n <= 0:
+        raise ValueError(f"pairwise_gauss_lse: {what} is empty")
+    if n > 1 and rows.stride(1) != 1:
+        raise ValueError(f"pairwise_gauss_lse: the particles of a row of {what} must be contiguous (column stride 1)")
+    stride = int(rows.stride(0)) if d > 1 else n
+    if stride < n:
+        raise ValueError(f"pairwise_gauss_lse: the rows of {what} overlap (row stride < n)")
+    return rows, stride, d, n
+
+
+def pairwise_gauss_lse(q_rows: torch.Tensor, k_rows: torch.Tensor, bias=None, precision: float = 1.0, centre=None, ws=None,
+                       out=None) -> torch.Tensor:
+    """gjx_pairwise_gauss_lse: queries f32[d][n_q] and keys f32[d][n_k] (SoA; views are fine as long as the column stride is 1, no
+    alignment is asked), ``bias`` f32[n_k] (None: zeros) -> f32[n_q], out[r] = log sum_c exp(bias[c] - 1/2 precision |q_r - k_c|^2).
+    A key with bias -inf or NaN is dead whatever its coordinates; no live key gives -inf; a query with a non-finite coordinate gives NaN
+    for that query alone.  ``centre`` f32[d] (None: zeros) is subtracted from both sets on the way in: it changes nothing mathematically
+    and decides the accuracy (the error grows with the centred squared norms): pass the keys' mean.  d <= 32.  O(n_q n_k d) on the matrix
+    cores, nothing of size n_q x n_k is stored; two launches, bit-reproducible."""
+    q_rows, stride_q, d, n_q = _pairwise_rows("q_rows", q_rows)
+    k_rows, stride_k, d_k, n_k = _pairwise_rows("k_rows", k_rows)
+    if d_k != d:
+        raise ValueError(f"pairwise_gauss_lse: queries have {d} components, keys {d_k}")
+    if d > A.PAIRWISE_MAX_DIM:
+        raise ValueError(f"pairwise_gauss_lse: at most {A.PAIRWISE_MAX_DIM} components, not {d}")
+    p = float(precision)
+    if not (p > 0.0 and p < float("inf")):
+        raise ValueError(f"pairwise_gauss_lse: precision must be positive and finite, not {precision}")
+    dev = q_rows.device
+    if bias is not None:
+        if bias.dtype != torch.float32 or bias.numel() != n_k:
+            raise ValueError("pairwise_gauss_lse: bias must be f32[n_k]")
+        bias = bias.reshape(-1).contiguous()
+    if centre is not None:
+        if centre.dtype != torch.float32 or centre.numel() != d:
+            raise ValueError("pairwise_gauss_lse: centre must be f32[d]")
+        centre = centre.reshape(-1).contiguous()
+    if out is None:
+        out = torch.empty(n_q, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.numel() != n_q or not out.is_contiguous():
+        raise ValueError("pairwise_gauss_lse: out must be a contiguous f32[n_q]")
+    if ws is None:
+        ws = torch.empty(load().gjx_pairwise_gauss_lse_workspace_bytes(n_q, n_k, d), dtype=torch.uint8, device=dev)   # partials only
+    check(load().gjx_pairwise_gauss_lse(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(bias), p, _ptr(centre), _ptr(out),
+                                        _ptr(ws), ws.numel(), _stream()), "gjx_pairwise_gauss_lse")
+    return out
+
+
+def ffbs_weights(states, logw_steps, means, precision: float) -> torch.Tensor:
+    """Marginal backward-smoothing weights (FFBSm, Doucet, Godsill & Andrieu 2000) of a recorded filter run whose transition is
+    additive-Gaussian, x_{t+1} ~ N(m(x_t), I / precision) -> f32[T][K], every row normalised to sum 1: step t's stored particles under
+    row t are the smoothing marginal p(x_t | y_{1:T}).  Unlike ``lineage_weights`` these use all K particles of every step and no
+    ancestor, so early steps do not collapse onto a few dozen survivors.
+      states[t]      f32[d][K], the particles of step t
+      logw_steps[t]  f32[K], the FILTERING log-weights of step t's particles (None: equal weights; -inf / NaN: dead)
+      means[t]       f32[d][K], the transition mean m(x_t^i) of step t's particles (means[T-1] is not read)
+    Recursion, backwards from w_{T-1|T} = w_{T-1}:  w_{t|T}^i = w_t^i sum_j w_{t+1|T}^j f(x_{t+1}^j | x_t^i) / sum_l w_t^l f(x_{t+1}^j | x_t^l),
+    in the log domain two ``pairwise_gauss_lse`` calls per step with the two particle sets in swapped roles; the centre of step t's
+    calls is the weighted mean of states[t+1] (``weighted_moments``).  Cost: O(T K^2 d) — 2 (T - 1) K^2 pairs, each d multiply-adds on
+    the matrix cores and one exponential — against O(T K) for the genealogy; outputs and workspace are allocated once, nothing is
+    read back."""
+    T = len(states)
+    if T == 0 or len(logw_steps) != T or len(means) != T:
+        raise ValueError("ffbs_weights: states, logw_steps and means must have one entry per step")
+    d, K = int(states[0].shape[0]), int(states[0].shape[1])
+    dev = states[0].device
+    ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
+
+    def log_normalised(lw):
+        lw = torch.where(torch.isnan(lw), ninf, lw)                       # (a NaN weight is dead, as everywhere in the library)
+        return lw - torch.logsumexp(lw, 0)
+
+    lw_filter = [torch.zeros(K, dtype=torch.float32, device=dev) if lw is None else lw.reshape(-1) for lw in logw_steps]
+    out = torch.empty((T, K), dtype=torch.float32, device=dev)
+    out[T - 1] = log_normalised(lw_filter[T - 1])
+    if T > 1:
+        ws = torch.empty(load().gjx_pairwise_gauss_lse_workspace_bytes(K, K, d), dtype=torch.uint8, device=dev)
+        D, back = torch.empty(K, dtype=torch.float32, device=dev), torch.empty(K, dtype=torch.float32, device=dev)
+    for t in range(T - 2, -1, -1):
+        lw_t = log_normalised(lw_filter[t])
+        centre = weighted_moments(states[t + 1], logw_steps[t + 1], "mean")["mean"]
+        pairwise_gauss_lse(states[t + 1], means[t], lw_t, precision, centre, ws, out=D)
+        pairwise_gauss_lse(means[t], states[t + 1], out[t + 1] - D, precision, centre, ws, out=back)
+        out[t] = log_normalised(lw_t + back)
+    return torch.exp_(out)
+
+
+PSIS_MAX_SEGMENT = 1 << 22         # gjx_pareto_smooth: particles per segment at most
 
 
 def pareto_tail(n: int) -> int:

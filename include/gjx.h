@@ -1095,6 +1095,46 @@ int gjx_lineage_weights(const int32_t* ancestors /* i32[T-1][anc_stride], may be
 size_t gjx_pareto_smooth_workspace_bytes(int64_t K, int64_t n_segments);
 int gjx_pareto_smooth(const float* logw, int64_t K, int64_t n_segments, float* logw_out /* f32[K] */, float* fit /* f32[S][4] */,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* Pairwise Gaussian log-sum-exp:  out[r] = log sum_{c < n_k} exp(bias[c] - 1/2 precision |q_r - k_c|^2),  r < n_q.  It is the
+ * n_q x n_k part of marginal backward smoothing (FFBSm, Doucet, Godsill & Andrieu 2000) for additive-Gaussian transitions
+ * x_{t+1} ~ N(m(x_t), I / precision): with m_i the transition mean of step t's particle i and lw the filtering log-weights,
+ *     D_j     = LSE_i (lw_t^i - 1/2 precision |x_{t+1}^j - m_i|^2)                         (queries x_{t+1}, keys m, bias lw_t)
+ *     lw_{t|T}^i = lw_t^i + LSE_j (lw_{t+1|T}^j - D_j - 1/2 precision |m_i - x_{t+1}^j|^2)  (queries m, keys x_{t+1}, bias lw_{t+1|T} - D)
+ * are two calls with the particle sets in swapped roles (the Gaussian's normalising constant cancels between them).  These weights
+ * use all K stored particles of every step and no ancestor, so they do not collapse with the genealogy as gjx_lineage_weights' do;
+ * a step costs O(n_q n_k d), nothing of size n_q x n_k is stored.  The reference has no counterpart.
+ *   q          f32[d][stride_q], stride_q >= n_q: the queries, one row per component (SoA, as a filter's particles)
+ *   k          f32[d][stride_k], stride_k >= n_k: the keys
+ *   bias       f32[n_k]; NULL: zeros
+ *   precision  > 0 and finite (anisotropic noise: the caller pre-whitens)
+ *   centre     f32[d] or NULL (zeros): subtracted from both sets as they are loaded.  Mathematically it changes nothing; numerically
+ *              the score is evaluated as  -1/2 p |q~|^2 + [bias - 1/2 p |k~|^2] + p q~ . k~  (tildes: centred values), whose terms cancel,
+ *              so the error of out[r] is of the order 2^-24 (d + 4) p (|q~_r|^2 + max_c |k~_c|^2): pass the keys' (weighted) mean
+ *   out        f32[n_q]
+ * d runs from 1 to GJX_PAIRWISE_MAX_DIM.  Rows need no alignment and any stride >= n is taken: both sets are read with dword loads
+ * (there is no vector path to fall off), so odd-column views of a history are served as they are.
+ * Semantics.  A key whose bias is -inf or NaN is DEAD: it contributes nothing whatever its coordinates are (NaN and inf included); its
+ * coordinates are replaced by zeros when the key is staged and never reach a matrix instruction.  No live key: out = -inf.  A query
+ * with a non-finite coordinate (or a centred norm that overflows) gives NaN for that query alone.  A LIVE key with a non-finite
+ * coordinate (or an overflowing centred norm) is not a number anybody can weigh: it is staged as zeros too and makes every output NaN.
+ * A bias of +inf is not supported (NaN).
+ * Device work.  Two plain launches on `stream`, nothing read back, no atomics, no block waits for another.  The first runs on a grid
+ * of (256-query blocks) x (key splits): the cross term p q~ . k~ on v_mfma_f32_16x16x4_f32 with f32 inputs (keys the A operand, queries
+ * the B operand, d padded with zeros to a multiple of 4), bias - 1/2 p |k~|^2 as the C operand, and a streaming log-sum-exp whose
+ * running maximum is rescaled once per staged tile of 64 keys: one hardware exponential per pair.  Every (query, split) leaves a
+ * (max, sum) pair in the workspace; the second launch folds the splits of a query in index order and adds -1/2 p |q~|^2.  The number
+ * of key splits depends on (n_q, n_k) alone and every sum runs in an order fixed by the shape: the output is bit-reproducible.
+ * Exponentials and the final logarithm are the hardware's (v_exp_f32 / v_log_f32, about 1 ulp).
+ * GJX_EINVAL: a NULL q, k, out or workspace; n_q <= 0, n_k <= 0, n_q >= 2^31, n_k >= 2^31 - 64; d <= 0; stride_q < n_q or stride_k <
+ * n_k; a precision that is not > 0 and finite.  GJX_EUNSUPPORTED: d > GJX_PAIRWISE_MAX_DIM.  GJX_EWORKSPACE: less than
+ * gjx_pairwise_gauss_lse_workspace_bytes(n_q, n_k, d) (0 for shapes the call refuses).  The workspace needs no initialisation:
+ * every word that is read was written by the same call.  Nothing is launched on a refusal. */
+#define GJX_PAIRWISE_MAX_DIM 32
+size_t gjx_pairwise_gauss_lse_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d);
+int gjx_pairwise_gauss_lse(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q, const float* k /* f32[d][stride_k] */,
+                           int64_t stride_k, int64_t n_k, int32_t d, const float* bias /* f32[n_k] or NULL */, float precision,
+                           const float* centre /* f32[d] or NULL */, float* out /* f32[n_q] */, void* workspace,
+                           size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
