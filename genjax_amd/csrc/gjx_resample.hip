@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void k_pick_partial(const float* logw, int64_t
   }
 }
 
-__global__ __launch_bounds__(256) void k_pick_finish(const PickPair* partials, int n, PickPair* out) {
+__global__ __launch_bounds__(256) void k_pick_finish(const PickPair* partials, int n, int32_t first, PickPair* out) {
   __shared__ float rv[4];
   __shared__ int32_t ri[4];
   float bv = -INFINITY;
@@ -77,7 +77,9 @@ __global__ __launch_bounds__(256) void k_pick_finish(const PickPair* partials, i
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int w = 1; w < 4; ++w) pick_better(bv, bi, rv[w], ri[w]);
-    *out = PickPair{bv, bi};
+    // a dead collection (lse = -inf, every value NaN): its first particle.  0x7FFFFFFF is reserved for "nothing compared greater":
+    // a global index particle_offset + i of 2^31 - 1 itself is not supported (it would be reported as `first`)
+    *out = PickPair{bv, bi == 0x7FFFFFFF ? first : bi};
   }
 }
 
@@ -100,12 +102,15 @@ __global__ __launch_bounds__(256) void k_trials_lse_pick(const float* logw, int6
   const float bm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   float sm = 0.0f;
   if (bm > -INFINITY)
-    for (int64_t i = threadIdx.x; i < K; i += 256) sm += fast_exp(lw[i] - bm);
+    for (int64_t i = threadIdx.x; i < K; i += 256) {
+      const float e = fast_exp(lw[i] - bm);
+      sm += e > 0.0f ? e : 0.0f;      // (a NaN weight is dead: the maximum dropped it, this drops its term)
+    }
   sm = wave_sum(sm);
   if ((threadIdx.x & 63) == 0) red[4 + (threadIdx.x >> 6)] = sm;
   __syncthreads();
   const float bs = (red[4] + red[5]) + (red[6] + red[7]);
-  const float l = bm > -INFINITY ? bm + fast_log(bs) : -INFINITY;
+  const float l = fabsf(bm) < INFINITY ? bm + fast_log(bs) : bm;   // a maximum that is not finite is the result (gjx.h, "non-finite weights")
   if (threadIdx.x == 0) {
     float* o = lse_out + 4 * t;
     o[0] = bm; o[1] = bs; o[2] = l; o[3] = l - log_k;
@@ -1011,7 +1016,7 @@ extern "C" int gjx_categorical_pick(const float* logw, int64_t K, int64_t partic
   else
     hipLaunchKernelGGL(k_pick_partial<GJX_RNG_FLAT>, dim3(nblocks), dim3(256), 0, st, logw, K, particle_offset, lse, key2{key0, key1}, partials);
   GJX_CHECK_LAUNCH("gjx_categorical_pick/partial");
-  hipLaunchKernelGGL(k_pick_finish, dim3(1), dim3(256), 0, st, (const PickPair*)partials, nblocks, (PickPair*)out_dev);
+  hipLaunchKernelGGL(k_pick_finish, dim3(1), dim3(256), 0, st, (const PickPair*)partials, nblocks, (int32_t)particle_offset, (PickPair*)out_dev);
   GJX_CHECK_LAUNCH("gjx_categorical_pick/finish");
   return GJX_OK;
 }

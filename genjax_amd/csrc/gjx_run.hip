@@ -983,7 +983,8 @@ __global__ __launch_bounds__(256) void k_lse_finish(const float2* partials, int 
   __syncthreads();
   if (threadIdx.x == 0) {
     const float bs = red[4] + red[5] + red[6] + red[7];
-    const float lse = bm > -INFINITY ? bm + logf(bs) : -INFINITY;
+    // a maximum that is not finite is the result (gjx.h, "non-finite weights"): -inf for no live entry, +inf for a live +inf
+    const float lse = fabsf(bm) < INFINITY ? bm + logf(bs) : bm;
     out[0] = bm; out[1] = bs; out[2] = lse; out[3] = lse - log_k_total;
   }
 }
@@ -994,7 +995,11 @@ __global__ __launch_bounds__(256) void k_lse_partial(const float* x, int64_t K, 
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < K; i += (int64_t)gridDim.x * 256) {
     const float v = x[i];
     const float nm = fmaxf(tmax, v);
-    if (nm > -INFINITY) tsum = tsum * fast_exp(tmax - nm) + fast_exp(v - nm);
+    if (nm > -INFINITY) {
+      float e = fast_exp(v - nm);
+      e = e > 0.0f ? e : 0.0f;        // (a NaN weight is dead wherever it sits: fmaxf dropped it from nm, this drops its term)
+      tsum = tsum * fast_exp(tmax - nm) + e;
+    }
     tmax = nm;
   }
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;

@@ -475,11 +475,25 @@ int gjx_importance_step_ex(const gjx_program* prog, uint32_t key0, uint32_t key1
                            int32_t* ancestors, void* workspace, size_t workspace_bytes, void* stream,
                            void* start_event, void* stop_event);
 
-/* ---- log-sum-exp (smc.py:97,107,464) -----------------------------------------------------
- * out[4] = {max, sum exp(x-max), logsumexp, logsumexp - log(K_total)} */
+/* ---- Non-finite weights: one rule for every call that takes weights -------------------------
+ * (gjx_logsumexp, gjx_lse_combine, gjx_trials_lse_pick, gjx_categorical_pick, gjx_weight_cumsum with is_log 0 and 1,
+ * gjx_resample_indices, gjx_resample_gather, gjx_ess; the calls further down state the same for themselves)
+ *  1. A log-weight of -inf or NaN is DEAD wherever it sits: the output of a call equals, bit for bit, its output with -inf in
+ *     place of every NaN.  Linear weights (is_log 0): <= 0 or NaN is dead.
+ *  2. A record without a live particle is {-inf, 0, -inf, -inf}.  A pick returns the first index of the collection or of the trial
+ *     (particle_offset [+ t K]); a resampler returns the identity ancestors j mod K and sets status bit 1 (gjx_workspace_status).
+ *  3. A live +inf log-weight makes the record of the three log-sum-exp calls max = lse = lse - log K_total = +inf (a maximum that is
+ *     not finite is the result, as for GJX_E_LSEN); entry 1 (sumexp) is then unspecified.  +inf is NOT supported by the picks and
+ *     the resamplers: their output for such weights is unspecified (in bounds, nothing else).
+ *  4. gjx_lse_combine: a pair whose maximum is -inf or NaN is an empty rank whatever its sum holds.
+ * Not covered: the block {max, sumexp} pairs that a producing kernel leaves (gjx_run_program with lse == NULL, the filters' own
+ * records) and therefore gjx_weight_cumsum with is_log 2 and gjx_importance_step: a NaN weight may still poison those sums.
+ *
+ * ---- log-sum-exp (smc.py:97,107,464) -----------------------------------------------------
+ * out[4] = {max, sum exp(x-max), logsumexp, logsumexp - log(K_total)}; non-finite entries: the rule above */
 int gjx_logsumexp(const float* x, int64_t K, int64_t K_total, float* out, void* workspace,
                   size_t workspace_bytes, void* stream);
-/* combine G partial {max, sumexp} pairs (one per rank, gathered by the caller over RCCL) */
+/* combine G partial {max, sumexp} pairs (one per rank, gathered by the caller over RCCL); empty ranks and +inf: "Non-finite weights" */
 int gjx_lse_combine(const float* pairs /*[G][2]*/, int G, int64_t K_total, float* out,
                     void* stream);
 
@@ -489,7 +503,7 @@ int gjx_lse_combine(const float* pairs /*[G][2]*/, int G, int64_t K_total, float
  * that offset of the sharded run, normalised on its own): lse_out f32[n_trials][4] = {max, sumexp, lse, lse - log K} per
  * trial; pick_out (or NULL) int32[n_trials] = the trial's 1-of-K draw as a GLOBAL index, by the rule of
  * gjx_categorical_pick (smc.py:102-109) with that trial's offset (a trial whose weights are all zero: lse = -inf, and the
- * index of its first particle). */
+ * index of its first particle).  -inf, NaN and +inf weights: "Non-finite weights" above; a trial's NaN stays in that trial. */
 int gjx_trials_lse_pick(const float* logw, int64_t n_trials, int64_t K, int64_t particle_offset, uint32_t key0,
                         uint32_t key1, int32_t rng_mode, float* lse_out, int32_t* pick_out, void* stream);
 
@@ -503,7 +517,12 @@ int gjx_event_elapsed_us(void* start_event, void* stop_event, float* us_out); /*
 
 /* ---- 1-of-K categorical draw over the weights: ParticleCollection.sample_particle
  * (smc.py:102-109): idx = argmax_i (logw[i] - lse) + Gumbel(bits(key, i)).
- * out_dev: {float best_value, int32 idx (global index = particle_offset + i)} as 2 words */
+ * out_dev: {float best_value, int32 idx (global index = particle_offset + i)} as 2 words.  A dead particle (-inf, NaN) is never
+ * drawn while a live one exists; a dead collection (lse = -inf) gives particle_offset ("Non-finite weights" above).
+ * Sharded over ranks (every rank passes the global lse): a shard without a live particle returns the value -inf and an index of its
+ * own (its particle_offset when lse = -inf); the caller keeps the pair with the larger value, the lower index at a tie, so a live
+ * shard's pair always wins and a collection dead on every rank gives the lowest offset. The global index 2^31 - 1 is reserved as the kernels' "none yet" mark:
+ * particle_offset + K must stay at or below it. */
 int gjx_categorical_pick(const float* logw, int64_t K, int64_t particle_offset, const float* lse,
                          uint32_t key0, uint32_t key1, int32_t rng_mode, void* out_dev,
                          void* workspace, size_t workspace_bytes, void* stream);
@@ -511,7 +530,8 @@ int gjx_categorical_pick(const float* logw, int64_t K, int64_t particle_offset, 
 /* ---- N-of-K resampling (not in the reference library; the cookbook idiom is K independent
  * categorical draws + gather, docs/cookbook/inactive/inference/importance_sampling.ipynb) ----
  * Weights are turned into exact fixed-point integers q_i = (uint64)(w_i * 2^30),
- * w_i = is_log ? exp(x_i - max) : x_i, so prefix sums and comb searches are exact integer work.
+ * w_i = is_log ? exp(x_i - max) : x_i, so prefix sums and comb searches are exact integer work.  Dead weights (log: -inf or NaN,
+ * linear: <= 0 or NaN; "Non-finite weights" above) have q_i = 0 and never get offspring.
  *   cum            u64[K] out : inclusive prefix sums of q
  *   base_total_dev u64[2] out : {0, sum q} — ready to pass to the resamplers on one GPU; with several ranks the
  *                               caller overwrites it with {sum of lower ranks' totals, sum over all ranks}

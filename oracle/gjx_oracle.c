@@ -1136,12 +1136,16 @@ static void lse4(const float* x, int64_t K, int64_t K_total, float* out) {
   float mx = -INFINITY;
   for (int64_t i = 0; i < K; ++i)
     if (x[i] > mx) mx = x[i];
+  /* include/gjx.h, "non-finite weights": -inf and NaN entries are dead (the comparison above never takes a NaN, the sum below
+   * leaves both out); a maximum that is not finite is the result: -inf without a live entry, +inf with a live +inf (the sum is
+   * then left at 0: entry 1 is unspecified) */
   double s = 0.0;
-  if (mx > -INFINITY)
-    for (int64_t i = 0; i < K; ++i) s += exp((double)x[i] - (double)mx);
+  if (isfinite(mx))
+    for (int64_t i = 0; i < K; ++i)
+      if (x[i] > -INFINITY) s += exp((double)x[i] - (double)mx);
   out[0] = mx;
   out[1] = (float)s;
-  out[2] = (mx > -INFINITY) ? (float)((double)mx + log(s)) : -INFINITY;
+  out[2] = isfinite(mx) ? (float)((double)mx + log(s)) : mx;
   out[3] = (float)((double)out[2] - log((double)K_total));
 }
 
@@ -1189,7 +1193,7 @@ int gjxo_categorical_pick(const float* logw, int64_t K, int64_t particle_offset,
                           int64_t* best_idx) {
   okey key = {key0, key1};
   float bv = -INFINITY;
-  int64_t bi = 0;
+  int64_t bi = particle_offset; /* a dead collection (lse = -inf: every value NaN, none compares greater): its first particle */
   for (int64_t i = 0; i < K; ++i) {
     uint64_t gi = (uint64_t)(particle_offset + i);
     float g;
