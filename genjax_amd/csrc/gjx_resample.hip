@@ -329,7 +329,11 @@ __global__ __launch_bounds__(256) void k_resample_fused(const float* __restrict_
 
 // ------------------------------------------------------------------------------------------
 // One-launch resampling + gather for a single GPU (N = K): weights -> systematic ancestors -> rows of the children,
-// the ancestors never written to memory unless asked for.  Block b scans its own tile of 256 ITEMS fixed-point weights,
+// the ancestors never written to memory unless asked for.  Every block waits for the LAST tile total, so the way to the publication is
+// kept short: the own tile's weights are the first load, the epoch of the rendezvous the second; with block partials (mode 2) a block
+// reduces only their MAXIMUM (block_ref_max_only: a lane's pairs in flight together, one barrier) — the sum of the partials feeds
+// nothing but lse_out, and block 0 finishes it (block_ref_max_unfused, the same record bit for bit) once its total is out.
+// Block b scans its own tile of 256 ITEMS fixed-point weights,
 // the tile totals are all-gathered (the one rendezvous, as in k_resample_fused), and then the block is the CONSUMER of
 // the output slots [b TILE, (b+1) TILE): each lane takes ITEMS consecutive slots, computes their comb thresholds T_j,
 // and finds the source tile of each among the eight tiles around its own, whose boundaries are the weight below them (summed
@@ -363,8 +367,6 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
   __shared__ __align__(16) uint64_t cumL[CH * TILE];   // inclusive cumulative weights of the tiles being searched, relative to each tile's start (16-byte reads)
   __shared__ uint64_t s_wtot[CH][4];
   __shared__ int s_range[2];                    // first and last source tile of this block's slots
-  unsigned epoch;
-  const unsigned long long tag = grid_tag(ctrl, &epoch);
   const int nb = (int)gridDim.x;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * ITEMS;   // first particle this lane scans
@@ -381,13 +383,17 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
   // tiles b - 1 .. b + 1, so their cumulative weights are laid out in LDS while the tile totals travel (below)
   const int w0 = (int)blockIdx.x - 1;            // first tile of the prefetched window
   float xv[ITEMS], xn[2][ITEMS];
+  // the own tile is requested FIRST and the epoch behind it: load_tile's two forms write the same registers, and the compiler puts a
+  // wait for every earlier load in front of the 16-byte one — with the epoch requested first (grid_tag at the top) the first weights
+  // left one L2 round trip late.  The epoch is taken up again only behind the reduction (the empty asm keeps its use from moving up)
   load_tile(i0, xv);
-  float sm_sum;
-  const float mx = block_ref_max(mode, lse, n_partials, fred, &sm_sum);
-  if (mode == 2 && lse_out && blockIdx.x == 0 && threadIdx.x == 0) {
-    const float l = mx > -INFINITY ? mx + logf(sm_sum) : -INFINITY;
-    lse_out[0] = mx; lse_out[1] = sm_sum; lse_out[2] = l; lse_out[3] = l - log_k_total;
-  }
+  unsigned epoch = grid_epoch(ctrl);
+  // ---- reference maximum: the maximum ALONE on the way to the publication (mode 2: a lane's pairs in flight together, no exponentials,
+  //      one barrier; the other modes: no barrier).  The sum of the partials feeds nothing but lse_out: block 0 finishes it behind its
+  //      publication (below) ----
+  const float mx = block_ref_max_only(mode, lse, n_partials, fred);
+  asm volatile("" : "+v"(epoch));
+  const unsigned long long tag = grid_tag_of(epoch);
   // ---- own tile total -> all-gather ----
   uint64_t qown[ITEMS], sown = 0, incown;
   {
@@ -399,10 +405,19 @@ __global__ __launch_bounds__(256) void k_resample_gather(const float* __restrict
     if (threadIdx.x == 0) grid_publish(agg, tag, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
   }
   GJX_STAMP(1);
+  if (mode == 2 && lse_out && blockIdx.x == 0) {   // block-uniform: the whole reduction as block_ref_max does it (same pairs, same order, nothing fused: the same record)
+    float sm_sum;
+    const float m2 = block_ref_max_unfused(lse, n_partials, fred, &sm_sum);   // (its first barrier: every lane has read fred)
+    if (threadIdx.x == 0) {
+      const float l = m2 > -INFINITY ? m2 + logf(sm_sum) : -INFINITY;
+      lse_out[0] = m2; lse_out[1] = sm_sum; lse_out[2] = l; lse_out[3] = l - log_k_total;
+    }
+  }
   // ---- while the totals are in flight: cumulative weights of tiles b - 1, b, b + 1 RELATIVE to each tile's start.  Written out, not a
   //      rescan_round: the own tile's scan above is reused (scanning it again measured 0.3 us per step at K = 2^20)
   //      (the neighbours' log-weights are requested only now: nothing may delay the publication above, every block waits
-  //      for the last one) ----
+  //      for the last one — requested earlier they are covered by the own tile's wait, which the compiler emits as vmcnt(0):
+  //      the loads sit in divergent branches, profiles/r08_resample_gather_head.txt) ----
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
     const int tc = w0 + 2 * c;

@@ -49,6 +49,54 @@ GJX_DEV float block_ref_max(int mode, const float* lse, int n_partials, float* r
   return m;
 }
 
+// The maximum ALONE, for a caller whose way to its first use of it must be short (k_resample_gather): no exponentials, no second wave
+// reduction, ONE barrier in mode 2 and none in the other modes (as block_ref_max).  A thread's pairs are requested together (the
+// maxima do not depend on each other; block_ref_max's loop waits for each pair before it asks for the next: one L2 round trip per
+// 256 pairs) and combined in block_ref_max's order, waves and block as there: the same bits.  The sum is left to whoever needs it
+// (block_ref_max again).  `red` must not be in use: there is no barrier in front of its writes.
+GJX_DEV float block_ref_max_only(int mode, const float* lse, int n_partials, float* red) {
+  if (mode != 2) return mode == 1 ? lse[0] : 0.0f;
+  const float2* parts = (const float2*)lse;
+  float tmax = -INFINITY;
+  for (int t0 = threadIdx.x; t0 < n_partials; t0 += 1024) {
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = t0 + 256 * k < n_partials ? parts[t0 + 256 * k].x : -INFINITY;   // (fmaxf(tmax, -inf) == tmax: tmax is never NaN)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tmax = fmaxf(tmax, v[k]);
+  }
+  const float wm = wave_max(tmax);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = wm;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// block_ref_max's whole reduction over the pairs (mode 2) for a caller in which ONE block runs it behind other work and one thread
+// takes the result (k_resample_gather's block 0): the same pairs in the same order, every product and every sum rounded on its own
+// (contraction off) — what block_ref_max compiles to where every block runs it ahead of its weights.  Inlined into that branch,
+// block_ref_max's last four multiply-adds were contracted into fused ones and the sum moved by one ulp for some inputs.
+GJX_DEV float block_ref_max_unfused(const float* lse, int n_partials, float* red, float* sum_out) {
+#pragma clang fp contract(off)
+  const float2* parts = (const float2*)lse;
+  float tmax = -INFINITY, tsum = 0.0f;
+  for (int t = threadIdx.x; t < n_partials; t += 256) {
+    const float2 p = parts[t];
+    const float nm = fmaxf(tmax, p.x);
+    if (nm > -INFINITY) tsum = tsum * fast_exp(tmax - nm) + p.y * fast_exp(p.x - nm);
+    tmax = nm;
+  }
+  const float wm = wave_max(tmax);
+  const float ws = wave_sum(wm > -INFINITY ? tsum * fast_exp(tmax - wm) : 0.0f);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = wm; red[4 + (threadIdx.x >> 6)] = ws; }
+  __syncthreads();
+  const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float sm = 0.0f;
+  for (int w = 0; w < 4; ++w) sm += m > -INFINITY ? red[4 + w] * fast_exp(red[w] - m) : 0.0f;
+  *sum_out = sm;
+  return m;
+}
+
 // the same reduction over block pairs that other blocks of THIS launch stored (agent-scope 8-byte stores of pack_f2)
 GJX_DEV float block_ref_max_live(const float* lse, int n_partials, float* red, float* sum_out) {
   const unsigned long long* parts = (const unsigned long long*)lse;
@@ -134,6 +182,10 @@ GJX_DEV unsigned long long grid_tag(const unsigned* ctrl, unsigned* epoch_out) {
   *epoch_out = epoch;
   return (unsigned long long)(epoch % 16383u) + 1ull;
 }
+
+// grid_tag in two halves, for a kernel that requests the epoch with its first loads and wants it only at the publication
+GJX_DEV unsigned grid_epoch(const unsigned* ctrl) { return __hip_atomic_load(&ctrl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+GJX_DEV unsigned long long grid_tag_of(unsigned epoch) { return (unsigned long long)(epoch % 16383u) + 1ull; }
 
 // PAD: one granule every PAD words (PAD = 8: one per 64-byte line).  Blocks that store into a shared line serialise in the
 // L2, readers pay PAD times the lines: worth it for the 256-block grids of the one-launch filters, not for 1024 blocks.
