@@ -31,6 +31,9 @@
 // 1024 blocks, never less than 2 tiles per split.  Block (x, y) writes the (max, sum) of its 256 queries over its keys to
 // part[y][query]; k_pw_merge, one thread per query, folds the splits in index order, adds -1/2 p |q~|^2 and writes out.  No
 // atomics, no block waits for another, every sum in an order fixed by the shape: the output is bit-reproducible.
+//
+// gjx_pairwise_gauss_mean (k_pw_mean, k_pw_mean_merge; second half of this file) adds the softmax-weighted mean of a value matrix
+// over the same scores: attention with a Gaussian kernel.  Its scheme is described there.
 #include <math.h>
 #include <string.h>
 
@@ -214,6 +217,230 @@ static void pw_launch(const PwArgs& a, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL(k_pw_lse<DC>, grid, dim3(kPwThreads), 0, st, a);
 }
 
+// ---- gjx_pairwise_gauss_mean:  mean[j][r] = sum_c softmax_c(score(r, c)) v[j][c],  and the log-sum-exp as a by-product ----
+//
+// Scores are made exactly as in k_pw_lse (same staging, same centring, same zeroing of dead, tail and poisoned keys, kb as the C
+// operand).  Second product.  Lane l's accumulators acc[u][i] are the scores of keys 16 u + 4 (l / 16) + i for the one query l % 16:
+// that is the B-operand layout of a 16x16x4 product whose contraction index is l / 16.  So P = exp2(acc - max) feeds a second
+// v_mfma_f32_16x16x4_f32 as B with no shuffle and no LDS round trip: MFMA (u, i) contracts the four keys 16 u + 4 quad + i, quad =
+// 0 .. 3, its A fragment is V[j = l % 16][that key].  The output is O^T[j][query]: lane l holds j = 4 (l / 16) + r for query l % 16,
+// so the online rescale factor of a query is lane-local.  dv is padded with zero rows to VB = ceil(dv / 16) blocks of 16: 16 VB
+// MFMAs per staged tile and query group on top of the 4 DC of the scores; O^T lives in 4 VB accumulators per group for the whole loop.
+//
+// Shared maximum.  The second product contracts over the four lanes l % 16 + {0, 16, 32, 48} of a query, so these must agree on the
+// maximum BEFORE the exponentials (k_pw_lse lets each keep its own).  Two v_permlane{16,32}_swap per tile and group exchange the
+// rows of the wave in the VALU (ds_bpermute where the compiler lacks them).  The running maximum is then the same number in the four
+// lanes; the running sum stays lane-local (a lane's own 16 keys per tile) and the four are added after the loop.  O^T and the sum
+// are rescaled once per staged tile by one exponential.
+//
+// Values go through LDS with the keys, double-buffered, under the same single barrier per tile, laid out [j][key] with row stride
+// 68 floats: a lane's four i are one 16-byte read at [j = col][16 u + 4 quad], and the 16 lanes of a quad-row (col = 0 .. 15) start
+// 68 floats = 4 banks (mod 64) apart: 16 x 4 dwords on 64 distinct banks.  (Staging stores fall 4 spart + skey: up to 4 lanes on
+// a bank, 4 VB dword stores a thread and tile, nothing next to the 16 (DC / 4 + VB) MFMAs.)  A dead or tail key's values are staged
+// as zeros (they often hold NaN / inf, and 0 x NaN must not reach an accumulator); a live key's non-finite value is staged as NaN:
+// the A fragment's row j is then NaN in every query's accumulator whether or not the weight underflowed.
+//
+// Grid and plan are k_pw_lse's.  A split leaves (max, sum) and O^T[dv] per query in the workspace ([split][j][n_q], coalesced over
+// queries); k_pw_mean_merge, one thread per (query, j), folds the splits in index order, divides, and (j = 0) writes the lse.
+constexpr int kPwLdV = kPwTile + 4;                   // floats between value rows in LDS
+
+struct PwMeanArgs {
+  PwArgs pw;               // pw.out: the lse, or NULL
+  const float* v;
+  float* mean;             // f32[dv][n_q]
+  float* opart;            // [n_splits][dv][n_q], scaled by 2^-max of the split
+  int64_t stride_v;
+  int32_t dv;
+};
+
+// the maximum over the four lanes l % 16 + {0, 16, 32, 48}, in all four
+GJX_DEV float pw_rows_max(float x) {
+#if __has_builtin(__builtin_amdgcn_permlane16_swap) && __has_builtin(__builtin_amdgcn_permlane32_swap)
+  unsigned u = __float_as_uint(x);
+  auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);          // {r0 r0 r2 r2}, {r1 r1 r3 r3}
+  x = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
+  u = __float_as_uint(x);
+  auto b = __builtin_amdgcn_permlane32_swap(u, u, false, false);          // {lo lo}, {hi hi}
+  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+#else
+  x = fmaxf(x, __shfl_xor(x, 16, 64));
+  return fmaxf(x, __shfl_xor(x, 32, 64));
+#endif
+}
+
+template <int DC, int VB>
+__global__ __launch_bounds__(kPwThreads) void k_pw_mean(const PwMeanArgs ma) {
+  const PwArgs& a = ma.pw;
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sb[2][kPwTile];
+  __shared__ __attribute__((aligned(16))) float sv[2][16 * VB * kPwLdV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;
+  const int skey = tid >> 2, spart = tid & 3;
+
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  const float ps = a.p * kPwLog2e;
+  float qf[kPwGroups][DC];
+  float scen[DC];
+#pragma unroll
+  for (int c = 0; c < DC; ++c) {
+    const int dq = 4 * c + quad, ds = 4 * c + spart;
+    const float cen = (a.centre && dq < a.d) ? a.centre[dq] : 0.0f;
+    scen[c] = (a.centre && ds < a.d) ? a.centre[ds] : 0.0f;
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      const int qi = q0 + 16 * g + col;
+      qf[g][c] = (dq < a.d && qi < a.n_q) ? (a.q[(int64_t)dq * a.stride_q + qi] - cen) * ps : 0.0f;
+    }
+  }
+
+  float kv[DC], vv[4 * VB], b;
+  auto load = [&](int tile) {
+    const int key = tile * kPwTile + skey;
+    const bool in = key < a.n_k;
+    b = in ? (a.bias ? a.bias[key] : 0.0f) : -INFINITY;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int ds = 4 * c + spart;
+      kv[c] = (in && ds < a.d) ? a.k[(int64_t)ds * a.stride_k + key] - scen[c] : 0.0f;
+    }
+#pragma unroll
+    for (int c = 0; c < 4 * VB; ++c) {
+      const int j = 4 * c + spart;
+      vv[c] = (in && j < ma.dv) ? ma.v[(int64_t)j * ma.stride_v + key] : 0.0f;
+    }
+  };
+  auto store = [&](int buf) {
+    float k2 = 0.0f;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) k2 = fmaf(kv[c], kv[c], k2);
+    k2 = quad_sum(k2);
+    const bool dead = !(b > -INFINITY);                   // -inf or NaN
+    const bool zero = dead || !(k2 < INFINITY);
+#pragma unroll
+    for (int c = 0; c < DC; ++c) sk[buf][(4 * c + spart) * kPwLd + skey] = zero ? 0.0f : kv[c];
+#pragma unroll
+    for (int c = 0; c < 4 * VB; ++c)
+      sv[buf][(4 * c + spart) * kPwLdV + skey] = dead ? 0.0f : (fabsf(vv[c]) < INFINITY ? vv[c] : NAN);
+    if (spart == 0) sb[buf][skey] = dead ? -INFINITY : (zero ? NAN : (b - 0.5f * a.p * k2) * kPwLog2e);
+  };
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  float m[kPwGroups], s[kPwGroups];
+  pw_v4f o[kPwGroups][VB];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    m[g] = -INFINITY;
+    s[g] = 0.0f;
+#pragma unroll
+    for (int vb = 0; vb < VB; ++vb) o[g][vb] = pw_v4f{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+
+  load(t0);
+  store(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) load(t + 1);
+    float af[4][DC];
+    pw_v4f seed[4], vf[4][VB];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      seed[u] = *reinterpret_cast<const pw_v4f*>(&sb[buf][16 * u + 4 * quad]);
+#pragma unroll
+      for (int c = 0; c < DC; ++c) af[u][c] = sk[buf][(4 * c + quad) * kPwLd + 16 * u + col];
+#pragma unroll
+      for (int vb = 0; vb < VB; ++vb)
+        vf[u][vb] = *reinterpret_cast<const pw_v4f*>(&sv[buf][(16 * vb + col) * kPwLdV + 16 * u + 4 * quad]);
+    }
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      pw_v4f acc[4];
+      float mn = m[g];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc[u] = seed[u];
+#pragma unroll
+        for (int c = 0; c < DC; ++c) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][c], qf[g][c], acc[u], 0, 0, 0);
+        mn = fmaxf(fmaxf(mn, fmaxf(acc[u][0], acc[u][1])), fmaxf(acc[u][2], acc[u][3]));        // (fmaxf drops a NaN)
+      }
+      mn = pw_rows_max(mn);                               // the query's four lanes agree before the exponentials
+      const float ms = mn > -INFINITY ? mn : 0.0f;
+      const float f = __builtin_amdgcn_exp2f(m[g] - ms);
+      float e = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          acc[u][r] = __builtin_amdgcn_exp2f(acc[u][r] - ms);
+          e += acc[u][r];
+        }
+      s[g] = s[g] * f + e;
+      m[g] = mn;
+#pragma unroll
+      for (int vb = 0; vb < VB; ++vb) {
+        o[g][vb] *= f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) o[g][vb] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[u][vb][r], acc[u][r], o[g][vb], 0, 0, 0);
+      }
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+  }
+
+  // the four lanes of a query share m; their sums are added in one fixed order.  Then the partials.
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    s[g] += __shfl_xor(s[g], 16, 64);
+    s[g] += __shfl_xor(s[g], 32, 64);
+    const int qi = q0 + 16 * g + col;
+    if (qi >= a.n_q) continue;
+    if (quad == 0) a.part[(int64_t)blockIdx.y * a.n_q + qi] = make_float2(m[g], s[g]);
+#pragma unroll
+    for (int vb = 0; vb < VB; ++vb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = 16 * vb + 4 * quad + r;
+        if (j < ma.dv) ma.opart[((int64_t)blockIdx.y * ma.dv + j) * a.n_q + qi] = o[g][vb][r];
+      }
+  }
+}
+
+// one thread per (query, value row): the splits in index order, the division, and from row 0 the log-sum-exp
+__global__ __launch_bounds__(kPwThreads) void k_pw_mean_merge(const PwMeanArgs ma) {
+  const PwArgs& a = ma.pw;
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  const int j = (int)blockIdx.y;
+  if (r >= a.n_q) return;
+  float q2 = 0.0f;
+  for (int i = 0; i < a.d; ++i) {
+    const float x = a.q[(int64_t)i * a.stride_q + r] - (a.centre ? a.centre[i] : 0.0f);
+    q2 = fmaf(x, x, q2);
+  }
+  float m = -INFINITY, s = 0.0f;
+  for (int y = 0; y < a.n_splits; ++y) {
+    const float2 p = a.part[(int64_t)y * a.n_q + r];
+    pw_fold(m, s, p.x, p.y);
+  }
+  const float ms = m > -INFINITY ? m : 0.0f;
+  float o = 0.0f;
+  for (int y = 0; y < a.n_splits; ++y)
+    o = fmaf(ma.opart[((int64_t)y * ma.dv + j) * a.n_q + r], __builtin_amdgcn_exp2f(a.part[(int64_t)y * a.n_q + r].x - ms), o);
+  // no live key: 0 / 0 = NaN; a poisoned key: s = NaN; a live key's non-finite value: o = NaN in its row
+  ma.mean[(int64_t)j * a.n_q + r] = q2 < INFINITY ? o / s : NAN;
+  if (j == 0 && a.out) a.out[r] = q2 < INFINITY ? (m + __builtin_amdgcn_logf(s)) * kPwLn2 - 0.5f * a.p * q2 : NAN;
+}
+
+template <int DC>
+static void pw_mean_launch(const PwMeanArgs& ma, dim3 grid, hipStream_t st) {
+  if (ma.dv <= 16) hipLaunchKernelGGL((k_pw_mean<DC, 1>), grid, dim3(kPwThreads), 0, st, ma);
+  else hipLaunchKernelGGL((k_pw_mean<DC, 2>), grid, dim3(kPwThreads), 0, st, ma);
+}
+
 }  // namespace gjx
 
 extern "C" size_t gjx_pairwise_gauss_lse_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
@@ -253,5 +480,51 @@ extern "C" int gjx_pairwise_gauss_lse(const float* q, int64_t stride_q, int64_t 
   GJX_CHECK_LAUNCH("gjx_pairwise_gauss_lse(lse)");
   hipLaunchKernelGGL(k_pw_merge, dim3((unsigned)((n_q + kPwThreads - 1) / kPwThreads)), dim3(kPwThreads), 0, st, a);
   GJX_CHECK_LAUNCH("gjx_pairwise_gauss_lse(merge)");
+  return GJX_OK;
+}
+
+extern "C" size_t gjx_pairwise_gauss_mean_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d, int32_t dv) {
+  gjx::PwArgs a;
+  if (dv <= 0 || dv > GJX_PAIRWISE_MAX_DIM || !gjx::pw_plan(n_q, n_k, d, &a)) return 0;
+  return 8 + (sizeof(float2) + sizeof(float) * (size_t)dv) * (size_t)a.n_splits * (size_t)n_q;
+}
+
+extern "C" int gjx_pairwise_gauss_mean(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k,
+                                       int32_t d, const float* v, int64_t stride_v, int32_t dv, const float* bias, float precision,
+                                       const float* centre, float* mean, float* lse, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  using namespace gjx;
+  if (!q || !k || !v || !mean || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      dv <= 0 || stride_q < n_q || stride_k < n_k || stride_v < n_k || !(precision > 0.0f) || !(precision < INFINITY))
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_gauss_mean: bad argument");
+  if (d > GJX_PAIRWISE_MAX_DIM || dv > GJX_PAIRWISE_MAX_DIM)
+    return gjx_fail(GJX_EUNSUPPORTED, "gjx_pairwise_gauss_mean: more than GJX_PAIRWISE_MAX_DIM components");
+  PwMeanArgs ma;
+  memset(&ma, 0, sizeof(ma));
+  PwArgs& a = ma.pw;
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_gauss_mean_workspace_bytes(n_q, n_k, d, dv))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_gauss_mean: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = lse;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k; a.p = precision;
+  ma.v = v; ma.mean = mean; ma.stride_v = stride_v; ma.dv = dv;
+  ma.opart = (float*)(a.part + (size_t)a.n_splits * (size_t)n_q);
+  const unsigned n_qb = (unsigned)((n_q + kPwBlockQ - 1) / kPwBlockQ);
+  const dim3 grid(n_qb, (unsigned)a.n_splits);
+  switch ((d + 3) / 4) {
+    case 1: pw_mean_launch<1>(ma, grid, st); break;
+    case 2: pw_mean_launch<2>(ma, grid, st); break;
+    case 3: pw_mean_launch<3>(ma, grid, st); break;
+    case 4: pw_mean_launch<4>(ma, grid, st); break;
+    case 5: pw_mean_launch<5>(ma, grid, st); break;
+    case 6: pw_mean_launch<6>(ma, grid, st); break;
+    case 7: pw_mean_launch<7>(ma, grid, st); break;
+    default: pw_mean_launch<8>(ma, grid, st); break;
+  }
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_mean(mean)");
+  hipLaunchKernelGGL(k_pw_mean_merge, dim3((unsigned)((n_q + kPwThreads - 1) / kPwThreads), (unsigned)dv), dim3(kPwThreads), 0, st, ma);
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_mean(merge)");
   return GJX_OK;
 }

@@ -242,11 +242,21 @@ class ParticleHistory(LineageSmoothing):
         in ``smoothed_moments``"""
         return self._smoothed_quantiles(None, q, method)
 
-    def smoothed_pair_moments(self) -> dict:
+    def smoothed_pair_moments(self, method: str = "lineage") -> dict:
         """the lag-one smoothing expectations for t = 1 .. T-1: dict(mean f32[T-1][dx] = E[x_t], mean_prev f32[T-1][dx] = E[x_{t-1}],
         cross f32[T-1][dx][dx] = Cov[x_t, x_{t-1}] (centred), ess f32[T-1]) given y_{1:T}: one gjx_weighted_cross_moments call per
-        pair, step t-1's stored particles read through the ancestors of step t.  At most 16 components."""
-        return self._smoothed_pair_moments(None)
+        pair, step t-1's stored particles read through the ancestors of step t.  At most 16 components.  ``method`` "ffbs": the
+        FFBSm pair distribution instead of the genealogy's (``kernels.ffbs_pair_moments`` under the kept ``ffbs_weights()``): every
+        pair of stored particles carries weight, at O(T K^2 dx)."""
+        from .. import kernels
+        if method == "lineage":
+            return self._smoothed_pair_moments(None)
+        if method != "ffbs":
+            raise ValueError(f"smoothing method is 'lineage' or 'ffbs', not {method!r}")
+        w = self.ffbs_weights()
+        A_dev = torch.from_numpy(self.ssm.A).to(self.states[0].device)
+        means = [torch.matmul(A_dev, x) for x in self.states]
+        return kernels.ffbs_pair_moments(self.states, self.logw_steps, means, 1.0 / (self.ssm.q * self.ssm.q), w)
 
 
 class BootstrapFilter:

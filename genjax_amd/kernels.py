@@ -711,6 +711,29 @@ def _pairwise_rows(what: str, rows: torch.Tensor):
     return rows, stride, d, n
 
 
+def _pairwise_args(name: str, q_rows, k_rows, bias, precision, centre):
+    """the arguments pairwise_gauss_lse and pairwise_gauss_mean share, checked once
+    -> q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, precision, centre"""
+    q_rows, stride_q, d, n_q = _pairwise_rows("q_rows", q_rows)
+    k_rows, stride_k, d_k, n_k = _pairwise_rows("k_rows", k_rows)
+    if d_k != d:
+        raise ValueError(f"{name}: queries have {d} components, keys {d_k}")
+    if d > A.PAIRWISE_MAX_DIM:
+        raise ValueError(f"{name}: at most {A.PAIRWISE_MAX_DIM} components, not {d}")
+    p = float(precision)
+    if not (p > 0.0 and p < float("inf")):
+        raise ValueError(f"{name}: precision must be positive and finite, not {precision}")
+    if bias is not None:
+        if bias.dtype != torch.float32 or bias.numel() != n_k:
+            raise ValueError(f"{name}: bias must be f32[n_k]")
+        bias = bias.reshape(-1).contiguous()
+    if centre is not None:
+        if centre.dtype != torch.float32 or centre.numel() != d:
+            raise ValueError(f"{name}: centre must be f32[d]")
+        centre = centre.reshape(-1).contiguous()
+    return q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre
+
+
 def pairwise_gauss_lse(q_rows: torch.Tensor, k_rows: torch.Tensor, bias=None, precision: float = 1.0, centre=None, ws=None,
                        out=None) -> torch.Tensor:
     """gjx_pairwise_gauss_lse: queries f32[d][n_q] and keys f32[d][n_k] (SoA; views are fine as long as the column stride is 1, no
@@ -719,24 +742,9 @@ def pairwise_gauss_lse(q_rows: torch.Tensor, k_rows: torch.Tensor, bias=None, pr
     for that query alone.  ``centre`` f32[d] (None: zeros) is subtracted from both sets on the way in: it changes nothing mathematically
     and decides the accuracy (the error grows with the centred squared norms): pass the keys' mean.  d <= 32.  O(n_q n_k d) on the matrix
     cores, nothing of size n_q x n_k is stored; two launches, bit-reproducible."""
-    q_rows, stride_q, d, n_q = _pairwise_rows("q_rows", q_rows)
-    k_rows, stride_k, d_k, n_k = _pairwise_rows("k_rows", k_rows)
-    if d_k != d:
-        raise ValueError(f"pairwise_gauss_lse: queries have {d} components, keys {d_k}")
-    if d > A.PAIRWISE_MAX_DIM:
-        raise ValueError(f"pairwise_gauss_lse: at most {A.PAIRWISE_MAX_DIM} components, not {d}")
-    p = float(precision)
-    if not (p > 0.0 and p < float("inf")):
-        raise ValueError(f"pairwise_gauss_lse: precision must be positive and finite, not {precision}")
+    q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre = _pairwise_args("pairwise_gauss_lse", q_rows, k_rows, bias, precision,
+                                                                                      centre)
     dev = q_rows.device
-    if bias is not None:
-        if bias.dtype != torch.float32 or bias.numel() != n_k:
-            raise ValueError("pairwise_gauss_lse: bias must be f32[n_k]")
-        bias = bias.reshape(-1).contiguous()
-    if centre is not None:
-        if centre.dtype != torch.float32 or centre.numel() != d:
-            raise ValueError("pairwise_gauss_lse: centre must be f32[d]")
-        centre = centre.reshape(-1).contiguous()
     if out is None:
         out = torch.empty(n_q, dtype=torch.float32, device=dev)
     elif out.dtype != torch.float32 or out.numel() != n_q or not out.is_contiguous():
@@ -746,6 +754,72 @@ def pairwise_gauss_lse(q_rows: torch.Tensor, k_rows: torch.Tensor, bias=None, pr
     check(load().gjx_pairwise_gauss_lse(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(bias), p, _ptr(centre), _ptr(out),
                                         _ptr(ws), ws.numel(), _stream()), "gjx_pairwise_gauss_lse")
     return out
+
+
+def pairwise_gauss_mean(q_rows: torch.Tensor, k_rows: torch.Tensor, v_rows: torch.Tensor, bias=None, precision: float = 1.0,
+                        centre=None, ws=None, out=None, lse_out=None) -> dict:
+    """gjx_pairwise_gauss_mean: queries f32[d][n_q], keys f32[d][n_k] and values f32[dv][n_k] (SoA views as in ``pairwise_gauss_lse``)
+    -> dict(mean f32[dv][n_q], lse f32[n_q]):  mean[j][r] = sum_c softmax_c(bias[c] - 1/2 precision |q_r - k_c|^2) v[j][c], the
+    Gaussian-kernel weighted mean of the values for every query, and the log-sum-exp of the same scores.  A dead key (bias -inf or
+    NaN) is left out whatever its coordinates and values hold; no live key gives mean NaN and lse -inf; a query with a non-finite
+    coordinate gives NaN for that query alone; a live key's non-finite value makes its component of every mean NaN.  d, dv <= 32.
+    Both products on the matrix cores, nothing of size n_q x n_k is stored; two launches, bit-reproducible."""
+    name = "pairwise_gauss_mean"
+    q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre = _pairwise_args(name, q_rows, k_rows, bias, precision, centre)
+    v_rows, stride_v, dv, n_v = _pairwise_rows("v_rows", v_rows)
+    if n_v != n_k:
+        raise ValueError(f"{name}: {n_k} keys, {n_v} values")
+    if dv > A.PAIRWISE_MAX_DIM:
+        raise ValueError(f"{name}: at most {A.PAIRWISE_MAX_DIM} value components, not {dv}")
+    dev = q_rows.device
+    if out is None:
+        out = torch.empty((dv, n_q), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (dv, n_q) or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous f32[dv][n_q]")
+    if lse_out is None:
+        lse_out = torch.empty(n_q, dtype=torch.float32, device=dev)
+    elif lse_out.dtype != torch.float32 or lse_out.numel() != n_q or not lse_out.is_contiguous():
+        raise ValueError(f"{name}: lse_out must be a contiguous f32[n_q]")
+    if ws is None:
+        ws = torch.empty(load().gjx_pairwise_gauss_mean_workspace_bytes(n_q, n_k, d, dv), dtype=torch.uint8, device=dev)   # partials only
+    check(load().gjx_pairwise_gauss_mean(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(v_rows), stride_v, dv, _ptr(bias),
+                                         p, _ptr(centre), _ptr(out), _ptr(lse_out), _ptr(ws), ws.numel(), _stream()),
+          "gjx_pairwise_gauss_mean")
+    return {"mean": out, "lse": lse_out}
+
+
+def ffbs_pair_moments(states, logw_steps, means, precision: float, weights=None) -> dict:
+    """The lag-one expectations of marginal backward smoothing (FFBSm) for t = 1 .. T-1 -> dict(mean f32[T-1][d] = E[x_t], mean_prev
+    f32[T-1][d] = E[x_{t-1}], cross f32[T-1][d][d] = Cov[x_t, x_{t-1}] (centred), ess f32[T-1]) given y_{1:T}; arguments as
+    ``ffbs_weights``, whose output ``weights`` f32[T][K] is (computed when None).  The pair (x_t^j, x_{t-1}^i) has weight
+    w_{t|T}^j w_{t-1}^i f(x_t^j | x_{t-1}^i) / sum_l w_{t-1}^l f(x_t^j | x_{t-1}^l), so E[x_t x_{t-1}^T] = sum_j w_{t|T}^j x_t^j c_j^T with
+    c_j the conditional mean of the parent given child j: one ``pairwise_gauss_mean`` call per step (queries states[t], keys
+    means[t-1], values states[t-1], bias the normalised logw_steps[t-1], centre the weighted mean of states[t]), then the T-1 tables
+    of c go through one ``weighted_cross_moments_steps`` call under log weights[t]; mean_prev is E[c] (tower rule).  At most 16
+    components.  O(T K^2 d); outputs and workspace are allocated once, nothing is read back."""
+    T = len(states)
+    if T == 0 or len(logw_steps) != T or len(means) != T:
+        raise ValueError("ffbs_pair_moments: states, logw_steps and means must have one entry per step")
+    d, K = int(states[0].shape[0]), int(states[0].shape[1])
+    dev = states[0].device
+    _cross_rows("ffbs_pair_moments", "states", states[0])                     # (at most 16 rows: raised here as the moments call does)
+    if weights is None:
+        weights = ffbs_weights(states, logw_steps, means, precision)
+    if T == 1:
+        e = lambda *s: torch.empty((0,) + s, dtype=torch.float32, device=dev)
+        return {"mean": e(d), "mean_prev": e(d), "cross": e(d, d), "ess": e()}
+    ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
+    cond = torch.empty((T - 1, d, K), dtype=torch.float32, device=dev)        # c: the parents' conditional means, one table per pair
+    lse = torch.empty(K, dtype=torch.float32, device=dev)
+    ws = torch.empty(load().gjx_pairwise_gauss_mean_workspace_bytes(K, K, d, d), dtype=torch.uint8, device=dev)
+    for t in range(1, T):
+        lw = torch.zeros(K, dtype=torch.float32, device=dev) if logw_steps[t - 1] is None else logw_steps[t - 1].reshape(-1)
+        lw = torch.where(torch.isnan(lw), ninf, lw)
+        centre = weighted_moments(states[t], logw_steps[t], "mean")["mean"]
+        pairwise_gauss_mean(states[t], means[t - 1], states[t - 1], lw - torch.logsumexp(lw, 0), precision, centre, ws, out=cond[t - 1],
+                            lse_out=lse)
+    m = weighted_cross_moments_steps([(states[t], cond[t - 1], None, t) for t in range(1, T)], torch.log(weights))
+    return {"mean": m["mean_a"], "mean_prev": m["mean_b"], "cross": m["cross"], "ess": m["stats"][:, 3]}
 
 
 def ffbs_weights(states, logw_steps, means, precision: float) -> torch.Tensor:

@@ -1155,6 +1155,42 @@ int gjx_pairwise_gauss_lse(const float* q /* f32[d][stride_q] */, int64_t stride
                            int64_t stride_k, int64_t n_k, int32_t d, const float* bias /* f32[n_k] or NULL */, float precision,
                            const float* centre /* f32[d] or NULL */, float* out /* f32[n_q] */, void* workspace,
                            size_t workspace_bytes, void* stream);
+/* Pairwise Gaussian weighted mean: the softmax over the scores of gjx_pairwise_gauss_lse applied to a value matrix (attention with a
+ * Gaussian kernel).  For r < n_q, c < n_k, j < dv, with s_rc = bias[c] - 1/2 precision |q_r - k_c|^2:
+ *     lse[r]     = log sum_c exp(s_rc)
+ *     mean[j][r] = sum_c exp(s_rc - lse[r]) v[j][c]
+ * It is the missing part of the FFBSm lag-one pair distribution: the pair (x_t^j, x_{t-1}^i) has weight
+ * w_{t|T}^j w_{t-1}^i f(x_t^j | x_{t-1}^i) / sum_l w_{t-1}^l f(x_t^j | x_{t-1}^l), so with queries x_t, keys m(x_{t-1}), bias lw_{t-1}
+ * and values x_{t-1}, mean[.][j] = c_j is the conditional mean of the parent given child j, and E[x_t x_{t-1}^T | y_{1:T}] =
+ * sum_j w_{t|T}^j x_t^j c_j^T: gjx_weighted_cross_moments on (x_t, c) under log w_{t|T} gives Cov[x_t, x_{t-1}] as `cross` and, by
+ * the tower rule, E[x_{t-1} | y_{1:T}] as `mean_b`.  Nothing of size n_q x n_k is stored.
+ *   q, k, d, bias, precision, centre   exactly as in gjx_pairwise_gauss_lse
+ *   v          f32[dv][stride_v], stride_v >= n_k: the values, one row per component (SoA, dword loads, no alignment asked);
+ *              1 <= dv <= GJX_PAIRWISE_MAX_DIM
+ *   mean       f32[dv][n_q]
+ *   lse        f32[n_q], or NULL.  It agrees with gjx_pairwise_gauss_lse's output to that call's error, not bit for bit (the running
+ *              maximum is shared between a query's lanes here).
+ * Semantics, next to the lse's.  A dead key (bias -inf or NaN) contributes nothing whatever its coordinates AND values hold: both
+ * are staged as zeros.  No live key: lse = -inf, mean = NaN (0 / 0).  A query with a non-finite coordinate: NaN in lse and in every
+ * mean[.][r] of that query alone.  A poisoned live key (non-finite centred norm): NaN everywhere, as for the lse.  A LIVE key's
+ * non-finite value v[j][c] is staged as NaN and makes mean[j][.] NaN for every query, in that component alone, whether or not the
+ * key's weight underflows for a query.
+ * Device work.  Two plain launches on `stream`, grid and key splits as gjx_pairwise_gauss_lse plans them.  Scores as there.  A lane's
+ * four score accumulators are four consecutive keys of one query, which is the B-operand layout of a second v_mfma_f32_16x16x4_f32:
+ * exp2(score - max) is multiplied with the staged values (the A operand, read from LDS [j][key], row stride 68 floats, one 16-byte
+ * read per 16 keys and 16 value rows) into O^T[j][query], 4 ceil(dv / 16) accumulators per 16 queries held for the whole key loop and
+ * rescaled once per staged tile.  The maximum of a query is exchanged between its four lanes (v_permlane16_swap / v_permlane32_swap)
+ * before the exponentials.  Every (query, split) leaves (max, sum, O^T[dv]) in the workspace; the second launch, one thread per
+ * (query, j), folds the splits in index order and divides.  No atomics, every sum in an order fixed by the shape: bit-reproducible.
+ * Refusals as gjx_pairwise_gauss_lse, and: GJX_EINVAL for a NULL v or mean, dv <= 0 or stride_v < n_k; GJX_EUNSUPPORTED for d or dv >
+ * GJX_PAIRWISE_MAX_DIM; GJX_EWORKSPACE below gjx_pairwise_gauss_mean_workspace_bytes(n_q, n_k, d, dv) (0 for shapes the call
+ * refuses).  The workspace needs no initialisation.  Nothing is launched on a refusal. */
+size_t gjx_pairwise_gauss_mean_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d, int32_t dv);
+int gjx_pairwise_gauss_mean(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q, const float* k /* f32[d][stride_k] */,
+                            int64_t stride_k, int64_t n_k, int32_t d, const float* v /* f32[dv][stride_v] */, int64_t stride_v,
+                            int32_t dv, const float* bias /* f32[n_k] or NULL */, float precision,
+                            const float* centre /* f32[d] or NULL */, float* mean /* f32[dv][n_q] */, float* lse /* f32[n_q] or NULL */,
+                            void* workspace, size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
