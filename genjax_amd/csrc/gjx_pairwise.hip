@@ -441,6 +441,256 @@ static void pw_mean_launch(const PwMeanArgs& ma, dim3 grid, hipStream_t st) {
   else hipLaunchKernelGGL((k_pw_mean<DC, 2>), grid, dim3(kPwThreads), 0, st, ma);
 }
 
+// ---- gjx_pairwise_gauss_pick:  pick[r] = the first key c with  sum_{c' <= c} e_rc' >= u_r sum_c e_rc,  e_rc = exp(score(r, c)) ----
+//
+// Backward simulation (FFBSi): one categorical draw per query over the scores of k_pw_lse, by inverse CDF in key-index order with the
+// caller's uniform.  Four launches, nothing of size n_q x n_k stored, no atomics, no block waits for another.
+//   1. k_pw_lse as it is: part[split][query] = (max, sum).
+//   2. k_pw_pick_plan, one thread per query: folds the splits in index order (as k_pw_merge) to L = max + log2(sum) in the loop's
+//      units, and writes the lse if asked.  With L known the mass of split y in units of the total is sum_y 2^(max_y - L); the splits
+//      are walked in index order to the first positive one whose prefix interval reaches the target.  The target is u, but +inf for
+//      u >= 1 (nothing ever reaches it: every level falls back to its last positive entry) and 0 for u <= 0 (the first positive entry
+//      reaches it).  That split OWNS the query; the target left inside it (`resid`) goes to the workspace.  A query without a pick
+//      (no live key, a poisoned key, a non-finite query, a NaN u) is owned by nobody and gets -1 here.
+//   3. k_pw_pick<DC>: grid, plan, staging and MFMAs of k_pw_lse, but exp2(acc - L) <= 1 needs no running maximum and no rescaling.
+//      A CHUNK is one staged tile of 64 keys: a lane adds its 16 keys, the query's four lanes are added with two
+//      v_permlane{16,32}_swap (the same bits in all four), and the running cumulative is compared with the residual target: the first
+//      positive chunk that reaches it is recorded together with the cumulative before it, else the last positive chunk.  Only the
+//      lanes of the owning split hold a finite L, and a 16-query group of which this split owns nobody is skipped (wave-uniform): with
+//      S splits about (1 - 1/S)^16 of the matrix work goes away.  The split's maximum key contributes exp2(max_y - L), the very number
+//      that was positive in launch 2, so an owned query always records a positive chunk.
+//   4. k_pw_pick_finish, one thread per query: the recorded chunk's 64 scores again in plain VALU in key order (same centring, same
+//      kb), the cumulative walked to the first key with positive mass that reaches resid - before; else the last key with positive
+//      mass; and should the VALU scores of a chunk of vanishing mass all underflow, the chunk's largest score.  64 d multiply-adds a
+//      query.
+// Chunk-then-key in index order is inverse-CDF in index order.  Registers per 16-query group next to qf: L, residual, cumulative,
+// recorded chunk and the cumulative before it.  LDS: k_pw_lse's.
+struct PwPickArgs {
+  PwArgs pw;               // pw.out: the lse, or NULL
+  const float* u;
+  int32_t* pick;
+  float* L;                // [n_q] log2 of the total, without the query's own term
+  float* resid;            // [n_q] the target inside the owning split, in units of the total
+  int32_t* own;            // [n_q] the owning split; -1: no pick
+  int32_t* rchunk;         // [n_q] the recorded tile, written by the owning split's block
+  float* rbefore;          // [n_q] the split's cumulative before that tile
+};
+
+// the sum over the four lanes l % 16 + {0, 16, 32, 48}, the same bits in all four (a + b is b + a)
+GJX_DEV float pw_rows_sum(float x) {
+#if __has_builtin(__builtin_amdgcn_permlane16_swap) && __has_builtin(__builtin_amdgcn_permlane32_swap)
+  unsigned u = __float_as_uint(x);
+  auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);          // {r0 r0 r2 r2}, {r1 r1 r3 r3}
+  x = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+  u = __float_as_uint(x);
+  auto b = __builtin_amdgcn_permlane32_swap(u, u, false, false);          // {lo lo}, {hi hi}
+  return __uint_as_float(b[0]) + __uint_as_float(b[1]);
+#else
+  x += __shfl_xor(x, 16, 64);
+  return x + __shfl_xor(x, 32, 64);
+#endif
+}
+
+__global__ __launch_bounds__(kPwThreads) void k_pw_pick_plan(const PwPickArgs pa) {
+  const PwArgs& a = pa.pw;
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  if (r >= a.n_q) return;
+  float q2 = 0.0f;
+  for (int i = 0; i < a.d; ++i) {
+    const float x = a.q[(int64_t)i * a.stride_q + r] - (a.centre ? a.centre[i] : 0.0f);
+    q2 = fmaf(x, x, q2);
+  }
+  float m = -INFINITY, s = 0.0f;
+  for (int y = 0; y < a.n_splits; ++y) {
+    const float2 p = a.part[(int64_t)y * a.n_q + r];
+    pw_fold(m, s, p.x, p.y);
+  }
+  const float L = m + __builtin_amdgcn_logf(s);
+  if (a.out) a.out[r] = q2 < INFINITY ? L * kPwLn2 - 0.5f * a.p * q2 : NAN;
+  const float u = pa.u[r];
+  int own = -1;
+  float resid = 0.0f;
+  if (q2 < INFINITY && m > -INFINITY && s == s && u == u) {
+    const float target = u >= 1.0f ? INFINITY : fmaxf(u, 0.0f);
+    float cum = 0.0f;
+    for (int y = 0; y < a.n_splits; ++y) {
+      const float2 p = a.part[(int64_t)y * a.n_q + r];
+      const float mass = p.y * __builtin_amdgcn_exp2f(p.x - L);
+      if (mass > 0.0f) {
+        own = y;
+        resid = target - cum;
+        if (cum + mass >= target) break;
+      }
+      cum += mass;
+    }
+  }
+  pa.L[r] = L;
+  pa.resid[r] = resid;
+  pa.own[r] = own;
+  if (own < 0) pa.pick[r] = -1;
+}
+
+template <int DC>
+__global__ __launch_bounds__(kPwThreads) void k_pw_pick(const PwPickArgs pa) {
+  const PwArgs& a = pa.pw;
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sb[2][kPwTile];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;
+  const int skey = tid >> 2, spart = tid & 3;
+
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  const float ps = a.p * kPwLog2e;
+  float qf[kPwGroups][DC];
+  float scen[DC];
+#pragma unroll
+  for (int c = 0; c < DC; ++c) {
+    const int dq = 4 * c + quad, ds = 4 * c + spart;
+    const float cen = (a.centre && dq < a.d) ? a.centre[dq] : 0.0f;
+    scen[c] = (a.centre && ds < a.d) ? a.centre[ds] : 0.0f;
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      const int qi = q0 + 16 * g + col;
+      qf[g][c] = (dq < a.d && qi < a.n_q) ? (a.q[(int64_t)dq * a.stride_q + qi] - cen) * ps : 0.0f;
+    }
+  }
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  // per group: the query's L and residual target where this split owns it, the running cumulative, the record
+  float L[kPwGroups], want[kPwGroups], cum[kPwGroups], rb[kPwGroups];
+  int rt[kPwGroups];
+  bool mine[kPwGroups], act[kPwGroups], done[kPwGroups];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    const int qi = q0 + 16 * g + col;
+    mine[g] = qi < a.n_q && pa.own[qi] == (int)blockIdx.y;
+    act[g] = __any(mine[g]) != 0;                         // wave-uniform: somebody in the group is owned here
+    L[g] = mine[g] ? pa.L[qi] : INFINITY;                 // (+inf: every exponential of a query owned elsewhere is 0)
+    want[g] = mine[g] ? pa.resid[qi] : INFINITY;
+    cum[g] = rb[g] = 0.0f;
+    rt[g] = t0;
+    done[g] = false;
+  }
+
+  float v[DC], b;
+  auto load = [&](int tile) {
+    const int key = tile * kPwTile + skey;
+    const bool in = key < a.n_k;
+    b = in ? (a.bias ? a.bias[key] : 0.0f) : -INFINITY;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int ds = 4 * c + spart;
+      v[c] = (in && ds < a.d) ? a.k[(int64_t)ds * a.stride_k + key] - scen[c] : 0.0f;
+    }
+  };
+  auto store = [&](int buf) {
+    float k2 = 0.0f;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) k2 = fmaf(v[c], v[c], k2);
+    k2 = quad_sum(k2);
+    const bool dead = !(b > -INFINITY);                   // -inf or NaN
+    const bool zero = dead || !(k2 < INFINITY);
+#pragma unroll
+    for (int c = 0; c < DC; ++c) sk[buf][(4 * c + spart) * kPwLd + skey] = zero ? 0.0f : v[c];
+    if (spart == 0) sb[buf][skey] = dead ? -INFINITY : (zero ? NAN : (b - 0.5f * a.p * k2) * kPwLog2e);
+  };
+
+  load(t0);
+  store(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) load(t + 1);
+    float af[4][DC];
+    pw_v4f seed[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      seed[u] = *reinterpret_cast<const pw_v4f*>(&sb[buf][16 * u + 4 * quad]);
+#pragma unroll
+      for (int c = 0; c < DC; ++c) af[u][c] = sk[buf][(4 * c + quad) * kPwLd + 16 * u + col];
+    }
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      if (!act[g]) continue;
+      pw_v4f acc[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc[u] = seed[u];
+#pragma unroll
+        for (int c = 0; c < DC; ++c) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][c], qf[g][c], acc[u], 0, 0, 0);
+      }
+      float e = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) e += __builtin_amdgcn_exp2f(acc[u][r] - L[g]);
+      e = pw_rows_sum(e);                                 // the chunk's mass, the same bits in the query's four lanes
+      if (!done[g] && e > 0.0f) {
+        rt[g] = t;
+        rb[g] = cum[g];
+        done[g] = cum[g] + e >= want[g];
+      }
+      cum[g] += e;
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    const int qi = q0 + 16 * g + col;
+    if (quad == 0 && mine[g]) {
+      pa.rchunk[qi] = rt[g];
+      pa.rbefore[qi] = rb[g];
+    }
+  }
+}
+
+// one thread per query: the recorded chunk key by key
+__global__ __launch_bounds__(kPwThreads) void k_pw_pick_finish(const PwPickArgs pa) {
+  const PwArgs& a = pa.pw;
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  if (r >= a.n_q || pa.own[r] < 0) return;                // (no pick: k_pw_pick_plan wrote the -1)
+  const float ps = a.p * kPwLog2e;
+  float qv[GJX_PAIRWISE_MAX_DIM];
+#pragma unroll
+  for (int i = 0; i < GJX_PAIRWISE_MAX_DIM; ++i)
+    qv[i] = i < a.d ? (a.q[(int64_t)i * a.stride_q + r] - (a.centre ? a.centre[i] : 0.0f)) * ps : 0.0f;
+  const float L = pa.L[r], want = pa.resid[r] - pa.rbefore[r];
+  const int t = min(max(pa.rchunk[r], 0), a.n_tiles - 1);
+  const int c0 = t * kPwTile, c1 = min(c0 + kPwTile, a.n_k);
+  float cum = 0.0f, top = -INFINITY;
+  int pick = -1, last = -1, topc = -1;
+  for (int c = c0; c < c1 && pick < 0; ++c) {
+    const float b = a.bias ? a.bias[c] : 0.0f;
+    if (!(b > -INFINITY)) continue;                       // dead
+    float k2 = 0.0f, dot = 0.0f;
+#pragma unroll
+    for (int i = 0; i < GJX_PAIRWISE_MAX_DIM; ++i) {
+      if (i >= a.d) break;
+      const float x = a.k[(int64_t)i * a.stride_k + c] - (a.centre ? a.centre[i] : 0.0f);
+      k2 = fmaf(x, x, k2);
+      dot = fmaf(x, qv[i], dot);
+    }
+    const float sc = (b - 0.5f * a.p * k2) * kPwLog2e + dot;
+    if (sc > top) { top = sc; topc = c; }
+    const float e = __builtin_amdgcn_exp2f(sc - L);
+    if (e > 0.0f) {
+      last = c;
+      cum += e;
+      if (cum >= want) pick = c;
+    }
+  }
+  pa.pick[r] = pick >= 0 ? pick : (last >= 0 ? last : topc);
+}
+
+template <int DC>
+static void pw_pick_launch(const PwPickArgs& pa, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL(k_pw_pick<DC>, grid, dim3(kPwThreads), 0, st, pa);
+}
+
 }  // namespace gjx
 
 extern "C" size_t gjx_pairwise_gauss_lse_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
@@ -526,5 +776,66 @@ extern "C" int gjx_pairwise_gauss_mean(const float* q, int64_t stride_q, int64_t
   GJX_CHECK_LAUNCH("gjx_pairwise_gauss_mean(mean)");
   hipLaunchKernelGGL(k_pw_mean_merge, dim3((unsigned)((n_q + kPwThreads - 1) / kPwThreads), (unsigned)dv), dim3(kPwThreads), 0, st, ma);
   GJX_CHECK_LAUNCH("gjx_pairwise_gauss_mean(merge)");
+  return GJX_OK;
+}
+
+extern "C" size_t gjx_pairwise_gauss_pick_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
+  gjx::PwArgs a;
+  if (!gjx::pw_plan(n_q, n_k, d, &a)) return 0;
+  return 8 + (sizeof(float2) * (size_t)a.n_splits + 5 * sizeof(float)) * (size_t)n_q;
+}
+
+extern "C" int gjx_pairwise_gauss_pick(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k,
+                                       int32_t d, const float* bias, float precision, const float* centre, const float* u, int32_t* pick,
+                                       float* lse, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace gjx;
+  if (!q || !k || !u || !pick || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      stride_q < n_q || stride_k < n_k || !(precision > 0.0f) || !(precision < INFINITY))
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_gauss_pick: bad argument");
+  if (d > GJX_PAIRWISE_MAX_DIM) return gjx_fail(GJX_EUNSUPPORTED, "gjx_pairwise_gauss_pick: more than GJX_PAIRWISE_MAX_DIM components");
+  PwPickArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  PwArgs& a = pa.pw;
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_gauss_pick_workspace_bytes(n_q, n_k, d))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_gauss_pick: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = lse;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k; a.p = precision;
+  pa.u = u; pa.pick = pick;
+  pa.L = (float*)(a.part + (size_t)a.n_splits * (size_t)n_q);
+  pa.resid = pa.L + n_q;
+  pa.rbefore = pa.resid + n_q;
+  pa.own = (int32_t*)(pa.rbefore + n_q);
+  pa.rchunk = pa.own + n_q;
+  const dim3 grid((unsigned)((n_q + kPwBlockQ - 1) / kPwBlockQ), (unsigned)a.n_splits);
+  const dim3 per_query((unsigned)((n_q + kPwThreads - 1) / kPwThreads));
+  switch ((d + 3) / 4) {
+    case 1: pw_launch<1>(a, grid, st); break;
+    case 2: pw_launch<2>(a, grid, st); break;
+    case 3: pw_launch<3>(a, grid, st); break;
+    case 4: pw_launch<4>(a, grid, st); break;
+    case 5: pw_launch<5>(a, grid, st); break;
+    case 6: pw_launch<6>(a, grid, st); break;
+    case 7: pw_launch<7>(a, grid, st); break;
+    default: pw_launch<8>(a, grid, st); break;
+  }
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_pick(lse)");
+  hipLaunchKernelGGL(k_pw_pick_plan, per_query, dim3(kPwThreads), 0, st, pa);
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_pick(plan)");
+  switch ((d + 3) / 4) {
+    case 1: pw_pick_launch<1>(pa, grid, st); break;
+    case 2: pw_pick_launch<2>(pa, grid, st); break;
+    case 3: pw_pick_launch<3>(pa, grid, st); break;
+    case 4: pw_pick_launch<4>(pa, grid, st); break;
+    case 5: pw_pick_launch<5>(pa, grid, st); break;
+    case 6: pw_pick_launch<6>(pa, grid, st); break;
+    case 7: pw_pick_launch<7>(pa, grid, st); break;
+    default: pw_pick_launch<8>(pa, grid, st); break;
+  }
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_pick(pick)");
+  hipLaunchKernelGGL(k_pw_pick_finish, per_query, dim3(kPwThreads), 0, st, pa);
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_pick(finish)");
   return GJX_OK;
 }

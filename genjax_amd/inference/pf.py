@@ -221,6 +221,27 @@ class ParticleHistory(LineageSmoothing):
             self._ffbs_w = kernels.ffbs_weights(self.states, self.logw_steps, means, 1.0 / (self.ssm.q * self.ssm.q))
         return self._ffbs_w
 
+    def backward_paths(self, key, n_paths=None):
+        """-> f32[T][dx][n_paths] (default n_paths = K): joint draws from p(x_{0:T-1} | y_{1:T}) by backward simulation (FFBSi) —
+        ``kernels.ffbs_sample_paths`` with the model's transition, means[t] = A x_t and precision 1 / q^2 as in ``ffbs_weights``.
+        Every path may pass through any of a step's K stored particles, where ``paths()`` only follows the surviving ancestors; the
+        price is O(T n_paths K dx).  ``backward_indices`` holds the particle indices i32[T][n_paths] of the last call.  Refusals as
+        ``ffbs_weights``."""
+        import torch
+        from .. import kernels
+        if self._moved:
+            raise NotImplementedError("backward_paths: a resample-move history stores moved parents; its transition is not additive-Gaussian")
+        if self.ssm is None or len(self.logw_steps) != len(self.states):
+            raise ValueError("backward_paths: the history lacks the model or the per-step log-weights (BootstrapFilter.run records them)")
+        n = int(self.states[-1].shape[1] if n_paths is None else n_paths)
+        if n <= 0:
+            raise ValueError(f"backward_paths: n_paths must be positive, not {n_paths}")
+        A_dev = torch.from_numpy(self.ssm.A).to(self.states[0].device)
+        means = [torch.matmul(A_dev, x) for x in self.states]
+        res = kernels.ffbs_sample_paths(self.states, self.logw_steps, means, 1.0 / (self.ssm.q * self.ssm.q), key, n)
+        self.backward_indices = res["idx"]
+        return res["paths"]
+
     def _smoothing_logw(self, method: str = "lineage"):
         import torch
         if method == "lineage":

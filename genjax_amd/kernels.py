@@ -788,6 +788,72 @@ def pairwise_gauss_mean(q_rows: torch.Tensor, k_rows: torch.Tensor, v_rows: torc
     return {"mean": out, "lse": lse_out}
 
 
+def pairwise_gauss_pick(q_rows: torch.Tensor, k_rows: torch.Tensor, u: torch.Tensor, bias=None, precision: float = 1.0, centre=None,
+                        ws=None, out=None, lse_out=None) -> dict:
+    """gjx_pairwise_gauss_pick: queries f32[d][n_q], keys f32[d][n_k] (SoA views as in ``pairwise_gauss_lse``) and one uniform per
+    query ``u`` f32[n_q] -> dict(pick i32[n_q], lse f32[n_q]): pick[r] is the smallest key index c at which the cumulative of
+    exp(bias[c] - 1/2 precision |q_r - k_c|^2) over the keys in index order reaches u[r] times its total — a categorical draw per query
+    by inverse CDF, the random numbers being the caller's.  Dead keys (bias -inf or NaN) are never picked; u <= 0 gives the first key
+    with positive mass, u >= 1 the last; -1 where there is nothing to pick (no live key, a non-finite query, a poisoned live key, a NaN
+    u).  d <= 32.  Two passes on the matrix cores, nothing of size n_q x n_k is stored; four launches, bit-reproducible."""
+    name = "pairwise_gauss_pick"
+    q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre = _pairwise_args(name, q_rows, k_rows, bias, precision, centre)
+    if u.dtype != torch.float32 or u.dim() != 1 or u.numel() != n_q or not u.is_contiguous():
+        raise ValueError(f"{name}: u must be a contiguous f32[n_q]")
+    dev = q_rows.device
+    if out is None:
+        out = torch.empty(n_q, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.numel() != n_q or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous i32[n_q]")
+    if lse_out is None:
+        lse_out = torch.empty(n_q, dtype=torch.float32, device=dev)
+    elif lse_out.dtype != torch.float32 or lse_out.numel() != n_q or not lse_out.is_contiguous():
+        raise ValueError(f"{name}: lse_out must be a contiguous f32[n_q]")
+    if ws is None:
+        ws = torch.empty(load().gjx_pairwise_gauss_pick_workspace_bytes(n_q, n_k, d), dtype=torch.uint8, device=dev)   # partials only
+    check(load().gjx_pairwise_gauss_pick(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(bias), p, _ptr(centre), _ptr(u),
+                                         _ptr(out), _ptr(lse_out), _ptr(ws), ws.numel(), _stream()), "gjx_pairwise_gauss_pick")
+    return {"pick": out, "lse": lse_out}
+
+
+def ffbs_sample_paths(states, logw_steps, means, precision: float, key, n_paths: int) -> dict:
+    """Backward simulation (FFBSi, Godsill, Doucet & West 2004): ``n_paths`` joint draws from p(x_{0:T-1} | y_{1:T}) over the stored
+    particles -> dict(idx i32[T][n_paths], paths f32[T][d][n_paths]), paths[t] = states[t][:, idx[t]]; arguments as ``ffbs_weights``.
+    idx[T-1] is a multinomial draw from the last step's filtering weights (``weight_cumsum`` + ``resample_multinomial`` under
+    fold_in(key, T-1)); then for t = T-2 .. 0 the parent of every path is drawn with probability proportional to
+    w_t^i f(x_{t+1} | x_t^i) by one ``pairwise_gauss_pick`` call: queries paths[t+1], keys means[t], bias the normalised logw_steps[t],
+    centre the weighted mean of states[t+1], uniforms (bits >> 8 + 1/2) 2^-24 of the first word of threefry2x32(key, n_paths, ctr_hi=t),
+    rounded to float32 and kept below 1: strictly inside (0, 1), made on the device.
+    Unlike ``ParticleHistory.paths`` every step's K particles can be reached.  O(T n_paths K d); outputs and workspace are allocated
+    once, nothing is read back."""
+    T, n = len(states), int(n_paths)
+    if T == 0 or len(logw_steps) != T or len(means) != T:
+        raise ValueError("ffbs_sample_paths: states, logw_steps and means must have one entry per step")
+    if n <= 0:
+        raise ValueError(f"ffbs_sample_paths: n_paths must be positive, not {n_paths}")
+    from .core import fold_in
+    d, K = int(states[0].shape[0]), int(states[0].shape[1])
+    dev = states[0].device
+    ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
+    lw_filter = [torch.zeros(K, dtype=torch.float32, device=dev) if lw is None else lw.reshape(-1) for lw in logw_steps]
+    idx = torch.empty((T, n), dtype=torch.int32, device=dev)
+    paths = torch.full((T, d, n), float("nan"), dtype=torch.float32, device=dev)   # (a path without a parent, idx -1, stays NaN)
+    cum, bt = weight_cumsum(lw_filter[T - 1], True, logsumexp(lw_filter[T - 1]))
+    idx[T - 1] = resample_multinomial(cum, bt, fold_in(key, T - 1), n)
+    gather_rows(states[T - 1], idx[T - 1], paths[T - 1])
+    if T > 1:
+        ws = torch.empty(load().gjx_pairwise_gauss_pick_workspace_bytes(n, K, d), dtype=torch.uint8, device=dev)
+        lse = torch.empty(n, dtype=torch.float32, device=dev)
+    for t in range(T - 2, -1, -1):
+        lw = torch.where(torch.isnan(lw_filter[t]), ninf, lw_filter[t])           # (a NaN weight is dead, as everywhere in the library)
+        centre = weighted_moments(states[t + 1], logw_steps[t + 1], "mean")["mean"]
+        bits = threefry2x32(key, n, ctr_hi=t, device=dev)[:, 0]
+        u = ((bits >> 8) & 0xFFFFFF).to(torch.float64).add_(0.5).mul_(2.0 ** -24).to(torch.float32).clamp_(max=1.0 - 2.0 ** -24)
+        pairwise_gauss_pick(paths[t + 1], means[t], u, lw - torch.logsumexp(lw, 0), precision, centre, ws, out=idx[t], lse_out=lse)
+        gather_rows(states[t], idx[t], paths[t])
+    return {"idx": idx, "paths": paths}
+
+
 def ffbs_pair_moments(states, logw_steps, means, precision: float, weights=None) -> dict:
     """The lag-one expectations of marginal backward smoothing (FFBSm) for t = 1 .. T-1 -> dict(mean f32[T-1][d] = E[x_t], mean_prev
     f32[T-1][d] = E[x_{t-1}], cross f32[T-1][d][d] = Cov[x_t, x_{t-1}] (centred), ess f32[T-1]) given y_{1:T}; arguments as

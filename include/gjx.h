@@ -1191,6 +1191,39 @@ int gjx_pairwise_gauss_mean(const float* q /* f32[d][stride_q] */, int64_t strid
                             int32_t dv, const float* bias /* f32[n_k] or NULL */, float precision,
                             const float* centre /* f32[d] or NULL */, float* mean /* f32[dv][n_q] */, float* lse /* f32[n_q] or NULL */,
                             void* workspace, size_t workspace_bytes, void* stream);
+/* Pairwise Gaussian pick: one categorical draw per query over the scores of gjx_pairwise_gauss_lse, the device part of backward
+ * simulation (FFBSi, Godsill, Doucet & West 2004): with queries x_{t+1} of the paths drawn so far, keys m(x_t^i) and bias lw_t, pick[r]
+ * is a parent index drawn with probability proportional to w_t^i f(x_{t+1} | x_t^i).  With s_rc = bias[c] - 1/2 precision |q_r - k_c|^2:
+ *     lse[r]  = log sum_c exp(s_rc)
+ *     e_rc    = exp(s_rc - lse[r]) for a live key, 0 for a dead one (bias -inf or NaN, as everywhere)
+ *     pick[r] = the smallest c with  sum_{c' <= c} e_rc' >= u_r sum_c e_rc
+ * that is inverse-CDF sampling in key-index order with ONE uniform per query supplied by the caller: the random numbers stay outside the
+ * kernel, the call is deterministic.  The picked key always has positive mass in the kernel's own arithmetic: u_r <= 0 gives the first
+ * such key, u_r >= 1 the last, and where rounding leaves the cumulative short of the target the last such key is picked.  (The one
+ * exception: a chunk of 64 keys whose mass is at the underflow threshold of float32 relative to the total may be entered by its
+ * largest score.)  pick[r] = -1: no live key; a query with a non-finite coordinate; a poisoned live key (as gjx_pairwise_gauss_lse
+ * defines it: then every query); a NaN u_r.
+ *   q, k, d, bias, precision, centre   exactly as in gjx_pairwise_gauss_lse
+ *   u          f32[n_q], the uniforms
+ *   pick       i32[n_q]
+ *   lse        f32[n_q], or NULL: gjx_pairwise_gauss_lse's output, by that call's rules
+ * Device work.  Four plain launches on `stream`, nothing read back, nothing of size n_q x n_k stored, no atomics, no block waits for
+ * another.  (1) gjx_pairwise_gauss_lse's first launch, unchanged: (max, sum) per (query, key split).  (2) One thread per query folds
+ * the splits in index order, which gives the total, and walks the splits' masses in index order to the one split whose prefix
+ * interval holds u_r times the total: that split owns the query.  (3) The grid and matrix products of launch 1 again, but with the
+ * total known the exponentials need no running maximum; the masses of 64-key chunks (one staged tile; a query's four lanes added by
+ * v_permlane16_swap / v_permlane32_swap) are accumulated in index order and the owning split's block records the first chunk that
+ * reaches the residual target, with the cumulative before it.  A 16-query group of which a split owns nobody is skipped.  (4) One
+ * thread per query recomputes the 64 scores of the recorded chunk in key order and walks to the key.  Chunk-then-key in index order is
+ * inverse CDF in index order.  Every sum runs in an order fixed by the shape: the output is bit-reproducible.
+ * Refusals as gjx_pairwise_gauss_lse, and GJX_EINVAL for a NULL u or pick; GJX_EWORKSPACE below
+ * gjx_pairwise_gauss_pick_workspace_bytes(n_q, n_k, d) (0 for shapes the call refuses).  The workspace needs no initialisation.
+ * Nothing is launched on a refusal. */
+size_t gjx_pairwise_gauss_pick_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d);
+int gjx_pairwise_gauss_pick(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q, const float* k /* f32[d][stride_k] */,
+                            int64_t stride_k, int64_t n_k, int32_t d, const float* bias /* f32[n_k] or NULL */, float precision,
+                            const float* centre /* f32[d] or NULL */, const float* u /* f32[n_q] */, int32_t* pick /* i32[n_q] */,
+                            float* lse /* f32[n_q] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
