@@ -59,6 +59,8 @@ MOMENTS_MEAN, MOMENTS_VAR, MOMENTS_COV = 0, 1, 2   # gjx_weighted_moments: what 
 MOMENTS_MAX_COV_ROWS = 16
 QUANTILES_MAX_LEVELS, HISTOGRAM_MAX_BINS = 16, 4096   # gjx_weighted_quantiles / gjx_weighted_histogram: the caps of one call
 PAIRWISE_MAX_DIM = 32                                  # gjx_pairwise_gauss_lse: components of a query / key at most
+PAIRWISE_DIAG_MAX_DIM = 16                             # gjx_pairwise_gauss_lse_diag: components at most (2 d features)
+PAIRWISE_PREC_KEYS, PAIRWISE_PREC_QUERIES = 0, 1       # gjx_pairwise_gauss_lse_diag: whose particles the precisions belong to
 MAX_PARAMS = 4
 
 i32, i64, u32, u64, f32, f64 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_double
@@ -220,6 +222,8 @@ PROTOTYPES = {
     "gjx_pairwise_gauss_mean": (C.c_int, [vp, i64, i64, vp, i64, i64, i32, vp, i64, i32, vp, f32, vp, vp, vp, vp, C.c_size_t, vp]),
     "gjx_pairwise_gauss_pick_workspace_bytes": (C.c_size_t, [i64, i64, i32]),
     "gjx_pairwise_gauss_pick": (C.c_int, [vp, i64, i64, vp, i64, i64, i32, vp, f32, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "gjx_pairwise_gauss_lse_diag_workspace_bytes": (C.c_size_t, [i64, i64, i32]),
+    "gjx_pairwise_gauss_lse_diag": (C.c_int, [vp, i64, i64, vp, i64, i64, i32, vp, vp, i64, i32, vp, vp, vp, C.c_size_t, vp]),
     "gjx_program_filter_source": (i64, [PP, i32, C.c_char_p, i64]),
     "gjx_program_filter_precompile": (C.c_int, [PP, i32]),
     "gjx_resample_indices_tiled": (C.c_int, [vp, i64, f64, i64, vp, vp, vp, vp, vp, C.c_size_t, vp]),

@@ -34,6 +34,9 @@
 //
 // gjx_pairwise_gauss_mean (k_pw_mean, k_pw_mean_merge; second half of this file) adds the softmax-weighted mean of a value matrix
 // over the same scores: attention with a Gaussian kernel.  Its scheme is described there.
+//
+// gjx_pairwise_gauss_lse_diag (k_pw_lse_diag, k_pw_merge_diag; last part of this file) is the log-sum-exp with one diagonal precision
+// per key or per query: the score becomes a bilinear form over 2 d features.  Its scheme and edge rules are described there.
 #include <math.h>
 #include <string.h>
 
@@ -691,6 +694,204 @@ static void pw_pick_launch(const PwPickArgs& pa, dim3 grid, hipStream_t st) {
   hipLaunchKernelGGL(k_pw_pick<DC>, grid, dim3(kPwThreads), 0, st, pa);
 }
 
+// ---- gjx_pairwise_gauss_lse_diag:  out[r] = log sum_c exp(bias[c] - 1/2 sum_j P_j(r, c) (q[j][r] - k[j][c])^2) ----
+//
+// P_j(r, c) = prec[j][c] (side KEYS) or prec[j][r] (side QUERIES): the diagonal precision belongs to one of the two particles of a
+// pair, so no scaling of the sets removes it.  With tildes for values minus `centre` the score is still bilinear, over 2 d FEATURES:
+//   KEYS:     score = [bias_c - 1/2 sum_j p_cj k~_cj^2]  +  sum_j (p_cj k~_cj) q~_rj  +  sum_j (-1/2 p_cj) q~_rj^2
+//   QUERIES:  score = bias_c  +  sum_j k~_cj (p_rj q~_rj)  +  sum_j k~_cj^2 (-1/2 p_rj)  -  1/2 sum_j p_rj q~_rj^2
+//   side     A operand (key features)   B operand (query features, x log2 e)   kb (C operand)                      added by the merge
+//   KEYS     p k~,  -1/2 p              q~,  q~^2                              (bias - 1/2 sum p k~^2) log2 e      nothing
+//   QUERIES  k~,    k~^2                p q~, -1/2 p                           bias log2 e                         -1/2 sum p q~^2
+// Feature order: f = 2 j + s, s = 0 the linear and s = 1 the quadratic feature of component j, padded with zeros to DC = ceil(2 d / 4)
+// chunks of 4 (d <= GJX_PAIRWISE_DIAG_MAX_DIM = 16: DC <= 8, the register budget k_pw_lse meets at d = 32).  A staging thread (key
+// t / 4, features 4 c + t % 4) and a B lane (features 4 c + l / 16) therefore turn ONE loaded coordinate, component 2 c + (t % 4) / 2,
+// into one feature; an odd d leaves the last chunk half empty.
+//
+// Everything else is k_pw_lse's, instruction for instruction in the key loop: keys the A operand and queries the B operand of
+// v_mfma_f32_16x16x4_f32 with f32 inputs, the running (max, sum) of a query lane-local, 256 threads, 4 groups of 16 queries per wave held
+// as B fragments for the whole kernel, 64-key tiles through double-buffered LDS (row stride 80 floats) under one barrier per tile, one
+// rescale per tile, pw_plan's grid and key splits, partials [split][n_q], a merge that folds the splits in index order.  No atomics,
+// fixed orders: bit-reproducible.  The workspace is gjx_pairwise_gauss_lse's.
+//
+// Edge rules.  A key whose bias is -inf or NaN is DEAD whatever its coordinates and precisions hold (NaN included); a key past n_k is
+// staged like a dead one: zero features, kb = -inf.  A LIVE key is POISONED (every query's output NaN) when a precision entry of its own
+// (side KEYS) is not > 0 and < inf, when a centred feature or kb is not finite (side QUERIES: a non-finite k~ or k~^2), or when its
+// bias is +inf: zero features, kb = NaN, so the A operand and the C operand's finite part are all the matrix cores see of a key.  A
+// query with a non-finite centred coordinate or square, or (side QUERIES) a precision entry that is not > 0 and < inf, gets NaN for
+// that query alone: k_pw_merge_diag decides it from q, prec and centre (a query's B fragment touches its own column only).  No live
+// key: -inf.  The normaliser 1/2 sum_j log prec is NOT part of the score: the caller folds it into bias (KEYS) or adds it to out.
+struct PwDiagArgs {
+  PwArgs pw;               // (pw.p is not read)
+  const float* prec;       // f32[d][stride_p]: a column per key (side KEYS) or per query (side QUERIES)
+  int64_t stride_p;
+  int32_t side;
+};
+
+GJX_DEV bool pw_prec_ok(float p) { return p > 0.0f && p < INFINITY; }
+
+template <int DC, int SIDE>
+__global__ __launch_bounds__(kPwThreads) void k_pw_lse_diag(const PwDiagArgs da) {
+  const PwArgs& a = da.pw;
+  constexpr bool kKeys = SIDE == GJX_PAIRWISE_PREC_KEYS;
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sb[2][kPwTile];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;            // the MFMA's view of the lane: query col, features 4 c + quad
+  const int skey = tid >> 2, spart = tid & 3;             // the staging's view: key of the tile, features 4 c + spart
+  const bool qquad = quad & 1, squad = spart & 1;         // the lane's features are the quadratic ones
+
+  // the wave's query features, for the whole kernel
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  float qf[kPwGroups][DC];
+  float scen[DC];
+#pragma unroll
+  for (int c = 0; c < DC; ++c) {
+    const int jq = 2 * c + (quad >> 1), js = 2 * c + (spart >> 1);
+    const float cen = (a.centre && jq < a.d) ? a.centre[jq] : 0.0f;
+    scen[c] = (a.centre && js < a.d) ? a.centre[js] : 0.0f;
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      const int qi = q0 + 16 * g + col;
+      float f = 0.0f;
+      if (jq < a.d && qi < a.n_q) {
+        const float x = a.q[(int64_t)jq * a.stride_q + qi] - cen;
+        if constexpr (kKeys) {
+          f = qquad ? x * x : x;
+        } else {
+          const float p = da.prec[(int64_t)jq * da.stride_p + qi];
+          f = qquad ? -0.5f * p : p * x;
+        }
+      }
+      qf[g][c] = f * kPwLog2e;
+    }
+  }
+
+  float v[DC], pv[kKeys ? DC : 1], b;
+  auto load = [&](int tile) {
+    const int key = tile * kPwTile + skey;
+    const bool in = key < a.n_k;
+    b = in ? (a.bias ? a.bias[key] : 0.0f) : -INFINITY;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int js = 2 * c + (spart >> 1);
+      const bool have = in && js < a.d;
+      v[c] = have ? a.k[(int64_t)js * a.stride_k + key] - scen[c] : 0.0f;
+      if constexpr (kKeys) pv[c] = have ? da.prec[(int64_t)js * da.stride_p + key] : 0.0f;
+    }
+  };
+  auto store = [&](int buf) {
+    // k2: sum_j p k~^2 (KEYS) or sum_j k~^2 (QUERIES, where only its finiteness is used); NaN for a precision that is not one
+    float k2 = 0.0f;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      if constexpr (kKeys) {
+        const bool pad = 2 * c + (spart >> 1) >= a.d;
+        const float p = pv[c], lin = p * v[c];
+        k2 = (pad || pw_prec_ok(p)) ? (squad ? k2 : fmaf(lin, v[c], k2)) : NAN;
+        v[c] = squad ? -0.5f * p : lin;
+      } else {
+        if (squad) {
+          v[c] *= v[c];
+          k2 += v[c];
+        }
+      }
+    }
+    k2 = quad_sum(k2);
+    const bool dead = !(b > -INFINITY);                   // -inf or NaN
+    const bool zero = dead || !(k2 < INFINITY) || !(b < INFINITY);
+#pragma unroll
+    for (int c = 0; c < DC; ++c) sk[buf][(4 * c + spart) * kPwLd + skey] = zero ? 0.0f : v[c];
+    if (spart == 0) sb[buf][skey] = dead ? -INFINITY : (zero ? NAN : (kKeys ? b - 0.5f * k2 : b) * kPwLog2e);
+  };
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  float m[kPwGroups], s[kPwGroups];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) { m[g] = -INFINITY; s[g] = 0.0f; }
+
+  load(t0);
+  store(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) load(t + 1);
+    float af[4][DC];
+    pw_v4f seed[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {                         // the tile's four 16-key subtiles
+      seed[u] = *reinterpret_cast<const pw_v4f*>(&sb[buf][16 * u + 4 * quad]);
+#pragma unroll
+      for (int c = 0; c < DC; ++c) af[u][c] = sk[buf][(4 * c + quad) * kPwLd + 16 * u + col];
+    }
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      pw_v4f acc[4];
+      float mn = m[g];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc[u] = seed[u];
+#pragma unroll
+        for (int c = 0; c < DC; ++c) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][c], qf[g][c], acc[u], 0, 0, 0);
+        mn = fmaxf(fmaxf(mn, fmaxf(acc[u][0], acc[u][1])), fmaxf(acc[u][2], acc[u][3]));        // (fmaxf drops a NaN)
+      }
+      const float ms = mn > -INFINITY ? mn : 0.0f;
+      float e = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) e += __builtin_amdgcn_exp2f(acc[u][r] - ms);
+      s[g] = s[g] * __builtin_amdgcn_exp2f(m[g] - ms) + e;
+      m[g] = mn;
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+  }
+
+  // the four lanes of a query, then its partial
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {
+      const float om = __shfl_xor(m[g], off, 64), os = __shfl_xor(s[g], off, 64);
+      pw_fold(m[g], s[g], om, os);
+    }
+    const int qi = q0 + 16 * g + col;
+    if (quad == 0 && qi < a.n_q) a.part[(int64_t)blockIdx.y * a.n_q + qi] = make_float2(m[g], s[g]);
+  }
+}
+
+// one thread per query: the splits in index order, the query's own term and its own verdict, the answer in natural units
+__global__ __launch_bounds__(kPwThreads) void k_pw_merge_diag(const PwDiagArgs da) {
+  const PwArgs& a = da.pw;
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  if (r >= a.n_q) return;
+  const bool keys = da.side == GJX_PAIRWISE_PREC_KEYS;
+  float q2 = 0.0f;                                        // sum_j p q~^2; side KEYS: p = 1, and only its finiteness is used
+  for (int i = 0; i < a.d; ++i) {
+    const float x = a.q[(int64_t)i * a.stride_q + r] - (a.centre ? a.centre[i] : 0.0f);
+    const float p = keys ? 1.0f : da.prec[(int64_t)i * da.stride_p + r];
+    q2 = pw_prec_ok(p) ? fmaf(p * x, x, q2) : NAN;
+  }
+  float m = -INFINITY, s = 0.0f;
+  for (int y = 0; y < a.n_splits; ++y) {
+    const float2 p = a.part[(int64_t)y * a.n_q + r];
+    pw_fold(m, s, p.x, p.y);
+  }
+  // no live key: m = -inf, s = 0 -> -inf; a poisoned key: s = NaN -> NaN
+  a.out[r] = q2 < INFINITY ? (m + __builtin_amdgcn_logf(s)) * kPwLn2 - (keys ? 0.0f : 0.5f * q2) : NAN;
+}
+
+template <int DC>
+static void pw_diag_launch(const PwDiagArgs& da, dim3 grid, hipStream_t st) {
+  if (da.side == GJX_PAIRWISE_PREC_KEYS)
+    hipLaunchKernelGGL((k_pw_lse_diag<DC, GJX_PAIRWISE_PREC_KEYS>), grid, dim3(kPwThreads), 0, st, da);
+  else
+    hipLaunchKernelGGL((k_pw_lse_diag<DC, GJX_PAIRWISE_PREC_QUERIES>), grid, dim3(kPwThreads), 0, st, da);
+}
+
 }  // namespace gjx
 
 extern "C" size_t gjx_pairwise_gauss_lse_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
@@ -837,5 +1038,48 @@ extern "C" int gjx_pairwise_gauss_pick(const float* q, int64_t stride_q, int64_t
   GJX_CHECK_LAUNCH("gjx_pairwise_gauss_pick(pick)");
   hipLaunchKernelGGL(k_pw_pick_finish, per_query, dim3(kPwThreads), 0, st, pa);
   GJX_CHECK_LAUNCH("gjx_pairwise_gauss_pick(finish)");
+  return GJX_OK;
+}
+
+extern "C" size_t gjx_pairwise_gauss_lse_diag_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
+  if (d > GJX_PAIRWISE_DIAG_MAX_DIM) return 0;
+  return gjx_pairwise_gauss_lse_workspace_bytes(n_q, n_k, d);
+}
+
+extern "C" int gjx_pairwise_gauss_lse_diag(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k,
+                                           int32_t d, const float* bias, const float* prec, int64_t stride_p, int32_t prec_side,
+                                           const float* centre, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace gjx;
+  const bool keys = prec_side == GJX_PAIRWISE_PREC_KEYS;
+  if (!q || !k || !prec || !out || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      stride_q < n_q || stride_k < n_k || (!keys && prec_side != GJX_PAIRWISE_PREC_QUERIES) || stride_p < (keys ? n_k : n_q))
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_gauss_lse_diag: bad argument");
+  if (d > GJX_PAIRWISE_DIAG_MAX_DIM)
+    return gjx_fail(GJX_EUNSUPPORTED, "gjx_pairwise_gauss_lse_diag: more than GJX_PAIRWISE_DIAG_MAX_DIM components");
+  PwDiagArgs da;
+  memset(&da, 0, sizeof(da));
+  PwArgs& a = da.pw;
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_gauss_lse_diag_workspace_bytes(n_q, n_k, d))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_gauss_lse_diag: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = out;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k;
+  da.prec = prec; da.stride_p = stride_p; da.side = prec_side;
+  const dim3 grid((unsigned)((n_q + kPwBlockQ - 1) / kPwBlockQ), (unsigned)a.n_splits);
+  switch ((2 * d + 3) / 4) {                              // chunks of 4 features
+    case 1: pw_diag_launch<1>(da, grid, st); break;
+    case 2: pw_diag_launch<2>(da, grid, st); break;
+    case 3: pw_diag_launch<3>(da, grid, st); break;
+    case 4: pw_diag_launch<4>(da, grid, st); break;
+    case 5: pw_diag_launch<5>(da, grid, st); break;
+    case 6: pw_diag_launch<6>(da, grid, st); break;
+    case 7: pw_diag_launch<7>(da, grid, st); break;
+    default: pw_diag_launch<8>(da, grid, st); break;
+  }
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_lse_diag(lse)");
+  hipLaunchKernelGGL(k_pw_merge_diag, dim3((unsigned)((n_q + kPwThreads - 1) / kPwThreads)), dim3(kPwThreads), 0, st, da);
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_lse_diag(merge)");
   return GJX_OK;
 }

@@ -734,14 +734,50 @@ def _pairwise_args(name: str, q_rows, k_rows, bias, precision, centre):
     return q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre
 
 
-def pairwise_gauss_lse(q_rows: torch.Tensor, k_rows: torch.Tensor, bias=None, precision: float = 1.0, centre=None, ws=None,
-                       out=None) -> torch.Tensor:
+_PAIRWISE_PREC_SIDES = {"keys": A.PAIRWISE_PREC_KEYS, "queries": A.PAIRWISE_PREC_QUERIES}
+
+
+def _pairwise_lse_diag(q_rows, k_rows, bias, precision: torch.Tensor, side: int, centre, ws, out) -> torch.Tensor:
+    """pairwise_gauss_lse with a precision matrix: gjx_pairwise_gauss_lse_diag"""
+    name = "pairwise_gauss_lse"
+    q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, _, centre = _pairwise_args(name, q_rows, k_rows, bias, 1.0, centre)
+    if d > A.PAIRWISE_DIAG_MAX_DIM:
+        raise ValueError(f"{name}: at most {A.PAIRWISE_DIAG_MAX_DIM} components with a precision matrix, not {d}")
+    prec, stride_p, d_p, n_p = _pairwise_rows("precision", precision)
+    n_side = n_k if side == A.PAIRWISE_PREC_KEYS else n_q
+    if (d_p, n_p) != (d, n_side):
+        raise ValueError(f"{name}: a precision matrix of the {'keys' if side == A.PAIRWISE_PREC_KEYS else 'queries'} must be "
+                         f"f32[{d}][{n_side}], not [{d_p}][{n_p}]")
+    dev = q_rows.device
+    if out is None:
+        out = torch.empty(n_q, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.numel() != n_q or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous f32[n_q]")
+    if ws is None:
+        ws = torch.empty(load().gjx_pairwise_gauss_lse_diag_workspace_bytes(n_q, n_k, d), dtype=torch.uint8, device=dev)   # partials only
+    check(load().gjx_pairwise_gauss_lse_diag(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(bias), _ptr(prec), stride_p,
+                                             side, _ptr(centre), _ptr(out), _ptr(ws), ws.numel(), _stream()), "gjx_pairwise_gauss_lse_diag")
+    return out
+
+
+def pairwise_gauss_lse(q_rows: torch.Tensor, k_rows: torch.Tensor, bias=None, precision=1.0, centre=None, ws=None,
+                       out=None, precision_of: str = "keys") -> torch.Tensor:
     """gjx_pairwise_gauss_lse: queries f32[d][n_q] and keys f32[d][n_k] (SoA; views are fine as long as the column stride is 1, no
     alignment is asked), ``bias`` f32[n_k] (None: zeros) -> f32[n_q], out[r] = log sum_c exp(bias[c] - 1/2 precision |q_r - k_c|^2).
     A key with bias -inf or NaN is dead whatever its coordinates; no live key gives -inf; a query with a non-finite coordinate gives NaN
     for that query alone.  ``centre`` f32[d] (None: zeros) is subtracted from both sets on the way in: it changes nothing mathematically
     and decides the accuracy (the error grows with the centred squared norms): pass the keys' mean.  d <= 32.  O(n_q n_k d) on the matrix
-    cores, nothing of size n_q x n_k is stored; two launches, bit-reproducible."""
+    cores, nothing of size n_q x n_k is stored; two launches, bit-reproducible.
+    ``precision`` may be a tensor instead of a number (gjx_pairwise_gauss_lse_diag): one diagonal precision per key, f32[d][n_k]
+    (``precision_of="keys"``), or per query, f32[d][n_q] (``"queries"``), a view under the rules of the particle sets:
+    out[r] = log sum_c exp(bias[c] - 1/2 sum_j P_j (q[j][r] - k[j][c])^2) with P_j = precision[j][c] or precision[j][r].  The normaliser
+    1/2 sum_j log P_j is not part of the score: fold it into ``bias`` (keys) or add it to the result (queries).  Every entry must be
+    > 0 and finite: a live key's bad entry makes every output NaN, a query's bad entry that query's; a dead key's are not looked at.
+    d <= 16 then; same launches, same workspace."""
+    if precision_of not in _PAIRWISE_PREC_SIDES:
+        raise ValueError(f"pairwise_gauss_lse: precision_of must be 'keys' or 'queries', not {precision_of!r}")
+    if isinstance(precision, torch.Tensor) and precision.dim() > 0:
+        return _pairwise_lse_diag(q_rows, k_rows, bias, precision, _PAIRWISE_PREC_SIDES[precision_of], centre, ws, out)
     q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre = _pairwise_args("pairwise_gauss_lse", q_rows, k_rows, bias, precision,
                                                                                       centre)
     dev = q_rows.device
@@ -900,13 +936,36 @@ def ffbs_weights(states, logw_steps, means, precision: float) -> torch.Tensor:
     in the log domain two ``pairwise_gauss_lse`` calls per step with the two particle sets in swapped roles; the centre of step t's
     calls is the weighted mean of states[t+1] (``weighted_moments``).  Cost: O(T K^2 d) — 2 (T - 1) K^2 pairs, each d multiply-adds on
     the matrix cores and one exponential — against O(T K) for the genealogy; outputs and workspace are allocated once, nothing is
-    read back."""
+    read back.
+    Heteroscedastic and anisotropic transitions, x_{t+1} ~ N(m(x_t), diag(1 / P_t(x_t))): ``precision`` is a list or tuple of T entries,
+    precision[t] f32[d][K] the diagonal precision of the transition OUT OF step t's particles (column i: particle i's), or f32[d] where
+    it is the same for all of them (precision[T-1] is not read).  The recursion is the same with the per-particle precisions inside the
+    two calls (``pairwise_gauss_lse`` with a precision matrix: the parents are the keys of the first call and the queries of the
+    second) and the Gaussian's normaliser ln_t^i = 1/2 sum_j log P_t[j][i], which no longer cancels, added to the bias of the first call
+    and to the result of the second.  d <= 16."""
     T = len(states)
     if T == 0 or len(logw_steps) != T or len(means) != T:
         raise ValueError("ffbs_weights: states, logw_steps and means must have one entry per step")
     d, K = int(states[0].shape[0]), int(states[0].shape[1])
     dev = states[0].device
     ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
+    diag = isinstance(precision, (list, tuple))
+    if diag:
+        if len(precision) != T:
+            raise ValueError("ffbs_weights: a sequence of precisions must have one entry per step")
+        for P in precision[:T - 1]:
+            if not isinstance(P, torch.Tensor) or P.dtype != torch.float32 or tuple(P.shape) not in ((d,), (d, K)):
+                raise ValueError(f"ffbs_weights: a step's precision must be f32[{d}][{K}] or f32[{d}]")
+        if d > A.PAIRWISE_DIAG_MAX_DIM and T > 1:
+            raise ValueError(f"ffbs_weights: at most {A.PAIRWISE_DIAG_MAX_DIM} components with per-step precisions, not {d}")
+        tables = {}                                                       # a constant f32[d] becomes its f32[d][K] table once
+
+        def table(P):
+            if P.dim() == 2:
+                return P
+            if id(P) not in tables:
+                tables[id(P)] = P.reshape(d, 1).expand(d, K).contiguous()
+            return tables[id(P)]
 
     def log_normalised(lw):
         lw = torch.where(torch.isnan(lw), ninf, lw)                       # (a NaN weight is dead, as everywhere in the library)
@@ -921,6 +980,13 @@ def ffbs_weights(states, logw_steps, means, precision: float) -> torch.Tensor:
     for t in range(T - 2, -1, -1):
         lw_t = log_normalised(lw_filter[t])
         centre = weighted_moments(states[t + 1], logw_steps[t + 1], "mean")["mean"]
+        if diag:
+            P = table(precision[t])
+            ln_t = 0.5 * torch.log(P).sum(0)
+            pairwise_gauss_lse(states[t + 1], means[t], lw_t + ln_t, P, centre, ws, out=D, precision_of="keys")
+            pairwise_gauss_lse(means[t], states[t + 1], out[t + 1] - D, P, centre, ws, out=back, precision_of="queries")
+            out[t] = log_normalised(lw_t + back + ln_t)
+            continue
         pairwise_gauss_lse(states[t + 1], means[t], lw_t, precision, centre, ws, out=D)
         pairwise_gauss_lse(means[t], states[t + 1], out[t + 1] - D, precision, centre, ws, out=back)
         out[t] = log_normalised(lw_t + back)

@@ -1224,6 +1224,44 @@ int gjx_pairwise_gauss_pick(const float* q /* f32[d][stride_q] */, int64_t strid
                             int64_t stride_k, int64_t n_k, int32_t d, const float* bias /* f32[n_k] or NULL */, float precision,
                             const float* centre /* f32[d] or NULL */, const float* u /* f32[n_q] */, int32_t* pick /* i32[n_q] */,
                             float* lse /* f32[n_q] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+/* Pairwise Gaussian log-sum-exp with one DIAGONAL precision per particle of one of the two sets:
+ *     out[r]   = log sum_{c < n_k} exp(bias[c] - 1/2 sum_{j < d} P_j(r, c) (q[j][r] - k[j][c])^2),   r < n_q
+ *     P_j(r, c) = prec[j][c]  (prec_side GJX_PAIRWISE_PREC_KEYS)   or   prec[j][r]  (GJX_PAIRWISE_PREC_QUERIES)
+ * It serves transitions x_{t+1} ~ N(m(x_t), diag(1 / p(x_t))) whose noise depends on the parent particle (Euler-Maruyama steps with
+ * state-dependent diffusion) or on the component (anisotropic noise), which the scalar precision of gjx_pairwise_gauss_lse cannot: the
+ * precision belongs to one particle of the pair, so no scaling of the two sets removes it.  FFBSm needs both sides: in D_j = LSE_i(..)
+ * the parents are the keys, in the backward call they are the queries.  The Gaussian normaliser 1/2 sum_j log prec is NOT part of the
+ * score: the caller folds it into bias (keys side) or adds it to out (queries side).  With queries as data and keys as components the
+ * keys side is also the log-density of a diagonal-covariance Gaussian mixture, or a kernel density estimate of adaptive bandwidth.
+ *   q, k, bias, centre, out   as in gjx_pairwise_gauss_lse
+ *   prec       f32[d][stride_p], stride_p >= n_k (keys side) or >= n_q (queries side): one column per particle of that set, every
+ *              entry > 0 and finite
+ *   d          1 .. GJX_PAIRWISE_DIAG_MAX_DIM
+ * Semantics.  A key whose bias is -inf or NaN is DEAD whatever its coordinates and its precisions hold (NaN included).  No live key:
+ * -inf.  A LIVE key poisons the call (every output NaN) when one of its own precisions (keys side) is not > 0 and < inf, when a
+ * centred coordinate, its square, or its product with the precision is not finite, or when its bias is +inf; it is staged as zeros and
+ * never reaches a matrix instruction.  A query with a non-finite centred coordinate or square, or (queries side) a precision entry
+ * that is not > 0 and < inf, gives NaN for that query alone.
+ * Device work.  Two plain launches on `stream`, grid, key splits, staging through LDS and the streaming log-sum-exp exactly as in
+ * gjx_pairwise_gauss_lse; the score is a bilinear form over 2 d features (per component one linear and one quadratic, interleaved,
+ * padded to a multiple of 4) on v_mfma_f32_16x16x4_f32 with f32 inputs:
+ *     keys side:     key features  p k~, -1/2 p;   query features  q~, q~^2;      C operand  bias - 1/2 sum_j p k~^2
+ *     queries side:  key features  k~,  k~^2;      query features  p q~, -1/2 p;  C operand  bias;  the second launch adds -1/2 sum_j p q~^2
+ * (tildes: minus centre).  The error of out[r] is of the order 2^-24 (2 d + 4) max_c sum_j P_j (q~_rj^2 + k~_cj^2): pass the keys'
+ * (weighted) mean as centre.  No atomics, every sum in an order fixed by the shape: bit-reproducible.
+ * GJX_EINVAL: a NULL q, k, prec, out or workspace; n_q, n_k, d out of gjx_pairwise_gauss_lse's ranges; a stride below its count; a
+ * prec_side that is neither constant.  GJX_EUNSUPPORTED: d > GJX_PAIRWISE_DIAG_MAX_DIM.  GJX_EWORKSPACE: less than
+ * gjx_pairwise_gauss_lse_diag_workspace_bytes(n_q, n_k, d), which is gjx_pairwise_gauss_lse's (0 for shapes the call refuses).  The
+ * workspace needs no initialisation.  Nothing is launched on a refusal. */
+#define GJX_PAIRWISE_DIAG_MAX_DIM 16
+#define GJX_PAIRWISE_PREC_KEYS 0
+#define GJX_PAIRWISE_PREC_QUERIES 1
+size_t gjx_pairwise_gauss_lse_diag_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d);
+int gjx_pairwise_gauss_lse_diag(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q,
+                                const float* k /* f32[d][stride_k] */, int64_t stride_k, int64_t n_k, int32_t d,
+                                const float* bias /* f32[n_k] or NULL */, const float* prec /* f32[d][stride_p] */, int64_t stride_p,
+                                int32_t prec_side, const float* centre /* f32[d] or NULL */, float* out /* f32[n_q] */,
+                                void* workspace, size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
