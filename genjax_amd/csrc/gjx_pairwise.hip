@@ -37,7 +37,11 @@
 //
 // gjx_pairwise_gauss_lse_diag (k_pw_lse_diag, k_pw_merge_diag; last part of this file) is the log-sum-exp with one diagonal precision
 // per key or per query: the score becomes a bilinear form over 2 d features.  Its scheme and edge rules are described there.
+//
+// gjx_pairwise_gauss_mean_diag and gjx_pairwise_gauss_pick_diag (k_pw_mean_diag, k_pw_pick_diag, k_pw_pick_finish_diag; after it) are
+// the mean and the pick over those scores with the precisions on the keys.
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include "gjx_device.h"
@@ -892,6 +896,350 @@ static void pw_diag_launch(const PwDiagArgs& da, dim3 grid, hipStream_t st) {
     hipLaunchKernelGGL((k_pw_lse_diag<DC, GJX_PAIRWISE_PREC_QUERIES>), grid, dim3(kPwThreads), 0, st, da);
 }
 
+// ---- gjx_pairwise_gauss_mean_diag, gjx_pairwise_gauss_pick_diag: the mean and the pick over the scores of k_pw_lse_diag<DC, KEYS> ----
+//
+// Side KEYS only (the parents of both smoothers are the keys).  k_pw_mean_diag<DC, VB> and k_pw_pick_diag<DC> are k_pw_mean and k_pw_pick
+// with the 2 d features in place of the d coordinates: PwDiagKeys<DC> below is the prologue, the loads and the staging of
+// k_pw_lse_diag<DC, KEYS>, operation for operation (same feature order, same kb, same zeroing of dead, tail and poisoned keys, so the
+// scores of the three kernels are the same bits), and everything after the scores is the isotropic kernel's.  DC = ceil(2 d / 4) <= 8.
+//
+// The per-query launches need no diag sibling.  Under KEYS a query adds nothing to its scores after the loop and its verdict is the
+// finiteness of sum_j q~_j^2 (that is: of every q~ and q~^2), which is what k_pw_mean_merge and k_pw_pick_plan compute with pw.p = 0:
+// their own term 1/2 p |q~|^2 is then exactly 0 for a finite sum, and the lse comes out as L ln 2.  Both run unchanged with p = 0.
+// Only k_pw_pick_finish has a sibling, k_pw_pick_finish_diag: it makes scores itself, with the key's own precisions.
+template <int DC>
+struct PwDiagKeys {
+  float scen[DC];          // the centre at the staging thread's components
+  float v[DC], pv[DC], b;  // the staging thread's key of the tile in flight: centred coordinates (then features), precisions, bias
+
+  // the wave's query features (q~, q~^2) log2 e, for the whole kernel
+  GJX_DEV void queries(const PwArgs& a, int q0, int col, int quad, int spart, float (&qf)[kPwGroups][DC]) {
+    const bool qquad = quad & 1;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int jq = 2 * c + (quad >> 1), js = 2 * c + (spart >> 1);
+      const float cen = (a.centre && jq < a.d) ? a.centre[jq] : 0.0f;
+      scen[c] = (a.centre && js < a.d) ? a.centre[js] : 0.0f;
+#pragma unroll
+      for (int g = 0; g < kPwGroups; ++g) {
+        const int qi = q0 + 16 * g + col;
+        float f = 0.0f;
+        if (jq < a.d && qi < a.n_q) {
+          const float x = a.q[(int64_t)jq * a.stride_q + qi] - cen;
+          f = qquad ? x * x : x;
+        }
+        qf[g][c] = f * kPwLog2e;
+      }
+    }
+  }
+
+  GJX_DEV void load(const PwArgs& a, const float* prec, int64_t stride_p, int tile, int skey, int spart) {
+    const int key = tile * kPwTile + skey;
+    const bool in = key < a.n_k;
+    b = in ? (a.bias ? a.bias[key] : 0.0f) : -INFINITY;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int js = 2 * c + (spart >> 1);
+      const bool have = in && js < a.d;
+      v[c] = have ? a.k[(int64_t)js * a.stride_k + key] - scen[c] : 0.0f;
+      pv[c] = have ? prec[(int64_t)js * stride_p + key] : 0.0f;
+    }
+  }
+
+  // the key features (p k~, -1/2 p) and kb into one LDS buffer; -> the key is dead (bias -inf or NaN, or past n_k)
+  GJX_DEV bool store(const PwArgs& a, float* sk, float* sb, int skey, int spart) {
+    const bool squad = spart & 1;
+    float k2 = 0.0f;                                      // sum_j p k~^2; NaN for a precision that is not one
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const bool pad = 2 * c + (spart >> 1) >= a.d;
+      const float p = pv[c], lin = p * v[c];
+      k2 = (pad || pw_prec_ok(p)) ? (squad ? k2 : fmaf(lin, v[c], k2)) : NAN;
+      v[c] = squad ? -0.5f * p : lin;
+    }
+    k2 = quad_sum(k2);
+    const bool dead = !(b > -INFINITY);                   // -inf or NaN
+    const bool zero = dead || !(k2 < INFINITY) || !(b < INFINITY);
+#pragma unroll
+    for (int c = 0; c < DC; ++c) sk[(4 * c + spart) * kPwLd + skey] = zero ? 0.0f : v[c];
+    if (spart == 0) sb[skey] = dead ? -INFINITY : (zero ? NAN : (b - 0.5f * k2) * kPwLog2e);
+    return dead;
+  }
+};
+
+struct PwMeanDiagArgs {
+  PwMeanArgs ma;           // ma.pw.p = 0: see above
+  const float* prec;       // f32[d][stride_p], a column per key
+  int64_t stride_p;
+};
+
+// k_pw_mean's loop over k_pw_lse_diag's scores: the shared maximum by pw_rows_max, exp2(acc - max) as the B operand of the value
+// product, values staged [j][key] with row stride 68, O^T in 4 VB accumulators per group, one rescale and one barrier per tile.
+template <int DC, int VB>
+__global__ __launch_bounds__(kPwThreads) void k_pw_mean_diag(const PwMeanDiagArgs mda) {
+  const PwMeanArgs& ma = mda.ma;
+  const PwArgs& a = ma.pw;
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sb[2][kPwTile];
+  __shared__ __attribute__((aligned(16))) float sv[2][16 * VB * kPwLdV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;            // the MFMA's view of the lane: query col, features 4 c + quad
+  const int skey = tid >> 2, spart = tid & 3;             // the staging's view: key of the tile, features 4 c + spart
+
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  float qf[kPwGroups][DC];
+  PwDiagKeys<DC> keys;
+  keys.queries(a, q0, col, quad, spart, qf);
+
+  float vv[4 * VB];
+  auto load = [&](int tile) {
+    keys.load(a, mda.prec, mda.stride_p, tile, skey, spart);
+    const int key = tile * kPwTile + skey;
+#pragma unroll
+    for (int c = 0; c < 4 * VB; ++c) {
+      const int j = 4 * c + spart;
+      vv[c] = (key < a.n_k && j < ma.dv) ? ma.v[(int64_t)j * ma.stride_v + key] : 0.0f;
+    }
+  };
+  auto store = [&](int buf) {
+    const bool dead = keys.store(a, sk[buf], sb[buf], skey, spart);
+#pragma unroll
+    for (int c = 0; c < 4 * VB; ++c)
+      sv[buf][(4 * c + spart) * kPwLdV + skey] = dead ? 0.0f : (fabsf(vv[c]) < INFINITY ? vv[c] : NAN);
+  };
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  float m[kPwGroups], s[kPwGroups];
+  pw_v4f o[kPwGroups][VB];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    m[g] = -INFINITY;
+    s[g] = 0.0f;
+#pragma unroll
+    for (int vb = 0; vb < VB; ++vb) o[g][vb] = pw_v4f{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+
+  load(t0);
+  store(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) load(t + 1);
+    float af[4][DC];
+    pw_v4f seed[4], vf[4][VB];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {                         // the tile's four 16-key subtiles
+      seed[u] = *reinterpret_cast<const pw_v4f*>(&sb[buf][16 * u + 4 * quad]);
+#pragma unroll
+      for (int c = 0; c < DC; ++c) af[u][c] = sk[buf][(4 * c + quad) * kPwLd + 16 * u + col];
+#pragma unroll
+      for (int vb = 0; vb < VB; ++vb)
+        vf[u][vb] = *reinterpret_cast<const pw_v4f*>(&sv[buf][(16 * vb + col) * kPwLdV + 16 * u + 4 * quad]);
+    }
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      pw_v4f acc[4];
+      float mn = m[g];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc[u] = seed[u];
+#pragma unroll
+        for (int c = 0; c < DC; ++c) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][c], qf[g][c], acc[u], 0, 0, 0);
+        mn = fmaxf(fmaxf(mn, fmaxf(acc[u][0], acc[u][1])), fmaxf(acc[u][2], acc[u][3]));        // (fmaxf drops a NaN)
+      }
+      mn = pw_rows_max(mn);                               // the query's four lanes agree before the exponentials
+      const float ms = mn > -INFINITY ? mn : 0.0f;
+      const float f = __builtin_amdgcn_exp2f(m[g] - ms);
+      float e = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          acc[u][r] = __builtin_amdgcn_exp2f(acc[u][r] - ms);
+          e += acc[u][r];
+        }
+      s[g] = s[g] * f + e;
+      m[g] = mn;
+#pragma unroll
+      for (int vb = 0; vb < VB; ++vb) {
+        o[g][vb] *= f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) o[g][vb] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[u][vb][r], acc[u][r], o[g][vb], 0, 0, 0);
+      }
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+  }
+
+  // the four lanes of a query share m; their sums are added in one fixed order.  Then the partials, laid out as k_pw_mean's.
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    s[g] += __shfl_xor(s[g], 16, 64);
+    s[g] += __shfl_xor(s[g], 32, 64);
+    const int qi = q0 + 16 * g + col;
+    if (qi >= a.n_q) continue;
+    if (quad == 0) a.part[(int64_t)blockIdx.y * a.n_q + qi] = make_float2(m[g], s[g]);
+#pragma unroll
+    for (int vb = 0; vb < VB; ++vb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = 16 * vb + 4 * quad + r;
+        if (j < ma.dv) ma.opart[((int64_t)blockIdx.y * ma.dv + j) * a.n_q + qi] = o[g][vb][r];
+      }
+  }
+}
+
+template <int DC>
+static void pw_mean_diag_launch(const PwMeanDiagArgs& mda, dim3 grid, hipStream_t st) {
+  if (mda.ma.dv <= 16) hipLaunchKernelGGL((k_pw_mean_diag<DC, 1>), grid, dim3(kPwThreads), 0, st, mda);
+  else hipLaunchKernelGGL((k_pw_mean_diag<DC, 2>), grid, dim3(kPwThreads), 0, st, mda);
+}
+
+struct PwPickDiagArgs {
+  PwPickArgs pa;           // pa.pw.p = 0: see above
+  const float* prec;       // f32[d][stride_p], a column per key
+  int64_t stride_p;
+};
+
+// k_pw_pick's loop over k_pw_lse_diag's scores: exp2(acc - L) with L from the plan, 64-key chunk masses by pw_rows_sum, the crossing
+// chunk recorded with the cumulative before it, groups this split does not own skipped wave-uniformly.
+template <int DC>
+__global__ __launch_bounds__(kPwThreads) void k_pw_pick_diag(const PwPickDiagArgs pda) {
+  const PwPickArgs& pa = pda.pa;
+  const PwArgs& a = pa.pw;
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sb[2][kPwTile];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;
+  const int skey = tid >> 2, spart = tid & 3;
+
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  float qf[kPwGroups][DC];
+  PwDiagKeys<DC> keys;
+  keys.queries(a, q0, col, quad, spart, qf);
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  // per group: the query's L and residual target where this split owns it, the running cumulative, the record
+  float L[kPwGroups], want[kPwGroups], cum[kPwGroups], rb[kPwGroups];
+  int rt[kPwGroups];
+  bool mine[kPwGroups], act[kPwGroups], done[kPwGroups];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    const int qi = q0 + 16 * g + col;
+    mine[g] = qi < a.n_q && pa.own[qi] == (int)blockIdx.y;
+    act[g] = __any(mine[g]) != 0;                         // wave-uniform: somebody in the group is owned here
+    L[g] = mine[g] ? pa.L[qi] : INFINITY;                 // (+inf: every exponential of a query owned elsewhere is 0)
+    want[g] = mine[g] ? pa.resid[qi] : INFINITY;
+    cum[g] = rb[g] = 0.0f;
+    rt[g] = t0;
+    done[g] = false;
+  }
+
+  keys.load(a, pda.prec, pda.stride_p, t0, skey, spart);
+  keys.store(a, sk[0], sb[0], skey, spart);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) keys.load(a, pda.prec, pda.stride_p, t + 1, skey, spart);
+    float af[4][DC];
+    pw_v4f seed[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      seed[u] = *reinterpret_cast<const pw_v4f*>(&sb[buf][16 * u + 4 * quad]);
+#pragma unroll
+      for (int c = 0; c < DC; ++c) af[u][c] = sk[buf][(4 * c + quad) * kPwLd + 16 * u + col];
+    }
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      if (!act[g]) continue;
+      pw_v4f acc[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc[u] = seed[u];
+#pragma unroll
+        for (int c = 0; c < DC; ++c) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][c], qf[g][c], acc[u], 0, 0, 0);
+      }
+      float e = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) e += __builtin_amdgcn_exp2f(acc[u][r] - L[g]);
+      e = pw_rows_sum(e);                                 // the chunk's mass, the same bits in the query's four lanes
+      if (!done[g] && e > 0.0f) {
+        rt[g] = t;
+        rb[g] = cum[g];
+        done[g] = cum[g] + e >= want[g];
+      }
+      cum[g] += e;
+    }
+    if (more) keys.store(a, sk[buf ^ 1], sb[buf ^ 1], skey, spart);
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    const int qi = q0 + 16 * g + col;
+    if (quad == 0 && mine[g]) {
+      pa.rchunk[qi] = rt[g];
+      pa.rbefore[qi] = rb[g];
+    }
+  }
+}
+
+// one thread per query: the recorded chunk key by key, every key scored with its own precisions:
+// score = kb + sum_j (p k~)(q~ log2 e) + sum_j (-1/2 p)(q~^2 log2 e).  An owned query has no poisoned live key (k_pw_pick_plan).
+__global__ __launch_bounds__(kPwThreads) void k_pw_pick_finish_diag(const PwPickDiagArgs pda) {
+  const PwPickArgs& pa = pda.pa;
+  const PwArgs& a = pa.pw;
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  if (r >= a.n_q || pa.own[r] < 0) return;                // (no pick: k_pw_pick_plan wrote the -1)
+  float ql[GJX_PAIRWISE_DIAG_MAX_DIM], qq[GJX_PAIRWISE_DIAG_MAX_DIM];
+#pragma unroll
+  for (int i = 0; i < GJX_PAIRWISE_DIAG_MAX_DIM; ++i) {
+    const float x = i < a.d ? a.q[(int64_t)i * a.stride_q + r] - (a.centre ? a.centre[i] : 0.0f) : 0.0f;
+    ql[i] = x * kPwLog2e;
+    qq[i] = x * x * kPwLog2e;
+  }
+  const float L = pa.L[r], want = pa.resid[r] - pa.rbefore[r];
+  const int t = min(max(pa.rchunk[r], 0), a.n_tiles - 1);
+  const int c0 = t * kPwTile, c1 = min(c0 + kPwTile, a.n_k);
+  float cum = 0.0f, top = -INFINITY;
+  int pick = -1, last = -1, topc = -1;
+  for (int c = c0; c < c1 && pick < 0; ++c) {
+    const float b = a.bias ? a.bias[c] : 0.0f;
+    if (!(b > -INFINITY)) continue;                       // dead
+    float k2 = 0.0f, dot = 0.0f;
+#pragma unroll
+    for (int i = 0; i < GJX_PAIRWISE_DIAG_MAX_DIM; ++i) {
+      if (i >= a.d) break;
+      const float x = a.k[(int64_t)i * a.stride_k + c] - (a.centre ? a.centre[i] : 0.0f);
+      const float p = pda.prec[(int64_t)i * pda.stride_p + c], lin = p * x;
+      k2 = fmaf(lin, x, k2);
+      dot = fmaf(-0.5f * p, qq[i], fmaf(lin, ql[i], dot));
+    }
+    const float sc = (b - 0.5f * k2) * kPwLog2e + dot;
+    if (sc > top) { top = sc; topc = c; }
+    const float e = __builtin_amdgcn_exp2f(sc - L);
+    if (e > 0.0f) {
+      last = c;
+      cum += e;
+      if (cum >= want) pick = c;
+    }
+  }
+  pa.pick[r] = pick >= 0 ? pick : (last >= 0 ? last : topc);
+}
+
+template <int DC>
+static void pw_pick_diag_launch(const PwPickDiagArgs& pda, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL(k_pw_pick_diag<DC>, grid, dim3(kPwThreads), 0, st, pda);
+}
+
 }  // namespace gjx
 
 extern "C" size_t gjx_pairwise_gauss_lse_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
@@ -1081,5 +1429,129 @@ extern "C" int gjx_pairwise_gauss_lse_diag(const float* q, int64_t stride_q, int
   GJX_CHECK_LAUNCH("gjx_pairwise_gauss_lse_diag(lse)");
   hipLaunchKernelGGL(k_pw_merge_diag, dim3((unsigned)((n_q + kPwThreads - 1) / kPwThreads)), dim3(kPwThreads), 0, st, da);
   GJX_CHECK_LAUNCH("gjx_pairwise_gauss_lse_diag(merge)");
+  return GJX_OK;
+}
+
+// what the two KEYS-only diag calls refuse beyond their isotropic siblings' own checks; GJX_OK: go on
+static int pw_diag_keys_only(const char* who, const float* prec, int64_t stride_p, int64_t n_k, int32_t prec_side, int32_t d) {
+  const bool queries = prec_side == GJX_PAIRWISE_PREC_QUERIES;
+  const bool bad = !queries && (!prec || prec_side != GJX_PAIRWISE_PREC_KEYS || stride_p < n_k);
+  if (!queries && !bad && d <= GJX_PAIRWISE_DIAG_MAX_DIM) return GJX_OK;
+  char msg[160];
+  snprintf(msg, sizeof(msg), "%s: %s", who, queries ? "GJX_PAIRWISE_PREC_QUERIES is not served, only GJX_PAIRWISE_PREC_KEYS"
+                                            : bad   ? "bad argument" : "more than GJX_PAIRWISE_DIAG_MAX_DIM components");
+  return gjx_fail(bad ? GJX_EINVAL : GJX_EUNSUPPORTED, msg);
+}
+
+extern "C" size_t gjx_pairwise_gauss_mean_diag_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d, int32_t dv) {
+  if (d > GJX_PAIRWISE_DIAG_MAX_DIM) return 0;
+  return gjx_pairwise_gauss_mean_workspace_bytes(n_q, n_k, d, dv);
+}
+
+extern "C" int gjx_pairwise_gauss_mean_diag(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k,
+                                            int32_t d, const float* v, int64_t stride_v, int32_t dv, const float* bias, const float* prec,
+                                            int64_t stride_p, int32_t prec_side, const float* centre, float* mean, float* lse,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace gjx;
+  if (!q || !k || !v || !mean || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      dv <= 0 || stride_q < n_q || stride_k < n_k || stride_v < n_k)
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_gauss_mean_diag: bad argument");
+  if (const int rc = pw_diag_keys_only("gjx_pairwise_gauss_mean_diag", prec, stride_p, n_k, prec_side, d)) return rc;
+  if (dv > GJX_PAIRWISE_MAX_DIM)
+    return gjx_fail(GJX_EUNSUPPORTED, "gjx_pairwise_gauss_mean_diag: more than GJX_PAIRWISE_MAX_DIM value components");
+  PwMeanDiagArgs mda;
+  memset(&mda, 0, sizeof(mda));
+  PwMeanArgs& ma = mda.ma;
+  PwArgs& a = ma.pw;
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_gauss_mean_diag_workspace_bytes(n_q, n_k, d, dv))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_gauss_mean_diag: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = lse;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k; a.p = 0.0f;             // (0: k_pw_mean_merge then adds no query term)
+  ma.v = v; ma.mean = mean; ma.stride_v = stride_v; ma.dv = dv;
+  ma.opart = (float*)(a.part + (size_t)a.n_splits * (size_t)n_q);
+  mda.prec = prec; mda.stride_p = stride_p;
+  const dim3 grid((unsigned)((n_q + kPwBlockQ - 1) / kPwBlockQ), (unsigned)a.n_splits);
+  switch ((2 * d + 3) / 4) {                              // chunks of 4 features
+    case 1: pw_mean_diag_launch<1>(mda, grid, st); break;
+    case 2: pw_mean_diag_launch<2>(mda, grid, st); break;
+    case 3: pw_mean_diag_launch<3>(mda, grid, st); break;
+    case 4: pw_mean_diag_launch<4>(mda, grid, st); break;
+    case 5: pw_mean_diag_launch<5>(mda, grid, st); break;
+    case 6: pw_mean_diag_launch<6>(mda, grid, st); break;
+    case 7: pw_mean_diag_launch<7>(mda, grid, st); break;
+    default: pw_mean_diag_launch<8>(mda, grid, st); break;
+  }
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_mean_diag(mean)");
+  hipLaunchKernelGGL(k_pw_mean_merge, dim3((unsigned)((n_q + kPwThreads - 1) / kPwThreads), (unsigned)dv), dim3(kPwThreads), 0, st, ma);
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_mean_diag(merge)");
+  return GJX_OK;
+}
+
+extern "C" size_t gjx_pairwise_gauss_pick_diag_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
+  if (d > GJX_PAIRWISE_DIAG_MAX_DIM) return 0;
+  return gjx_pairwise_gauss_pick_workspace_bytes(n_q, n_k, d);
+}
+
+extern "C" int gjx_pairwise_gauss_pick_diag(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k,
+                                            int32_t d, const float* bias, const float* prec, int64_t stride_p, int32_t prec_side,
+                                            const float* centre, const float* u, int32_t* pick, float* lse, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  using namespace gjx;
+  if (!q || !k || !u || !pick || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      stride_q < n_q || stride_k < n_k)
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_gauss_pick_diag: bad argument");
+  if (const int rc = pw_diag_keys_only("gjx_pairwise_gauss_pick_diag", prec, stride_p, n_k, prec_side, d)) return rc;
+  PwPickDiagArgs pda;
+  memset(&pda, 0, sizeof(pda));
+  PwPickArgs& pa = pda.pa;
+  PwArgs& a = pa.pw;
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_gauss_pick_diag_workspace_bytes(n_q, n_k, d))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_gauss_pick_diag: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = lse;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k; a.p = 0.0f;             // (0: k_pw_pick_plan then adds no query term)
+  pa.u = u; pa.pick = pick;
+  pa.L = (float*)(a.part + (size_t)a.n_splits * (size_t)n_q);
+  pa.resid = pa.L + n_q;
+  pa.rbefore = pa.resid + n_q;
+  pa.own = (int32_t*)(pa.rbefore + n_q);
+  pa.rchunk = pa.own + n_q;
+  pda.prec = prec; pda.stride_p = stride_p;
+  PwDiagArgs da;
+  memset(&da, 0, sizeof(da));
+  da.pw = a; da.prec = prec; da.stride_p = stride_p; da.side = GJX_PAIRWISE_PREC_KEYS;
+  const dim3 grid((unsigned)((n_q + kPwBlockQ - 1) / kPwBlockQ), (unsigned)a.n_splits);
+  const dim3 per_query((unsigned)((n_q + kPwThreads - 1) / kPwThreads));
+  switch ((2 * d + 3) / 4) {
+    case 1: pw_diag_launch<1>(da, grid, st); break;
+    case 2: pw_diag_launch<2>(da, grid, st); break;
+    case 3: pw_diag_launch<3>(da, grid, st); break;
+    case 4: pw_diag_launch<4>(da, grid, st); break;
+    case 5: pw_diag_launch<5>(da, grid, st); break;
+    case 6: pw_diag_launch<6>(da, grid, st); break;
+    case 7: pw_diag_launch<7>(da, grid, st); break;
+    default: pw_diag_launch<8>(da, grid, st); break;
+  }
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_pick_diag(lse)");
+  hipLaunchKernelGGL(k_pw_pick_plan, per_query, dim3(kPwThreads), 0, st, pa);
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_pick_diag(plan)");
+  switch ((2 * d + 3) / 4) {
+    case 1: pw_pick_diag_launch<1>(pda, grid, st); break;
+    case 2: pw_pick_diag_launch<2>(pda, grid, st); break;
+    case 3: pw_pick_diag_launch<3>(pda, grid, st); break;
+    case 4: pw_pick_diag_launch<4>(pda, grid, st); break;
+    case 5: pw_pick_diag_launch<5>(pda, grid, st); break;
+    case 6: pw_pick_diag_launch<6>(pda, grid, st); break;
+    case 7: pw_pick_diag_launch<7>(pda, grid, st); break;
+    default: pw_pick_diag_launch<8>(pda, grid, st); break;
+  }
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_pick_diag(pick)");
+  hipLaunchKernelGGL(k_pw_pick_finish_diag, per_query, dim3(kPwThreads), 0, st, pda);
+  GJX_CHECK_LAUNCH("gjx_pairwise_gauss_pick_diag(finish)");
   return GJX_OK;
 }

@@ -737,9 +737,8 @@ def _pairwise_args(name: str, q_rows, k_rows, bias, precision, centre):
 _PAIRWISE_PREC_SIDES = {"keys": A.PAIRWISE_PREC_KEYS, "queries": A.PAIRWISE_PREC_QUERIES}
 
 
-def _pairwise_lse_diag(q_rows, k_rows, bias, precision: torch.Tensor, side: int, centre, ws, out) -> torch.Tensor:
-    """pairwise_gauss_lse with a precision matrix: gjx_pairwise_gauss_lse_diag"""
-    name = "pairwise_gauss_lse"
+def _pairwise_diag_args(name: str, q_rows, k_rows, bias, precision: torch.Tensor, side: int, centre):
+    """_pairwise_args for a call with a precision matrix -> its tuple with (prec, stride_p) in the place of the number"""
     q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, _, centre = _pairwise_args(name, q_rows, k_rows, bias, 1.0, centre)
     if d > A.PAIRWISE_DIAG_MAX_DIM:
         raise ValueError(f"{name}: at most {A.PAIRWISE_DIAG_MAX_DIM} components with a precision matrix, not {d}")
@@ -748,6 +747,23 @@ def _pairwise_lse_diag(q_rows, k_rows, bias, precision: torch.Tensor, side: int,
     if (d_p, n_p) != (d, n_side):
         raise ValueError(f"{name}: a precision matrix of the {'keys' if side == A.PAIRWISE_PREC_KEYS else 'queries'} must be "
                          f"f32[{d}][{n_side}], not [{d_p}][{n_p}]")
+    return q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, (prec, stride_p), centre
+
+
+def _pairwise_keys_precision(name: str, precision, precision_of: str):
+    """the precision of pairwise_gauss_mean / pairwise_gauss_pick -> it is a matrix (of the keys: the only side those serve)"""
+    if not (isinstance(precision, torch.Tensor) and precision.dim() > 0):
+        return False
+    if precision_of != "keys":
+        raise ValueError(f"{name}: a precision matrix must belong to the keys (precision_of='keys'), not {precision_of!r}")
+    return True
+
+
+def _pairwise_lse_diag(q_rows, k_rows, bias, precision: torch.Tensor, side: int, centre, ws, out) -> torch.Tensor:
+    """pairwise_gauss_lse with a precision matrix: gjx_pairwise_gauss_lse_diag"""
+    name = "pairwise_gauss_lse"
+    q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, (prec, stride_p), centre = _pairwise_diag_args(name, q_rows, k_rows, bias,
+                                                                                                         precision, side, centre)
     dev = q_rows.device
     if out is None:
         out = torch.empty(n_q, dtype=torch.float32, device=dev)
@@ -792,16 +808,23 @@ def pairwise_gauss_lse(q_rows: torch.Tensor, k_rows: torch.Tensor, bias=None, pr
     return out
 
 
-def pairwise_gauss_mean(q_rows: torch.Tensor, k_rows: torch.Tensor, v_rows: torch.Tensor, bias=None, precision: float = 1.0,
-                        centre=None, ws=None, out=None, lse_out=None) -> dict:
+def pairwise_gauss_mean(q_rows: torch.Tensor, k_rows: torch.Tensor, v_rows: torch.Tensor, bias=None, precision=1.0,
+                        centre=None, ws=None, out=None, lse_out=None, precision_of: str = "keys") -> dict:
     """gjx_pairwise_gauss_mean: queries f32[d][n_q], keys f32[d][n_k] and values f32[dv][n_k] (SoA views as in ``pairwise_gauss_lse``)
     -> dict(mean f32[dv][n_q], lse f32[n_q]):  mean[j][r] = sum_c softmax_c(bias[c] - 1/2 precision |q_r - k_c|^2) v[j][c], the
     Gaussian-kernel weighted mean of the values for every query, and the log-sum-exp of the same scores.  A dead key (bias -inf or
     NaN) is left out whatever its coordinates and values hold; no live key gives mean NaN and lse -inf; a query with a non-finite
     coordinate gives NaN for that query alone; a live key's non-finite value makes its component of every mean NaN.  d, dv <= 32.
-    Both products on the matrix cores, nothing of size n_q x n_k is stored; two launches, bit-reproducible."""
+    Both products on the matrix cores, nothing of size n_q x n_k is stored; two launches, bit-reproducible.
+    ``precision`` may be a tensor f32[d][n_k], one diagonal precision per key (gjx_pairwise_gauss_mean_diag; a view under the rules of
+    the particle sets): the score is bias[c] - 1/2 sum_j precision[j][c] (q[j][r] - k[j][c])^2, under the rules of ``pairwise_gauss_lse``
+    with a precision matrix of the keys (the normaliser 1/2 sum_j log precision[j][c] is the caller's: fold it into ``bias``; a live key's
+    entry that is not > 0 and finite makes every output NaN).  d <= 16 then; ``precision_of="queries"`` is refused."""
     name = "pairwise_gauss_mean"
-    q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre = _pairwise_args(name, q_rows, k_rows, bias, precision, centre)
+    diag = _pairwise_keys_precision(name, precision, precision_of)
+    q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre = (
+        _pairwise_diag_args(name, q_rows, k_rows, bias, precision, A.PAIRWISE_PREC_KEYS, centre) if diag else
+        _pairwise_args(name, q_rows, k_rows, bias, precision, centre))
     v_rows, stride_v, dv, n_v = _pairwise_rows("v_rows", v_rows)
     if n_v != n_k:
         raise ValueError(f"{name}: {n_k} keys, {n_v} values")
@@ -818,22 +841,33 @@ def pairwise_gauss_mean(q_rows: torch.Tensor, k_rows: torch.Tensor, v_rows: torc
         raise ValueError(f"{name}: lse_out must be a contiguous f32[n_q]")
     if ws is None:
         ws = torch.empty(load().gjx_pairwise_gauss_mean_workspace_bytes(n_q, n_k, d, dv), dtype=torch.uint8, device=dev)   # partials only
+    if diag:                                                                  # (same workspace size)
+        check(load().gjx_pairwise_gauss_mean_diag(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(v_rows), stride_v, dv,
+                                                  _ptr(bias), _ptr(p[0]), p[1], A.PAIRWISE_PREC_KEYS, _ptr(centre), _ptr(out), _ptr(lse_out),
+                                                  _ptr(ws), ws.numel(), _stream()), "gjx_pairwise_gauss_mean_diag")
+        return {"mean": out, "lse": lse_out}
     check(load().gjx_pairwise_gauss_mean(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(v_rows), stride_v, dv, _ptr(bias),
                                          p, _ptr(centre), _ptr(out), _ptr(lse_out), _ptr(ws), ws.numel(), _stream()),
           "gjx_pairwise_gauss_mean")
     return {"mean": out, "lse": lse_out}
 
 
-def pairwise_gauss_pick(q_rows: torch.Tensor, k_rows: torch.Tensor, u: torch.Tensor, bias=None, precision: float = 1.0, centre=None,
-                        ws=None, out=None, lse_out=None) -> dict:
+def pairwise_gauss_pick(q_rows: torch.Tensor, k_rows: torch.Tensor, u: torch.Tensor, bias=None, precision=1.0, centre=None,
+                        ws=None, out=None, lse_out=None, precision_of: str = "keys") -> dict:
     """gjx_pairwise_gauss_pick: queries f32[d][n_q], keys f32[d][n_k] (SoA views as in ``pairwise_gauss_lse``) and one uniform per
     query ``u`` f32[n_q] -> dict(pick i32[n_q], lse f32[n_q]): pick[r] is the smallest key index c at which the cumulative of
     exp(bias[c] - 1/2 precision |q_r - k_c|^2) over the keys in index order reaches u[r] times its total — a categorical draw per query
     by inverse CDF, the random numbers being the caller's.  Dead keys (bias -inf or NaN) are never picked; u <= 0 gives the first key
     with positive mass, u >= 1 the last; -1 where there is nothing to pick (no live key, a non-finite query, a poisoned live key, a NaN
-    u).  d <= 32.  Two passes on the matrix cores, nothing of size n_q x n_k is stored; four launches, bit-reproducible."""
+    u).  d <= 32.  Two passes on the matrix cores, nothing of size n_q x n_k is stored; four launches, bit-reproducible.
+    ``precision`` may be a tensor f32[d][n_k], one diagonal precision per key (gjx_pairwise_gauss_pick_diag), exactly as in
+    ``pairwise_gauss_mean``: the mass of key c is exp(bias[c] - 1/2 sum_j precision[j][c] (q[j][r] - k[j][c])^2), a live key's bad entry
+    makes every pick -1.  d <= 16 then; ``precision_of="queries"`` is refused."""
     name = "pairwise_gauss_pick"
-    q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre = _pairwise_args(name, q_rows, k_rows, bias, precision, centre)
+    diag = _pairwise_keys_precision(name, precision, precision_of)
+    q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre = (
+        _pairwise_diag_args(name, q_rows, k_rows, bias, precision, A.PAIRWISE_PREC_KEYS, centre) if diag else
+        _pairwise_args(name, q_rows, k_rows, bias, precision, centre))
     if u.dtype != torch.float32 or u.dim() != 1 or u.numel() != n_q or not u.is_contiguous():
         raise ValueError(f"{name}: u must be a contiguous f32[n_q]")
     dev = q_rows.device
@@ -847,12 +881,41 @@ def pairwise_gauss_pick(q_rows: torch.Tensor, k_rows: torch.Tensor, u: torch.Ten
         raise ValueError(f"{name}: lse_out must be a contiguous f32[n_q]")
     if ws is None:
         ws = torch.empty(load().gjx_pairwise_gauss_pick_workspace_bytes(n_q, n_k, d), dtype=torch.uint8, device=dev)   # partials only
+    if diag:                                                                  # (same workspace size)
+        check(load().gjx_pairwise_gauss_pick_diag(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(bias), _ptr(p[0]), p[1],
+                                                  A.PAIRWISE_PREC_KEYS, _ptr(centre), _ptr(u), _ptr(out), _ptr(lse_out), _ptr(ws), ws.numel(),
+                                                  _stream()), "gjx_pairwise_gauss_pick_diag")
+        return {"pick": out, "lse": lse_out}
     check(load().gjx_pairwise_gauss_pick(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(bias), p, _ptr(centre), _ptr(u),
                                          _ptr(out), _ptr(lse_out), _ptr(ws), ws.numel(), _stream()), "gjx_pairwise_gauss_pick")
     return {"pick": out, "lse": lse_out}
 
 
-def ffbs_sample_paths(states, logw_steps, means, precision: float, key, n_paths: int) -> dict:
+def _ffbs_precision_tables(name: str, precision, T: int, d: int, K: int):
+    """``precision`` of the ffbs_* calls, checked before any device work -> None for a number; for a list or tuple of one f32[d][K] or
+    f32[d] per step (the last is not read) a function entry -> its f32[d][K] table (a constant f32[d] is expanded once)"""
+    if not isinstance(precision, (list, tuple)):
+        return None
+    if len(precision) != T:
+        raise ValueError(f"{name}: a sequence of precisions must have one entry per step")
+    for P in precision[:T - 1]:
+        if not isinstance(P, torch.Tensor) or P.dtype != torch.float32 or tuple(P.shape) not in ((d,), (d, K)):
+            raise ValueError(f"{name}: a step's precision must be f32[{d}][{K}] or f32[{d}]")
+    if d > A.PAIRWISE_DIAG_MAX_DIM and T > 1:
+        raise ValueError(f"{name}: at most {A.PAIRWISE_DIAG_MAX_DIM} components with per-step precisions, not {d}")
+    tables = {}
+
+    def table(P):
+        if P.dim() == 2:
+            return P
+        if id(P) not in tables:
+            tables[id(P)] = P.reshape(d, 1).expand(d, K).contiguous()
+        return tables[id(P)]
+
+    return table
+
+
+def ffbs_sample_paths(states, logw_steps, means, precision, key, n_paths: int) -> dict:
     """Backward simulation (FFBSi, Godsill, Doucet & West 2004): ``n_paths`` joint draws from p(x_{0:T-1} | y_{1:T}) over the stored
     particles -> dict(idx i32[T][n_paths], paths f32[T][d][n_paths]), paths[t] = states[t][:, idx[t]]; arguments as ``ffbs_weights``.
     idx[T-1] is a multinomial draw from the last step's filtering weights (``weight_cumsum`` + ``resample_multinomial`` under
@@ -861,7 +924,10 @@ def ffbs_sample_paths(states, logw_steps, means, precision: float, key, n_paths:
     centre the weighted mean of states[t+1], uniforms (bits >> 8 + 1/2) 2^-24 of the first word of threefry2x32(key, n_paths, ctr_hi=t),
     rounded to float32 and kept below 1: strictly inside (0, 1), made on the device.
     Unlike ``ParticleHistory.paths`` every step's K particles can be reached.  O(T n_paths K d); outputs and workspace are allocated
-    once, nothing is read back."""
+    once, nothing is read back.
+    ``precision`` may be the per-step list of ``ffbs_weights`` (d <= 16): the parents are the keys, so step t's call is
+    ``pairwise_gauss_pick`` with the matrix precision[t] of the keys and the parents' normaliser 1/2 sum_j log precision[t][j][i], which
+    differs per key and does not cancel in the draw, added to the bias."""
     T, n = len(states), int(n_paths)
     if T == 0 or len(logw_steps) != T or len(means) != T:
         raise ValueError("ffbs_sample_paths: states, logw_steps and means must have one entry per step")
@@ -869,6 +935,7 @@ def ffbs_sample_paths(states, logw_steps, means, precision: float, key, n_paths:
         raise ValueError(f"ffbs_sample_paths: n_paths must be positive, not {n_paths}")
     from .core import fold_in
     d, K = int(states[0].shape[0]), int(states[0].shape[1])
+    table = _ffbs_precision_tables("ffbs_sample_paths", precision, T, d, K)
     dev = states[0].device
     ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
     lw_filter = [torch.zeros(K, dtype=torch.float32, device=dev) if lw is None else lw.reshape(-1) for lw in logw_steps]
@@ -885,7 +952,11 @@ def ffbs_sample_paths(states, logw_steps, means, precision: float, key, n_paths:
         centre = weighted_moments(states[t + 1], logw_steps[t + 1], "mean")["mean"]
         bits = threefry2x32(key, n, ctr_hi=t, device=dev)[:, 0]
         u = ((bits >> 8) & 0xFFFFFF).to(torch.float64).add_(0.5).mul_(2.0 ** -24).to(torch.float32).clamp_(max=1.0 - 2.0 ** -24)
-        pairwise_gauss_pick(paths[t + 1], means[t], u, lw - torch.logsumexp(lw, 0), precision, centre, ws, out=idx[t], lse_out=lse)
+        bias, P = lw - torch.logsumexp(lw, 0), precision
+        if table is not None:
+            P = table(precision[t])
+            bias = bias + 0.5 * torch.log(P).sum(0)
+        pairwise_gauss_pick(paths[t + 1], means[t], u, bias, P, centre, ws, out=idx[t], lse_out=lse)
         gather_rows(states[t], idx[t], paths[t])
     return {"idx": idx, "paths": paths}
 
@@ -898,11 +969,15 @@ def ffbs_pair_moments(states, logw_steps, means, precision: float, weights=None)
     c_j the conditional mean of the parent given child j: one ``pairwise_gauss_mean`` call per step (queries states[t], keys
     means[t-1], values states[t-1], bias the normalised logw_steps[t-1], centre the weighted mean of states[t]), then the T-1 tables
     of c go through one ``weighted_cross_moments_steps`` call under log weights[t]; mean_prev is E[c] (tower rule).  At most 16
-    components.  O(T K^2 d); outputs and workspace are allocated once, nothing is read back."""
+    components.  O(T K^2 d); outputs and workspace are allocated once, nothing is read back.
+    ``precision`` may be the per-step list of ``ffbs_weights`` (which then gets the same list): the parents are the keys, so step t's
+    call is ``pairwise_gauss_mean`` with the matrix precision[t-1] of the keys and the parents' normaliser
+    1/2 sum_j log precision[t-1][j][i], which differs per key and does not cancel in the softmax, added to the bias."""
     T = len(states)
     if T == 0 or len(logw_steps) != T or len(means) != T:
         raise ValueError("ffbs_pair_moments: states, logw_steps and means must have one entry per step")
     d, K = int(states[0].shape[0]), int(states[0].shape[1])
+    table = _ffbs_precision_tables("ffbs_pair_moments", precision, T, d, K)
     dev = states[0].device
     _cross_rows("ffbs_pair_moments", "states", states[0])                     # (at most 16 rows: raised here as the moments call does)
     if weights is None:
@@ -918,8 +993,11 @@ def ffbs_pair_moments(states, logw_steps, means, precision: float, weights=None)
         lw = torch.zeros(K, dtype=torch.float32, device=dev) if logw_steps[t - 1] is None else logw_steps[t - 1].reshape(-1)
         lw = torch.where(torch.isnan(lw), ninf, lw)
         centre = weighted_moments(states[t], logw_steps[t], "mean")["mean"]
-        pairwise_gauss_mean(states[t], means[t - 1], states[t - 1], lw - torch.logsumexp(lw, 0), precision, centre, ws, out=cond[t - 1],
-                            lse_out=lse)
+        bias, P = lw - torch.logsumexp(lw, 0), precision
+        if table is not None:
+            P = table(precision[t - 1])
+            bias = bias + 0.5 * torch.log(P).sum(0)
+        pairwise_gauss_mean(states[t], means[t - 1], states[t - 1], bias, P, centre, ws, out=cond[t - 1], lse_out=lse)
     m = weighted_cross_moments_steps([(states[t], cond[t - 1], None, t) for t in range(1, T)], torch.log(weights))
     return {"mean": m["mean_a"], "mean_prev": m["mean_b"], "cross": m["cross"], "ess": m["stats"][:, 3]}
 
@@ -949,23 +1027,8 @@ def ffbs_weights(states, logw_steps, means, precision: float) -> torch.Tensor:
     d, K = int(states[0].shape[0]), int(states[0].shape[1])
     dev = states[0].device
     ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
-    diag = isinstance(precision, (list, tuple))
-    if diag:
-        if len(precision) != T:
-            raise ValueError("ffbs_weights: a sequence of precisions must have one entry per step")
-        for P in precision[:T - 1]:
-            if not isinstance(P, torch.Tensor) or P.dtype != torch.float32 or tuple(P.shape) not in ((d,), (d, K)):
-                raise ValueError(f"ffbs_weights: a step's precision must be f32[{d}][{K}] or f32[{d}]")
-        if d > A.PAIRWISE_DIAG_MAX_DIM and T > 1:
-            raise ValueError(f"ffbs_weights: at most {A.PAIRWISE_DIAG_MAX_DIM} components with per-step precisions, not {d}")
-        tables = {}                                                       # a constant f32[d] becomes its f32[d][K] table once
-
-        def table(P):
-            if P.dim() == 2:
-                return P
-            if id(P) not in tables:
-                tables[id(P)] = P.reshape(d, 1).expand(d, K).contiguous()
-            return tables[id(P)]
+    table = _ffbs_precision_tables("ffbs_weights", precision, T, d, K)
+    diag = table is not None
 
     def log_normalised(lw):
         lw = torch.where(torch.isnan(lw), ninf, lw)                       # (a NaN weight is dead, as everywhere in the library)

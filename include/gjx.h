@@ -1262,6 +1262,47 @@ int gjx_pairwise_gauss_lse_diag(const float* q /* f32[d][stride_q] */, int64_t s
                                 const float* bias /* f32[n_k] or NULL */, const float* prec /* f32[d][stride_p] */, int64_t stride_p,
                                 int32_t prec_side, const float* centre /* f32[d] or NULL */, float* out /* f32[n_q] */,
                                 void* workspace, size_t workspace_bytes, void* stream);
+/* gjx_pairwise_gauss_mean and gjx_pairwise_gauss_pick over the scores of gjx_pairwise_gauss_lse_diag, keys side:
+ *     s_rc       = bias[c] - 1/2 sum_{j < d} prec[j][c] (q[j][r] - k[j][c])^2
+ *     lse[r]     = log sum_c exp(s_rc)
+ *     mean[j][r] = sum_c exp(s_rc - lse[r]) v[j][c]                                   (gjx_pairwise_gauss_mean_diag)
+ *     pick[r]    = the smallest c with  sum_{c' <= c} exp(s_rc') >= u_r sum_c exp(s_rc)   (gjx_pairwise_gauss_pick_diag)
+ * the lag-one pair moments (FFBSm) and the backward-simulation draws (FFBSi) of a transition x_{t+1} ~ N(m(x_t), diag(1 / p(x_t))):
+ * in both the parents m(x_t) are the keys and the precision is the parent's.  The Gaussian normaliser 1/2 sum_j log prec[j][c] is
+ * NOT part of the score; it differs per key, so it cancels neither in the softmax nor in the draw: the caller folds it into bias.
+ *   prec, stride_p   f32[d][stride_p], stride_p >= n_k: a column per key, every entry > 0 and finite
+ *   prec_side        GJX_PAIRWISE_PREC_KEYS.  GJX_PAIRWISE_PREC_QUERIES is REFUSED (GJX_EUNSUPPORTED): neither smoother needs it
+ *                    and it would double the number of kernel instances.
+ *   d                1 .. GJX_PAIRWISE_DIAG_MAX_DIM;  dv: 1 .. GJX_PAIRWISE_MAX_DIM
+ *   everything else  as in gjx_pairwise_gauss_mean / gjx_pairwise_gauss_pick
+ * Semantics: the keys-side rules of gjx_pairwise_gauss_lse_diag, with the outputs of the isotropic calls.  A key whose bias is -inf or
+ * NaN is dead whatever its coordinates, precisions and values hold.  A live key with a precision that is not > 0 and < inf, a
+ * non-finite centred feature or C operand, or bias +inf poisons the call: every mean and lse NaN, every pick -1.  A query with a
+ * non-finite centred coordinate or square: NaN / -1 for that query alone.  A live key's non-finite value: NaN in that row of the
+ * mean.  No live key: mean NaN, lse -inf, pick -1.  A NaN u_r: pick -1.  The matrix instructions only ever see finite operands.
+ * Device work.  The launches of the isotropic calls (two; four), with the 2 d interleaved features of gjx_pairwise_gauss_lse_diag in
+ * place of the d coordinates in the kernels that make scores (v_mfma_f32_16x16x4_f32, f32 inputs; the pick's last launch scores the 64
+ * keys of the recorded chunk in the VALU with each key's own precisions).  The per-query launches are the isotropic calls' own, run
+ * with precision 0: under the keys side a query adds no term of its own and its verdict is the finiteness of sum_j q~_j^2.  No
+ * atomics, every sum in an order fixed by the shape: bit-reproducible.  The workspaces are the isotropic calls' sizes, 0 for
+ * d > GJX_PAIRWISE_DIAG_MAX_DIM and for every shape those refuse; they need no initialisation.
+ * GJX_EINVAL: a NULL q, k, v, mean, u, pick, prec or workspace; counts, d, dv out of range; a stride below its count; a prec_side that
+ * is neither constant.  GJX_EUNSUPPORTED: GJX_PAIRWISE_PREC_QUERIES; d > GJX_PAIRWISE_DIAG_MAX_DIM; dv > GJX_PAIRWISE_MAX_DIM.
+ * GJX_EWORKSPACE: less than the _workspace_bytes query.  Nothing is launched on a refusal. */
+size_t gjx_pairwise_gauss_mean_diag_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d, int32_t dv);
+int gjx_pairwise_gauss_mean_diag(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q,
+                                 const float* k /* f32[d][stride_k] */, int64_t stride_k, int64_t n_k, int32_t d,
+                                 const float* v /* f32[dv][stride_v] */, int64_t stride_v, int32_t dv,
+                                 const float* bias /* f32[n_k] or NULL */, const float* prec /* f32[d][stride_p] */, int64_t stride_p,
+                                 int32_t prec_side, const float* centre /* f32[d] or NULL */, float* mean /* f32[dv][n_q] */,
+                                 float* lse /* f32[n_q] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+size_t gjx_pairwise_gauss_pick_diag_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d);
+int gjx_pairwise_gauss_pick_diag(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q,
+                                 const float* k /* f32[d][stride_k] */, int64_t stride_k, int64_t n_k, int32_t d,
+                                 const float* bias /* f32[n_k] or NULL */, const float* prec /* f32[d][stride_p] */, int64_t stride_p,
+                                 int32_t prec_side, const float* centre /* f32[d] or NULL */, const float* u /* f32[n_q] */,
+                                 int32_t* pick /* i32[n_q] */, float* lse /* f32[n_q] or NULL */, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
