@@ -1240,6 +1240,247 @@ static void pw_pick_diag_launch(const PwPickDiagArgs& pda, dim3 grid, hipStream_
   hipLaunchKernelGGL(k_pw_pick_diag<DC>, grid, dim3(kPwThreads), 0, st, pda);
 }
 
+// ---- gjx_pairwise_gauss_argmax, gjx_pairwise_gauss_argmax_diag:  max[r] = max_c score(r, c),  arg[r] = the smallest c that attains it ----
+//
+// The max-plus twin of k_pw_lse / k_pw_lse_diag<KEYS> (the K x K part of the particle Viterbi recursion; with no bias, nearest key).
+// Scores are made as there: same centring, same zeroing of dead, tail and poisoned keys, kb as the C operand, pw_plan's grid and key
+// splits, 64-key tiles through double-buffered LDS under one barrier per tile; the diagonal kernel stages through PwDiagKeys<DC>.
+//
+// The running pair.  A lane's 16 accumulators of a tile and query group are the keys 64 t + 16 u + 4 quad + i of ONE query, so (max,
+// index) is lane-local for the whole key loop and there is no exponential anywhere.  Per tile and group: the tile's maximum joined
+// with the running one by 8 v_max3_f32; the index is touched only where the maximum rises STRICTLY (mn > m: an exec-masked region the
+// wave skips when no lane rises): a compare/select chain over the 16 accumulators from the last to the first leaves the first one
+// equal to mn.  Strictly: an equal score in a later tile never replaces an earlier key.  After the loop the four lanes of a query are
+// joined by (larger max, then smaller index), the split leaves {max, index} in part[split][query] (8 bytes: the lse's workspace), and
+// k_pw_argmax_merge, one thread per query, folds the splits in index order with strict >, adds the query's own term and converts
+// from units of log 2.  The smallest index among bit-equal scores wins at every level.  No atomics, no block waits for another,
+// nothing depends on the workspace's contents: bit-reproducible.
+//
+// Poison.  fmaxf drops a NaN, so the kb = NaN of a poisoned live key would vanish in the maximum where it spreads through the lse's
+// sum.  It is carried outside the arithmetic: the staging thread that writes a NaN kb sets a sticky flag, one __syncthreads_or after
+// the loop makes it the block's, and a poisoned block writes max = NaN into its partials.  Every block of a split stages every key
+// of the split, so every query sees it; the merge answers NaN / -1.  The loop pays nothing for it.  A bias of +inf is poison too
+// (the isotropic kernel's staging tests it here; PwDiagKeys already does).  A query's own verdict (non-finite centred coordinate or
+// norm) is the merge's, as in k_pw_merge; a score that overflows to +inf is NaN / -1 as well.
+struct PwArgmaxArgs {
+  PwArgs pw;               // pw.out: the maxima, or NULL; pw.part[split][query] = {max in units of log 2, the index's bits}; diag: pw.p = 0
+  int32_t* arg;
+  const float* prec;       // the diagonal call: f32[d][stride_p], a column per key
+  int64_t stride_p;
+};
+
+// one staged tile against the wave's four query groups; base = 64 tile + 4 quad, the lane's first key
+template <int DC>
+GJX_DEV void pw_argmax_tile(const float* sk, const float* sb, const float (&qf)[kPwGroups][DC], int base, int col, int quad,
+                            float (&m)[kPwGroups], int (&idx)[kPwGroups]) {
+  float af[4][DC];
+  pw_v4f seed[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {                           // the tile's four 16-key subtiles
+    seed[u] = *reinterpret_cast<const pw_v4f*>(&sb[16 * u + 4 * quad]);
+#pragma unroll
+    for (int c = 0; c < DC; ++c) af[u][c] = sk[(4 * c + quad) * kPwLd + 16 * u + col];
+  }
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    pw_v4f acc[4];
+    float mn = m[g];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      acc[u] = seed[u];
+#pragma unroll
+      for (int c = 0; c < DC; ++c) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][c], qf[g][c], acc[u], 0, 0, 0);
+      mn = fmaxf(fmaxf(fmaxf(fmaxf(mn, acc[u][0]), acc[u][1]), acc[u][2]), acc[u][3]);          // (fmaxf drops a NaN)
+    }
+    if (mn > m[g]) {                                      // some accumulator IS mn: the first of them, in key order
+      int j = 0;
+#pragma unroll
+      for (int u = 3; u >= 0; --u)
+#pragma unroll
+        for (int i = 3; i >= 0; --i) j = acc[u][i] == mn ? 16 * u + i : j;
+      m[g] = mn;
+      idx[g] = base + j;
+    }
+  }
+}
+
+// the four lanes of a query, the block's poison, the partial
+GJX_DEV void pw_argmax_partial(const PwArgs& a, int q0, int col, int quad, bool bad, float (&m)[kPwGroups], int (&idx)[kPwGroups]) {
+  const bool poisoned = __syncthreads_or(bad) != 0;
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {
+      const float om = __shfl_xor(m[g], off, 64);
+      const int oi = __shfl_xor(idx[g], off, 64);
+      const bool take = om > m[g] || (om == m[g] && oi < idx[g]);       // (no key yet: -inf and -1 on both sides)
+      m[g] = take ? om : m[g];
+      idx[g] = take ? oi : idx[g];
+    }
+    const int qi = q0 + 16 * g + col;
+    if (quad == 0 && qi < a.n_q)
+      a.part[(int64_t)blockIdx.y * a.n_q + qi] = make_float2(poisoned ? NAN : m[g], __int_as_float(idx[g]));
+  }
+}
+
+template <int DC>
+__global__ __launch_bounds__(kPwThreads) void k_pw_argmax(const PwArgmaxArgs aa) {
+  const PwArgs& a = aa.pw;
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sb[2][kPwTile];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;            // the MFMA's view of the lane
+  const int skey = tid >> 2, spart = tid & 3;             // the staging's view: key of the tile, components 4 c + spart
+
+  // the wave's query fragments, for the whole kernel
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  const float ps = a.p * kPwLog2e;
+  float qf[kPwGroups][DC];
+  float scen[DC];
+#pragma unroll
+  for (int c = 0; c < DC; ++c) {
+    const int dq = 4 * c + quad, ds = 4 * c + spart;
+    const float cen = (a.centre && dq < a.d) ? a.centre[dq] : 0.0f;
+    scen[c] = (a.centre && ds < a.d) ? a.centre[ds] : 0.0f;
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      const int qi = q0 + 16 * g + col;
+      qf[g][c] = (dq < a.d && qi < a.n_q) ? (a.q[(int64_t)dq * a.stride_q + qi] - cen) * ps : 0.0f;
+    }
+  }
+
+  float v[DC], b;
+  bool bad = false;                                       // this thread staged a poisoned key
+  auto load = [&](int tile) {
+    const int key = tile * kPwTile + skey;
+    const bool in = key < a.n_k;
+    b = in ? (a.bias ? a.bias[key] : 0.0f) : -INFINITY;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int ds = 4 * c + spart;
+      v[c] = (in && ds < a.d) ? a.k[(int64_t)ds * a.stride_k + key] - scen[c] : 0.0f;
+    }
+  };
+  auto store = [&](int buf) {
+    float k2 = 0.0f;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) k2 = fmaf(v[c], v[c], k2);
+    k2 = quad_sum(k2);
+    const bool dead = !(b > -INFINITY);                   // -inf or NaN
+    const bool zero = dead || !(k2 < INFINITY) || !(b < INFINITY);
+    bad |= zero && !dead;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) sk[buf][(4 * c + spart) * kPwLd + skey] = zero ? 0.0f : v[c];
+    if (spart == 0) sb[buf][skey] = dead ? -INFINITY : (zero ? NAN : (b - 0.5f * a.p * k2) * kPwLog2e);
+  };
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  float m[kPwGroups];
+  int idx[kPwGroups];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) { m[g] = -INFINITY; idx[g] = -1; }
+
+  load(t0);
+  store(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) load(t + 1);
+    pw_argmax_tile<DC>(sk[buf], sb[buf], qf, t * kPwTile + 4 * quad, col, quad, m, idx);
+    if (more) store(buf ^ 1);
+    __syncthreads();
+  }
+  pw_argmax_partial(a, q0, col, quad, bad, m, idx);
+}
+
+// the same loop over k_pw_lse_diag<DC, KEYS>'s scores: PwDiagKeys stages the 2 d features; the poison is read off the kb it wrote
+template <int DC>
+__global__ __launch_bounds__(kPwThreads) void k_pw_argmax_diag(const PwArgmaxArgs aa) {
+  const PwArgs& a = aa.pw;
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sb[2][kPwTile];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;
+  const int skey = tid >> 2, spart = tid & 3;
+
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  float qf[kPwGroups][DC];
+  PwDiagKeys<DC> keys;
+  keys.queries(a, q0, col, quad, spart, qf);
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  float m[kPwGroups];
+  int idx[kPwGroups];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) { m[g] = -INFINITY; idx[g] = -1; }
+  bool bad = false;
+  auto stage = [&](int buf) {
+    keys.store(a, sk[buf], sb[buf], skey, spart);
+    if (spart == 0) bad |= sb[buf][skey] != sb[buf][skey];                // (its own store: a live key staged as NaN)
+  };
+
+  keys.load(a, aa.prec, aa.stride_p, t0, skey, spart);
+  stage(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) keys.load(a, aa.prec, aa.stride_p, t + 1, skey, spart);
+    pw_argmax_tile<DC>(sk[buf], sb[buf], qf, t * kPwTile + 4 * quad, col, quad, m, idx);
+    if (more) stage(buf ^ 1);
+    __syncthreads();
+  }
+  pw_argmax_partial(a, q0, col, quad, bad, m, idx);
+}
+
+// one thread per query: the splits in index order (strict >: the earlier split keeps a tie), the query's own term and verdict.  The
+// diagonal call runs it with p = 0: under the keys side a query adds nothing and its verdict is the finiteness of sum_j q~_j^2.
+__global__ __launch_bounds__(kPwThreads) void k_pw_argmax_merge(const PwArgmaxArgs aa) {
+  const PwArgs& a = aa.pw;
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  if (r >= a.n_q) return;
+  float q2 = 0.0f;
+  for (int i = 0; i < a.d; ++i) {
+    const float x = a.q[(int64_t)i * a.stride_q + r] - (a.centre ? a.centre[i] : 0.0f);
+    q2 = fmaf(x, x, q2);
+  }
+  float m = -INFINITY;
+  int idx = -1;
+  bool bad = false;
+  for (int y = 0; y < a.n_splits; ++y) {
+    const float2 p = a.part[(int64_t)y * a.n_q + r];
+    bad |= p.x != p.x;
+    if (p.x > m) { m = p.x; idx = __float_as_int(p.y); }
+  }
+  // no live key: m = -inf, idx = -1
+  const bool ok = q2 < INFINITY && !bad && m < INFINITY;
+  aa.arg[r] = ok ? idx : -1;
+  if (a.out) a.out[r] = ok ? m * kPwLn2 - 0.5f * a.p * q2 : NAN;
+}
+
+// both calls after their own checks: chunks = DC, diag picks the kernel
+static int pw_argmax_launch(const char* who, const PwArgmaxArgs& aa, int chunks, bool diag, hipStream_t st) {
+  const PwArgs& a = aa.pw;
+  const dim3 grid((unsigned)((a.n_q + kPwBlockQ - 1) / kPwBlockQ), (unsigned)a.n_splits), block(kPwThreads);
+#define GJX_PW_ARGMAX(DC)                                                     \
+  case DC:                                                                    \
+    if (diag) hipLaunchKernelGGL(k_pw_argmax_diag<DC>, grid, block, 0, st, aa); \
+    else hipLaunchKernelGGL(k_pw_argmax<DC>, grid, block, 0, st, aa);         \
+    break;
+  switch (chunks) {
+    GJX_PW_ARGMAX(1) GJX_PW_ARGMAX(2) GJX_PW_ARGMAX(3) GJX_PW_ARGMAX(4) GJX_PW_ARGMAX(5) GJX_PW_ARGMAX(6) GJX_PW_ARGMAX(7)
+    default: GJX_PW_ARGMAX(8)
+  }
+#undef GJX_PW_ARGMAX
+  GJX_CHECK_LAUNCH(who);
+  hipLaunchKernelGGL(k_pw_argmax_merge, dim3((unsigned)((a.n_q + kPwThreads - 1) / kPwThreads)), block, 0, st, aa);
+  GJX_CHECK_LAUNCH(who);
+  return GJX_OK;
+}
+
 }  // namespace gjx
 
 extern "C" size_t gjx_pairwise_gauss_lse_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
@@ -1554,4 +1795,57 @@ extern "C" int gjx_pairwise_gauss_pick_diag(const float* q, int64_t stride_q, in
   hipLaunchKernelGGL(k_pw_pick_finish_diag, per_query, dim3(kPwThreads), 0, st, pda);
   GJX_CHECK_LAUNCH("gjx_pairwise_gauss_pick_diag(finish)");
   return GJX_OK;
+}
+
+extern "C" size_t gjx_pairwise_gauss_argmax_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
+  return gjx_pairwise_gauss_lse_workspace_bytes(n_q, n_k, d);             // {max, index} per (query, split)
+}
+
+extern "C" int gjx_pairwise_gauss_argmax(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k,
+                                         int32_t d, const float* bias, float precision, const float* centre, int32_t* arg, float* max,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace gjx;
+  if (!q || !k || !arg || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      stride_q < n_q || stride_k < n_k || !(precision > 0.0f) || !(precision < INFINITY))
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_gauss_argmax: bad argument");
+  if (d > GJX_PAIRWISE_MAX_DIM)
+    return gjx_fail(GJX_EUNSUPPORTED, "gjx_pairwise_gauss_argmax: more than GJX_PAIRWISE_MAX_DIM components");
+  PwArgmaxArgs aa;
+  memset(&aa, 0, sizeof(aa));
+  PwArgs& a = aa.pw;
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_gauss_argmax_workspace_bytes(n_q, n_k, d))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_gauss_argmax: workspace too small");
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = max;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k; a.p = precision;
+  aa.arg = arg;
+  return pw_argmax_launch("gjx_pairwise_gauss_argmax", aa, (d + 3) / 4, false, (hipStream_t)stream);
+}
+
+extern "C" size_t gjx_pairwise_gauss_argmax_diag_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
+  if (d > GJX_PAIRWISE_DIAG_MAX_DIM) return 0;
+  return gjx_pairwise_gauss_lse_workspace_bytes(n_q, n_k, d);
+}
+
+extern "C" int gjx_pairwise_gauss_argmax_diag(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k,
+                                              int32_t d, const float* bias, const float* prec, int64_t stride_p, int32_t prec_side,
+                                              const float* centre, int32_t* arg, float* max, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+  using namespace gjx;
+  if (!q || !k || !arg || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      stride_q < n_q || stride_k < n_k)
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_gauss_argmax_diag: bad argument");
+  if (const int rc = pw_diag_keys_only("gjx_pairwise_gauss_argmax_diag", prec, stride_p, n_k, prec_side, d)) return rc;
+  PwArgmaxArgs aa;
+  memset(&aa, 0, sizeof(aa));
+  PwArgs& a = aa.pw;
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_gauss_argmax_diag_workspace_bytes(n_q, n_k, d))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_gauss_argmax_diag: workspace too small");
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = max;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k; a.p = 0.0f;             // (0: k_pw_argmax_merge then adds no query term)
+  aa.arg = arg; aa.prec = prec; aa.stride_p = stride_p;
+  return pw_argmax_launch("gjx_pairwise_gauss_argmax_diag", aa, (2 * d + 3) / 4, true, (hipStream_t)stream);   // chunks of 4 features
 }

@@ -242,6 +242,26 @@ class ParticleHistory(LineageSmoothing):
         self.backward_indices = res["idx"]
         return res["paths"]
 
+    def map_path(self):
+        """-> f32[T][dx]: the single most probable trajectory through the stored particles (particle Viterbi,
+        ``kernels.ffbs_map_path``) under the model: means[t] = A x_t and precision 1 / q^2 as in ``ffbs_weights``, the recorded
+        per-step log-weights as log g(y_t | x_t) and log p(x_0) = -1/2 |x_0|^2 / q0^2.  Unlike ``smoothed_moments()["mean"]`` it is a
+        sequence of states the model can produce, and unlike ``paths()`` it may pass through any of a step's K particles; O(T K^2 dx).
+        ``map_indices`` holds its particle indices i32[T], ``map_log_joint`` its log joint up to the constants.  Refusals as
+        ``ffbs_weights``."""
+        import torch
+        from .. import kernels
+        if self._moved:
+            raise NotImplementedError("map_path: a resample-move history stores moved parents; its transition is not additive-Gaussian")
+        if self.ssm is None or len(self.logw_steps) != len(self.states):
+            raise ValueError("map_path: the history lacks the model or the per-step log-weights (BootstrapFilter.run records them)")
+        A_dev = torch.from_numpy(self.ssm.A).to(self.states[0].device)
+        means = [torch.matmul(A_dev, x) for x in self.states]
+        prior = (self.states[0] * self.states[0]).sum(0) * (-0.5 / (self.ssm.q0 * self.ssm.q0))
+        res = kernels.ffbs_map_path(self.states, self.logw_steps, means, 1.0 / (self.ssm.q * self.ssm.q), prior)
+        self.map_indices, self.map_log_joint = res["idx"], res["log_joint"]
+        return res["path"]
+
     def _smoothing_logw(self, method: str = "lineage"):
         import torch
         if method == "lineage":

@@ -891,6 +891,43 @@ def pairwise_gauss_pick(q_rows: torch.Tensor, k_rows: torch.Tensor, u: torch.Ten
     return {"pick": out, "lse": lse_out}
 
 
+def pairwise_gauss_argmax(q_rows: torch.Tensor, k_rows: torch.Tensor, bias=None, precision=1.0, centre=None, ws=None, out=None,
+                          max_out=None, precision_of: str = "keys") -> dict:
+    """gjx_pairwise_gauss_argmax: queries f32[d][n_q], keys f32[d][n_k] (SoA views as in ``pairwise_gauss_lse``) -> dict(arg i32[n_q],
+    max f32[n_q]): max[r] = max_c (bias[c] - 1/2 precision |q_r - k_c|^2) and arg[r] the smallest key index that attains it in the
+    kernel's arithmetic — the K x K part of a Viterbi step over a particle grid, and with ``bias=None`` the nearest key.  Dead keys
+    (bias -inf or NaN) are never returned; no live key gives -1 / -inf; a non-finite query gives -1 / NaN for that query alone; a
+    poisoned live key (non-finite coordinate, bias +inf) gives -1 / NaN everywhere.  d <= 32.  One pass on the matrix cores, no
+    exponentials, nothing of size n_q x n_k is stored; two launches, bit-reproducible.
+    ``precision`` may be a tensor f32[d][n_k], one diagonal precision per key (gjx_pairwise_gauss_argmax_diag), exactly as in
+    ``pairwise_gauss_pick``: the score is bias[c] - 1/2 sum_j precision[j][c] (q[j][r] - k[j][c])^2, the normaliser is the caller's, a
+    live key's bad entry makes every result -1 / NaN.  d <= 16 then; ``precision_of="queries"`` is refused."""
+    name = "pairwise_gauss_argmax"
+    diag = _pairwise_keys_precision(name, precision, precision_of)
+    q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre = (
+        _pairwise_diag_args(name, q_rows, k_rows, bias, precision, A.PAIRWISE_PREC_KEYS, centre) if diag else
+        _pairwise_args(name, q_rows, k_rows, bias, precision, centre))
+    dev = q_rows.device
+    if out is None:
+        out = torch.empty(n_q, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.numel() != n_q or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous i32[n_q]")
+    if max_out is None:
+        max_out = torch.empty(n_q, dtype=torch.float32, device=dev)
+    elif max_out.dtype != torch.float32 or max_out.numel() != n_q or not max_out.is_contiguous():
+        raise ValueError(f"{name}: max_out must be a contiguous f32[n_q]")
+    if ws is None:
+        ws = torch.empty(load().gjx_pairwise_gauss_argmax_workspace_bytes(n_q, n_k, d), dtype=torch.uint8, device=dev)   # partials only
+    if diag:                                                                  # (same workspace size)
+        check(load().gjx_pairwise_gauss_argmax_diag(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(bias), _ptr(p[0]), p[1],
+                                                    A.PAIRWISE_PREC_KEYS, _ptr(centre), _ptr(out), _ptr(max_out), _ptr(ws), ws.numel(),
+                                                    _stream()), "gjx_pairwise_gauss_argmax_diag")
+        return {"arg": out, "max": max_out}
+    check(load().gjx_pairwise_gauss_argmax(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(bias), p, _ptr(centre),
+                                           _ptr(out), _ptr(max_out), _ptr(ws), ws.numel(), _stream()), "gjx_pairwise_gauss_argmax")
+    return {"arg": out, "max": max_out}
+
+
 def _ffbs_precision_tables(name: str, precision, T: int, d: int, K: int):
     """``precision`` of the ffbs_* calls, checked before any device work -> None for a number; for a list or tuple of one f32[d][K] or
     f32[d] per step (the last is not read) a function entry -> its f32[d][K] table (a constant f32[d] is expanded once)"""
@@ -959,6 +996,69 @@ def ffbs_sample_paths(states, logw_steps, means, precision, key, n_paths: int) -
         pairwise_gauss_pick(paths[t + 1], means[t], u, bias, P, centre, ws, out=idx[t], lse_out=lse)
         gather_rows(states[t], idx[t], paths[t])
     return {"idx": idx, "paths": paths}
+
+
+def ffbs_map_path(states, loglik_steps, means, precision, log_prior=None) -> dict:
+    """The single most probable trajectory through the stored particles (particle Viterbi; Godsill, Doucet & West 2001) of a recorded
+    filter run with an additive-Gaussian transition -> dict(idx i32[T], path f32[T][d], log_joint f64 scalar), path[t] =
+    states[t][:, idx[t]]; ``states``, ``means`` and ``precision`` as in ``ffbs_weights``.
+      loglik_steps[t]  f32[K], log g(y_t | x_t^i) up to a per-step constant: a bootstrap filter's incremental log-weights (None: zeros;
+                       -inf / NaN: dead)
+      log_prior        f32[K], log p(x_0^i) up to a constant (None: zeros)
+    Recursion:  delta_0 = log_prior + loglik_0;  delta_t^j = loglik_t^j + max_i [delta_{t-1}^i + log f(x_t^j | x_{t-1}^i)],  psi_t^j the
+    maximising i: one ``pairwise_gauss_argmax`` call per step (queries states[t], keys means[t-1], bias delta_{t-1}, centre the weighted
+    mean of states[t]), then idx[T-1] = argmax delta_{T-1} and idx[t-1] = psi_t[idx[t]].  delta_t is shifted by its own maximum every
+    step (the argmax does not move, the bias stays small); the shifts add up to ``log_joint``, the path's log prior + log-likelihoods
+    + log transition densities without the constants left out above.  A particle with a non-finite coordinate is dead from its step on.
+    If a step leaves no live particle, idx is -1 and path NaN from the last step back to wherever the chain broke, log_joint -inf.
+    O(T K^2 d) on the matrix cores, no exponentials; outputs and workspace are allocated once, backtracking indexes on the device,
+    nothing is read back.
+    ``precision`` may be the per-step list of ``ffbs_weights`` (d <= 16): the parents are the keys, so step t's call takes the matrix
+    precision[t-1] of the keys, and the parents' normaliser 1/2 sum_j log precision[t-1][j][i] is added to the bias (and so counts in
+    log_joint)."""
+    T = len(states)
+    if T == 0 or len(loglik_steps) != T or len(means) != T:
+        raise ValueError("ffbs_map_path: states, loglik_steps and means must have one entry per step")
+    d, K = int(states[0].shape[0]), int(states[0].shape[1])
+    table = _ffbs_precision_tables("ffbs_map_path", precision, T, d, K)
+    dev = states[0].device
+    if log_prior is not None and (log_prior.dtype != torch.float32 or log_prior.numel() != K):
+        raise ValueError("ffbs_map_path: log_prior must be f32[K]")
+    ninf = torch.full((), float("-inf"), dtype=torch.float64, device=dev)
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+
+    def shifted(delta):
+        """a NaN is dead -> delta minus its maximum (as it is where nobody lives), the maximum"""
+        delta = torch.where(torch.isnan(delta), ninf, delta)
+        top = delta.max()
+        return delta - torch.where(top > ninf, top, zero), top
+
+    ll = lambda t: 0.0 if loglik_steps[t] is None else loglik_steps[t].reshape(-1).double()
+    delta, log_joint = shifted(ll(0) + (torch.zeros(K, dtype=torch.float64, device=dev) if log_prior is None else log_prior.reshape(-1).double()))
+    psi = torch.full((T, K), -1, dtype=torch.int32, device=dev)
+    if T > 1:
+        ws = torch.empty(load().gjx_pairwise_gauss_argmax_workspace_bytes(K, K, d), dtype=torch.uint8, device=dev)
+        top = torch.empty(K, dtype=torch.float32, device=dev)
+    for t in range(1, T):
+        centre = weighted_moments(states[t], loglik_steps[t], "mean")["mean"]
+        P = precision
+        if table is not None:
+            P = table(precision[t - 1])
+            delta = delta + 0.5 * torch.log(P.double()).sum(0)
+        pairwise_gauss_argmax(states[t], means[t - 1], delta.float(), P, centre, ws, out=psi[t], max_out=top)
+        delta, shift = shifted(ll(t) + top.double())
+        log_joint = log_joint + shift
+    idx = torch.empty(T, dtype=torch.int32, device=dev)
+    path = torch.empty((T, d), dtype=torch.float32, device=dev)
+    nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+    cur = torch.where(delta.max() > ninf, delta.argmax(), -1).reshape(1)      # (index_select throughout: no index leaves the device)
+    for t in range(T - 1, -1, -1):
+        idx[t:t + 1] = cur
+        j = cur.clamp(min=0)
+        path[t] = torch.where(cur >= 0, states[t].index_select(1, j).reshape(d), nan)
+        if t > 0:
+            cur = torch.where(cur >= 0, psi[t].index_select(0, j).long(), -1)
+    return {"idx": idx, "path": path, "log_joint": log_joint}
 
 
 def ffbs_pair_moments(states, logw_steps, means, precision: float, weights=None) -> dict:

@@ -1303,6 +1303,47 @@ int gjx_pairwise_gauss_pick_diag(const float* q /* f32[d][stride_q] */, int64_t 
                                  int32_t prec_side, const float* centre /* f32[d] or NULL */, const float* u /* f32[n_q] */,
                                  int32_t* pick /* i32[n_q] */, float* lse /* f32[n_q] or NULL */, void* workspace,
                                  size_t workspace_bytes, void* stream);
+/* Pairwise Gaussian argmax: the max-plus twin of gjx_pairwise_gauss_lse.  With s(r, c) = bias[c] - 1/2 precision |q_r - k_c|^2
+ * (gjx_pairwise_gauss_argmax) or bias[c] - 1/2 sum_{j < d} prec[j][c] (q[j][r] - k[j][c])^2 (gjx_pairwise_gauss_argmax_diag):
+ *     max[r] = max_{c < n_k} s(r, c)
+ *     arg[r] = the SMALLEST key index whose score, as the kernel computes it, equals that maximum
+ * It is the K x K part of the Viterbi recursion over a particle grid (Godsill, Doucet & West 2001: the MAP trajectory of a recorded
+ * filter run): with queries x_t, keys m(x_{t-1}^i) and bias delta_{t-1},  delta_t^j = log g(y_t | x_t^j) + max[j]  and  psi_t^j =
+ * arg[j].  With no bias it is the nearest key in Euclidean (diagonal call: Mahalanobis-diagonal) distance.
+ *   q, k, d, bias, precision, centre   exactly as in gjx_pairwise_gauss_lse
+ *   prec, stride_p, prec_side, d       (diagonal call) exactly as in gjx_pairwise_gauss_pick_diag: a column per key, keys side only
+ *                                      (GJX_PAIRWISE_PREC_QUERIES: GJX_EUNSUPPORTED), d <= GJX_PAIRWISE_DIAG_MAX_DIM.  The normaliser
+ *                                      1/2 sum_j log prec[j][c] is the caller's: fold it into bias
+ *   arg        i32[n_q]
+ *   max        f32[n_q], or NULL.  Its error is the lse's score error (see `centre` there)
+ * Edge rules (the family's).  A key whose bias is -inf or NaN is DEAD: it is never returned, whatever its coordinates (and precisions)
+ * hold.  No live key: max = -inf, arg = -1.  A query with a non-finite coordinate, or a centred norm that overflows: max = NaN, arg =
+ * -1 for that query alone.  A LIVE key with a non-finite coordinate (or an overflowing centred norm; diagonal call: also a precision
+ * entry that is not > 0 and finite) poisons the call: max = NaN, arg = -1 for EVERY query.  So does a bias of +inf.  (A maximum drops
+ * a NaN where the lse's sum spreads it, so the poison travels beside the arithmetic: a flag of the staging threads, joined per block,
+ * written into the block's partials as max = NaN.)  A score that overflows to +inf: NaN / -1 for that query.
+ * Device work.  Two plain launches on `stream`, nothing read back, no atomics, no block waits for another.  Grid, key splits, staging
+ * and the matrix products are gjx_pairwise_gauss_lse's (diagonal call: the 2 d interleaved features of gjx_pairwise_gauss_lse_diag, keys
+ * side).  A lane's 16 accumulators of a staged tile are 16 keys of one query, so the running (max, index) is lane-local for the whole
+ * key loop and no exponential is evaluated: per tile 8 v_max3_f32, and only where the maximum rises strictly a compare/select chain
+ * that finds the first accumulator equal to it.  A query's four lanes are joined after the loop by (larger max, then smaller index);
+ * every (query, split) leaves {max, index} in the workspace and the second launch, one thread per query, folds the splits in index
+ * order with a strict comparison, adds -1/2 p |q~|^2 and converts to natural units.  The tie rule holds at every level and nothing
+ * depends on the workspace's contents: bit-reproducible.
+ * Refusals as gjx_pairwise_gauss_lse (diagonal call: as gjx_pairwise_gauss_pick_diag), with GJX_EINVAL for a NULL arg.  GJX_EWORKSPACE below
+ * the _workspace_bytes query, which is gjx_pairwise_gauss_lse's (0 for shapes the call refuses; diagonal: 0 for d >
+ * GJX_PAIRWISE_DIAG_MAX_DIM).  The workspace needs no initialisation.  Nothing is launched on a refusal. */
+size_t gjx_pairwise_gauss_argmax_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d);
+int gjx_pairwise_gauss_argmax(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q, const float* k /* f32[d][stride_k] */,
+                              int64_t stride_k, int64_t n_k, int32_t d, const float* bias /* f32[n_k] or NULL */, float precision,
+                              const float* centre /* f32[d] or NULL */, int32_t* arg /* i32[n_q] */, float* max /* f32[n_q] or NULL */,
+                              void* workspace, size_t workspace_bytes, void* stream);
+size_t gjx_pairwise_gauss_argmax_diag_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d);
+int gjx_pairwise_gauss_argmax_diag(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q,
+                                   const float* k /* f32[d][stride_k] */, int64_t stride_k, int64_t n_k, int32_t d,
+                                   const float* bias /* f32[n_k] or NULL */, const float* prec /* f32[d][stride_p] */, int64_t stride_p,
+                                   int32_t prec_side, const float* centre /* f32[d] or NULL */, int32_t* arg /* i32[n_q] */,
+                                   float* max /* f32[n_q] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
