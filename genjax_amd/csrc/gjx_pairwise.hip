@@ -1481,6 +1481,381 @@ static int pw_argmax_launch(const char* who, const PwArgmaxArgs& aa, int chunks,
   return GJX_OK;
 }
 
+// ---- gjx_pairwise_t_lse, gjx_pairwise_t_mean: the log-sum-exp and the mean over Student-t scores ----
+//
+//   score(r, c) = bias[c] - 1/2 (nu + d) log(1 + p |q_r - k_c|^2 / nu)
+// the multivariate t with nu degrees of freedom and scale matrix I / p, up to the constant that cancels: FFBSm for heavy-tailed
+// transition noise.  The bias sits outside a logarithm, so the matrix product cannot make the score as it does in k_pw_lse.  It makes
+// the scaled squared distance instead.  With pn = p / nu and tildes for values minus `centre`:
+//   x(r, c) = pn |q~_r|^2 + pn |k~_c|^2 - 2 pn q~_r . k~_c
+// The query fragment is scaled by -2 pn; kn_c = pn |k~_c|^2 is computed when the key is staged and enters as the C operand of the
+// tile's first MFMA (a 16-byte LDS read per 16 keys, as kb in k_pw_lse); qn = pn |q~_r|^2 is one register per query group, lane-local
+// (a lane serves one query per group), summed over the query's four lanes once before the loop.  Per pair, from the accumulator:
+//   x  = max(acc + qn, 0)            v_add, v_max: the expansion cancels and a slightly negative x must not reach the logarithm
+//   l  = log2(1 + x)                 v_add, v_log_f32 (base 2 already)
+//   sc = b2 - a l                    v_fma, a = (nu + d) / 2, b2_c = bias_c log2 e from a second per-tile LDS array (same 16-byte read)
+// sc is the score in units of log 2, held in the accumulator's registers: from there on the loop IS k_pw_lse's / k_pw_mean's (tile
+// maximum, one v_exp_f32 per pair, one rescale per tile; the mean's shared maximum and second product).  Per pair one quarter-rate
+// and four full-rate instructions more than the Gaussian loop.
+//
+// Edge rules, the family's.  A dead key (bias -inf or NaN) and a key past n_k: zero coordinates, kn = 0, b2 = -inf: x is finite, sc =
+// -inf.  A live key whose scaled centred norm pn |k~|^2 is not finite, or whose bias is +inf, is POISON: zero coordinates, kn = 0, b2 =
+// NaN.  The clamp would drop a NaN that came through x (fmaxf does), so the poison rides in b2: the fma hands it to the exponential
+// and the exponential to every query's sum.  The matrix cores see finite numbers only, but for a bad query's own column.  A query
+// whose pn |q~|^2 is not finite gets NaN from the merge (k_pw_merge_t, k_pw_mean_merge_t), for that query alone.  These merges fold
+// the splits exactly as k_pw_merge / k_pw_mean_merge and add nothing: the query's term is inside the logarithm.
+// Plan, grid, partials, merge order and workspace are the Gaussian calls'.  LDS: one more 64-float array per buffer.
+struct PwTArgs {
+  PwArgs pw;               // pw.p: the precision
+  float pn, a;             // p / nu;  (nu + d) / 2
+};
+
+struct PwMeanTArgs {
+  PwMeanArgs m;
+  float pn, a;
+};
+
+// the t kernels' common parts.  Q: the wave's query fragments (x -2 pn) and qn; K: one key's staging
+template <int DC>
+struct PwT {
+  // qf[g][c], qn[g] for the lane's queries q0 + 16 g + col; scen[c] the staging's centre components
+  static GJX_DEV void queries(const PwArgs& a, float pn, int q0, int col, int quad, int spart, float (&qf)[kPwGroups][DC],
+                              float (&qn)[kPwGroups], float (&scen)[DC]) {
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) qn[g] = 0.0f;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int dq = 4 * c + quad, ds = 4 * c + spart;
+      const float cen = (a.centre && dq < a.d) ? a.centre[dq] : 0.0f;
+      scen[c] = (a.centre && ds < a.d) ? a.centre[ds] : 0.0f;
+#pragma unroll
+      for (int g = 0; g < kPwGroups; ++g) {
+        const int qi = q0 + 16 * g + col;
+        const float x = (dq < a.d && qi < a.n_q) ? a.q[(int64_t)dq * a.stride_q + qi] - cen : 0.0f;
+        qn[g] = fmaf(x, x, qn[g]);
+        qf[g][c] = x * (-2.0f * pn);
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) qn[g] = pn * pw_rows_sum(qn[g]);       // the same bits in the query's four lanes
+  }
+
+  // a staged key: k2 the quad's sum of squares -> zero coordinates?, kn, b2
+  static GJX_DEV bool classify(float b, float pn, float k2, float& kn, float& b2) {
+    kn = pn * k2;
+    const bool dead = !(b > -INFINITY);                   // -inf or NaN
+    const bool zero = dead || !(kn < INFINITY) || !(b < INFINITY);
+    b2 = dead ? -INFINITY : (zero ? NAN : b * kPwLog2e);
+    if (zero) kn = 0.0f;
+    return zero;
+  }
+
+  // the lane's 16 accumulators of a tile and group (scaled distances without qn) -> scores in units of log 2; returns their maximum
+  // joined with mn (fmaxf drops the NaN of a poisoned key: it reaches the sum through the exponential)
+  static GJX_DEV float scores(pw_v4f (&acc)[4], const pw_v4f (&b2)[4], float qn, float a, float mn) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float x = fmaxf(acc[u][r] + qn, 0.0f);
+        acc[u][r] = fmaf(-a, __builtin_amdgcn_logf(1.0f + x), b2[u][r]);
+      }
+      mn = fmaxf(fmaxf(mn, fmaxf(acc[u][0], acc[u][1])), fmaxf(acc[u][2], acc[u][3]));
+    }
+    return mn;
+  }
+};
+
+template <int DC>
+__global__ __launch_bounds__(kPwThreads) void k_pw_lse_t(const PwTArgs ta) {
+  const PwArgs& a = ta.pw;
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sn[2][kPwTile];            // kn
+  __shared__ __attribute__((aligned(16))) float sb[2][kPwTile];            // b2
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;            // the MFMA's view of the lane
+  const int skey = tid >> 2, spart = tid & 3;             // the staging's view: key of the tile, components 4 c + spart
+
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  float qf[kPwGroups][DC], qn[kPwGroups], scen[DC];
+  PwT<DC>::queries(a, ta.pn, q0, col, quad, spart, qf, qn, scen);
+
+  float v[DC], b;
+  auto load = [&](int tile) {
+    const int key = tile * kPwTile + skey;
+    const bool in = key < a.n_k;
+    b = in ? (a.bias ? a.bias[key] : 0.0f) : -INFINITY;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int ds = 4 * c + spart;
+      v[c] = (in && ds < a.d) ? a.k[(int64_t)ds * a.stride_k + key] - scen[c] : 0.0f;
+    }
+  };
+  auto store = [&](int buf) {
+    float k2 = 0.0f, kn, b2;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) k2 = fmaf(v[c], v[c], k2);
+    const bool zero = PwT<DC>::classify(b, ta.pn, quad_sum(k2), kn, b2);
+#pragma unroll
+    for (int c = 0; c < DC; ++c) sk[buf][(4 * c + spart) * kPwLd + skey] = zero ? 0.0f : v[c];
+    if (spart == 0) { sn[buf][skey] = kn; sb[buf][skey] = b2; }
+  };
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  float m[kPwGroups], s[kPwGroups];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) { m[g] = -INFINITY; s[g] = 0.0f; }
+
+  load(t0);
+  store(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) load(t + 1);
+    float af[4][DC];
+    pw_v4f seed[4], b2[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {                         // the tile's four 16-key subtiles
+      seed[u] = *reinterpret_cast<const pw_v4f*>(&sn[buf][16 * u + 4 * quad]);
+      b2[u] = *reinterpret_cast<const pw_v4f*>(&sb[buf][16 * u + 4 * quad]);
+#pragma unroll
+      for (int c = 0; c < DC; ++c) af[u][c] = sk[buf][(4 * c + quad) * kPwLd + 16 * u + col];
+    }
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      pw_v4f acc[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc[u] = seed[u];
+#pragma unroll
+        for (int c = 0; c < DC; ++c) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][c], qf[g][c], acc[u], 0, 0, 0);
+      }
+      const float mn = PwT<DC>::scores(acc, b2, qn[g], ta.a, m[g]);
+      const float ms = mn > -INFINITY ? mn : 0.0f;
+      float e = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) e += __builtin_amdgcn_exp2f(acc[u][r] - ms);
+      s[g] = s[g] * __builtin_amdgcn_exp2f(m[g] - ms) + e;
+      m[g] = mn;
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+  }
+
+  // the four lanes of a query, then its partial
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {
+      const float om = __shfl_xor(m[g], off, 64), os = __shfl_xor(s[g], off, 64);
+      pw_fold(m[g], s[g], om, os);
+    }
+    const int qi = q0 + 16 * g + col;
+    if (quad == 0 && qi < a.n_q) a.part[(int64_t)blockIdx.y * a.n_q + qi] = make_float2(m[g], s[g]);
+  }
+}
+
+// pn |q~_r|^2 of query r: only its finiteness is the merges' business
+GJX_DEV float pw_t_query_norm(const PwArgs& a, float pn, int64_t r) {
+  float q2 = 0.0f;
+  for (int i = 0; i < a.d; ++i) {
+    const float x = a.q[(int64_t)i * a.stride_q + r] - (a.centre ? a.centre[i] : 0.0f);
+    q2 = fmaf(x, x, q2);
+  }
+  return pn * q2;
+}
+
+// k_pw_merge without the query's own term
+__global__ __launch_bounds__(kPwThreads) void k_pw_merge_t(const PwTArgs ta) {
+  const PwArgs& a = ta.pw;
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  if (r >= a.n_q) return;
+  float m = -INFINITY, s = 0.0f;
+  for (int y = 0; y < a.n_splits; ++y) {
+    const float2 p = a.part[(int64_t)y * a.n_q + r];
+    pw_fold(m, s, p.x, p.y);
+  }
+  // no live key: m = -inf, s = 0 -> -inf; a poisoned key: s = NaN -> NaN
+  a.out[r] = pw_t_query_norm(a, ta.pn, r) < INFINITY ? (m + __builtin_amdgcn_logf(s)) * kPwLn2 : NAN;
+}
+
+template <int DC>
+static void pw_t_launch(const PwTArgs& ta, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL(k_pw_lse_t<DC>, grid, dim3(kPwThreads), 0, st, ta);
+}
+
+// k_pw_mean with the t scores: staging of the values, shared maximum, second product and partials as there
+template <int DC, int VB>
+__global__ __launch_bounds__(kPwThreads) void k_pw_mean_t(const PwMeanTArgs mta) {
+  const PwMeanArgs& ma = mta.m;
+  const PwArgs& a = ma.pw;
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sn[2][kPwTile];            // kn
+  __shared__ __attribute__((aligned(16))) float sb[2][kPwTile];            // b2
+  __shared__ __attribute__((aligned(16))) float sv[2][16 * VB * kPwLdV];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;
+  const int skey = tid >> 2, spart = tid & 3;
+
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  float qf[kPwGroups][DC], qn[kPwGroups], scen[DC];
+  PwT<DC>::queries(a, mta.pn, q0, col, quad, spart, qf, qn, scen);
+
+  float kv[DC], vv[4 * VB], b;
+  auto load = [&](int tile) {
+    const int key = tile * kPwTile + skey;
+    const bool in = key < a.n_k;
+    b = in ? (a.bias ? a.bias[key] : 0.0f) : -INFINITY;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int ds = 4 * c + spart;
+      kv[c] = (in && ds < a.d) ? a.k[(int64_t)ds * a.stride_k + key] - scen[c] : 0.0f;
+    }
+#pragma unroll
+    for (int c = 0; c < 4 * VB; ++c) {
+      const int j = 4 * c + spart;
+      vv[c] = (in && j < ma.dv) ? ma.v[(int64_t)j * ma.stride_v + key] : 0.0f;
+    }
+  };
+  auto store = [&](int buf) {
+    float k2 = 0.0f, kn, b2;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) k2 = fmaf(kv[c], kv[c], k2);
+    const bool zero = PwT<DC>::classify(b, mta.pn, quad_sum(k2), kn, b2);
+    const bool dead = !(b > -INFINITY);
+#pragma unroll
+    for (int c = 0; c < DC; ++c) sk[buf][(4 * c + spart) * kPwLd + skey] = zero ? 0.0f : kv[c];
+#pragma unroll
+    for (int c = 0; c < 4 * VB; ++c)
+      sv[buf][(4 * c + spart) * kPwLdV + skey] = dead ? 0.0f : (fabsf(vv[c]) < INFINITY ? vv[c] : NAN);
+    if (spart == 0) { sn[buf][skey] = kn; sb[buf][skey] = b2; }
+  };
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  float m[kPwGroups], s[kPwGroups];
+  pw_v4f o[kPwGroups][VB];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    m[g] = -INFINITY;
+    s[g] = 0.0f;
+#pragma unroll
+    for (int vb = 0; vb < VB; ++vb) o[g][vb] = pw_v4f{0.0f, 0.0f, 0.0f, 0.0f};
+  }
+
+  load(t0);
+  store(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) load(t + 1);
+    float af[4][DC];
+    pw_v4f seed[4], b2[4], vf[4][VB];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      seed[u] = *reinterpret_cast<const pw_v4f*>(&sn[buf][16 * u + 4 * quad]);
+      b2[u] = *reinterpret_cast<const pw_v4f*>(&sb[buf][16 * u + 4 * quad]);
+#pragma unroll
+      for (int c = 0; c < DC; ++c) af[u][c] = sk[buf][(4 * c + quad) * kPwLd + 16 * u + col];
+#pragma unroll
+      for (int vb = 0; vb < VB; ++vb)
+        vf[u][vb] = *reinterpret_cast<const pw_v4f*>(&sv[buf][(16 * vb + col) * kPwLdV + 16 * u + 4 * quad]);
+    }
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      pw_v4f acc[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc[u] = seed[u];
+#pragma unroll
+        for (int c = 0; c < DC; ++c) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][c], qf[g][c], acc[u], 0, 0, 0);
+      }
+      float mn = PwT<DC>::scores(acc, b2, qn[g], mta.a, m[g]);
+      mn = pw_rows_max(mn);                               // the query's four lanes agree before the exponentials
+      const float ms = mn > -INFINITY ? mn : 0.0f;
+      const float f = __builtin_amdgcn_exp2f(m[g] - ms);
+      float e = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          acc[u][r] = __builtin_amdgcn_exp2f(acc[u][r] - ms);
+          e += acc[u][r];
+        }
+      s[g] = s[g] * f + e;
+      m[g] = mn;
+#pragma unroll
+      for (int vb = 0; vb < VB; ++vb) {
+        o[g][vb] *= f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) o[g][vb] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[u][vb][r], acc[u][r], o[g][vb], 0, 0, 0);
+      }
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+  }
+
+  // the four lanes of a query share m; their sums are added in one fixed order.  Then the partials.
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    s[g] += __shfl_xor(s[g], 16, 64);
+    s[g] += __shfl_xor(s[g], 32, 64);
+    const int qi = q0 + 16 * g + col;
+    if (qi >= a.n_q) continue;
+    if (quad == 0) a.part[(int64_t)blockIdx.y * a.n_q + qi] = make_float2(m[g], s[g]);
+#pragma unroll
+    for (int vb = 0; vb < VB; ++vb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = 16 * vb + 4 * quad + r;
+        if (j < ma.dv) ma.opart[((int64_t)blockIdx.y * ma.dv + j) * a.n_q + qi] = o[g][vb][r];
+      }
+  }
+}
+
+// k_pw_mean_merge without the query's own term
+__global__ __launch_bounds__(kPwThreads) void k_pw_mean_merge_t(const PwMeanTArgs mta) {
+  const PwMeanArgs& ma = mta.m;
+  const PwArgs& a = ma.pw;
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  const int j = (int)blockIdx.y;
+  if (r >= a.n_q) return;
+  const bool ok = pw_t_query_norm(a, mta.pn, r) < INFINITY;
+  float m = -INFINITY, s = 0.0f;
+  for (int y = 0; y < a.n_splits; ++y) {
+    const float2 p = a.part[(int64_t)y * a.n_q + r];
+    pw_fold(m, s, p.x, p.y);
+  }
+  const float ms = m > -INFINITY ? m : 0.0f;
+  float o = 0.0f;
+  for (int y = 0; y < a.n_splits; ++y)
+    o = fmaf(ma.opart[((int64_t)y * ma.dv + j) * a.n_q + r], __builtin_amdgcn_exp2f(a.part[(int64_t)y * a.n_q + r].x - ms), o);
+  // no live key: 0 / 0 = NaN; a poisoned key: s = NaN; a live key's non-finite value: o = NaN in its row
+  ma.mean[(int64_t)j * a.n_q + r] = ok ? o / s : NAN;
+  if (j == 0 && a.out) a.out[r] = ok ? (m + __builtin_amdgcn_logf(s)) * kPwLn2 : NAN;
+}
+
+template <int DC>
+static void pw_mean_t_launch(const PwMeanTArgs& mta, dim3 grid, hipStream_t st) {
+  if (mta.m.dv <= 16) hipLaunchKernelGGL((k_pw_mean_t<DC, 1>), grid, dim3(kPwThreads), 0, st, mta);
+  else hipLaunchKernelGGL((k_pw_mean_t<DC, 2>), grid, dim3(kPwThreads), 0, st, mta);
+}
+
+// precision and dof of the t calls -> pn = p / nu and a = (nu + d) / 2 as floats; false: not positive and finite, or a quotient that is not
+static bool pw_t_scalars(float precision, float dof, int32_t d, float* pn, float* a) {
+  if (!(precision > 0.0f) || !(precision < INFINITY) || !(dof > 0.0f) || !(dof < INFINITY)) return false;
+  *pn = (float)((double)precision / (double)dof);
+  *a = (float)(0.5 * ((double)dof + (double)d));
+  return *pn > 0.0f && *pn < INFINITY;
+}
+
 }  // namespace gjx
 
 extern "C" size_t gjx_pairwise_gauss_lse_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
@@ -1848,4 +2223,78 @@ extern "C" int gjx_pairwise_gauss_argmax_diag(const float* q, int64_t stride_q, 
   a.stride_q = stride_q; a.stride_k = stride_k; a.p = 0.0f;             // (0: k_pw_argmax_merge then adds no query term)
   aa.arg = arg; aa.prec = prec; aa.stride_p = stride_p;
   return pw_argmax_launch("gjx_pairwise_gauss_argmax_diag", aa, (2 * d + 3) / 4, true, (hipStream_t)stream);   // chunks of 4 features
+}
+
+extern "C" int gjx_pairwise_t_lse(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k, int32_t d,
+                                  const float* bias, float precision, float dof, const float* centre, float* out, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  using namespace gjx;
+  PwTArgs ta;
+  memset(&ta, 0, sizeof(ta));
+  PwArgs& a = ta.pw;
+  if (!q || !k || !out || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      stride_q < n_q || stride_k < n_k || !pw_t_scalars(precision, dof, d, &ta.pn, &ta.a))
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_t_lse: bad argument");
+  if (d > GJX_PAIRWISE_MAX_DIM) return gjx_fail(GJX_EUNSUPPORTED, "gjx_pairwise_t_lse: more than GJX_PAIRWISE_MAX_DIM components");
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_gauss_lse_workspace_bytes(n_q, n_k, d))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_t_lse: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = out;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k; a.p = precision;
+  const dim3 grid((unsigned)((n_q + kPwBlockQ - 1) / kPwBlockQ), (unsigned)a.n_splits);
+  switch ((d + 3) / 4) {
+    case 1: pw_t_launch<1>(ta, grid, st); break;
+    case 2: pw_t_launch<2>(ta, grid, st); break;
+    case 3: pw_t_launch<3>(ta, grid, st); break;
+    case 4: pw_t_launch<4>(ta, grid, st); break;
+    case 5: pw_t_launch<5>(ta, grid, st); break;
+    case 6: pw_t_launch<6>(ta, grid, st); break;
+    case 7: pw_t_launch<7>(ta, grid, st); break;
+    default: pw_t_launch<8>(ta, grid, st); break;
+  }
+  GJX_CHECK_LAUNCH("gjx_pairwise_t_lse(lse)");
+  hipLaunchKernelGGL(k_pw_merge_t, dim3((unsigned)((n_q + kPwThreads - 1) / kPwThreads)), dim3(kPwThreads), 0, st, ta);
+  GJX_CHECK_LAUNCH("gjx_pairwise_t_lse(merge)");
+  return GJX_OK;
+}
+
+extern "C" int gjx_pairwise_t_mean(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k, int32_t d,
+                                   const float* v, int64_t stride_v, int32_t dv, const float* bias, float precision, float dof,
+                                   const float* centre, float* mean, float* lse, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace gjx;
+  PwMeanTArgs mta;
+  memset(&mta, 0, sizeof(mta));
+  PwMeanArgs& ma = mta.m;
+  PwArgs& a = ma.pw;
+  if (!q || !k || !v || !mean || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      dv <= 0 || stride_q < n_q || stride_k < n_k || stride_v < n_k || !pw_t_scalars(precision, dof, d, &mta.pn, &mta.a))
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_t_mean: bad argument");
+  if (d > GJX_PAIRWISE_MAX_DIM || dv > GJX_PAIRWISE_MAX_DIM)
+    return gjx_fail(GJX_EUNSUPPORTED, "gjx_pairwise_t_mean: more than GJX_PAIRWISE_MAX_DIM components");
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_gauss_mean_workspace_bytes(n_q, n_k, d, dv))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_t_mean: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = lse;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k; a.p = precision;
+  ma.v = v; ma.mean = mean; ma.stride_v = stride_v; ma.dv = dv;
+  ma.opart = (float*)(a.part + (size_t)a.n_splits * (size_t)n_q);
+  const dim3 grid((unsigned)((n_q + kPwBlockQ - 1) / kPwBlockQ), (unsigned)a.n_splits);
+  switch ((d + 3) / 4) {
+    case 1: pw_mean_t_launch<1>(mta, grid, st); break;
+    case 2: pw_mean_t_launch<2>(mta, grid, st); break;
+    case 3: pw_mean_t_launch<3>(mta, grid, st); break;
+    case 4: pw_mean_t_launch<4>(mta, grid, st); break;
+    case 5: pw_mean_t_launch<5>(mta, grid, st); break;
+    case 6: pw_mean_t_launch<6>(mta, grid, st); break;
+    case 7: pw_mean_t_launch<7>(mta, grid, st); break;
+    default: pw_mean_t_launch<8>(mta, grid, st); break;
+  }
+  GJX_CHECK_LAUNCH("gjx_pairwise_t_mean(mean)");
+  hipLaunchKernelGGL(k_pw_mean_merge_t, dim3((unsigned)((n_q + kPwThreads - 1) / kPwThreads), (unsigned)dv), dim3(kPwThreads), 0, st, mta);
+  GJX_CHECK_LAUNCH("gjx_pairwise_t_mean(merge)");
+  return GJX_OK;
 }

@@ -928,6 +928,90 @@ def pairwise_gauss_argmax(q_rows: torch.Tensor, k_rows: torch.Tensor, bias=None,
     return {"arg": out, "max": max_out}
 
 
+def _pairwise_t_args(name: str, q_rows, k_rows, bias, precision, dof, centre):
+    """_pairwise_args plus the degrees of freedom -> its tuple, dof"""
+    args = _pairwise_args(name, q_rows, k_rows, bias, precision, centre)
+    nu = float("nan") if dof is None else float(dof)
+    if not (nu > 0.0 and nu < float("inf")):
+        raise ValueError(f"{name}: dof must be positive and finite, not {dof}")
+    pn = C.c_float(args[8] / nu).value
+    if not (pn > 0.0 and pn < float("inf")):
+        raise ValueError(f"{name}: precision / dof must be a positive finite float32, not {precision} / {dof}")
+    return args, nu
+
+
+def pairwise_t_lse(q_rows: torch.Tensor, k_rows: torch.Tensor, bias=None, precision=1.0, dof=None, centre=None, ws=None,
+                   out=None) -> torch.Tensor:
+    """gjx_pairwise_t_lse: ``pairwise_gauss_lse`` with the pair scored by the multivariate Student-t with ``dof`` = nu degrees of freedom
+    (required, > 0 and finite) and scale matrix I / precision, up to the constant that cancels -> f32[n_q],
+    out[r] = log sum_c exp(bias[c] - 1/2 (nu + d) log(1 + precision |q_r - k_c|^2 / nu)).  Arguments, views, ``centre``, d <= 32, edge
+    rules (dead keys, no live key -> -inf, a NaN query -> NaN for it alone, a live key with a non-finite coordinate or bias +inf ->
+    NaN everywhere), launches, workspace (``gjx_pairwise_gauss_lse_workspace_bytes``) and bit-reproducibility are ``pairwise_gauss_lse``'s.
+    The scaled squared distance comes off the matrix cores, clamped at 0; one hardware logarithm and one exponential per pair.
+    Accuracy: the error is of the order 2^-24 [(d + 4) precision (|q~_r|^2 + max_c |k~_c|^2) (nu + d) / nu + (nu + d)] (tildes: minus
+    ``centre``; pass the keys' mean).  The last term grows with nu: with nu in the hundreds the t is a Gaussian to within that error,
+    and ``pairwise_gauss_lse`` is the call to make."""
+    name = "pairwise_t_lse"
+    (q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre), nu = _pairwise_t_args(name, q_rows, k_rows, bias, precision, dof,
+                                                                                              centre)
+    dev = q_rows.device
+    if out is None:
+        out = torch.empty(n_q, dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.numel() != n_q or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous f32[n_q]")
+    if ws is None:
+        ws = torch.empty(load().gjx_pairwise_gauss_lse_workspace_bytes(n_q, n_k, d), dtype=torch.uint8, device=dev)   # partials only
+    check(load().gjx_pairwise_t_lse(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(bias), p, nu, _ptr(centre), _ptr(out),
+                                    _ptr(ws), ws.numel(), _stream()), "gjx_pairwise_t_lse")
+    return out
+
+
+def pairwise_t_mean(q_rows: torch.Tensor, k_rows: torch.Tensor, v_rows: torch.Tensor, bias=None, precision=1.0, dof=None,
+                    centre=None, ws=None, out=None, lse_out=None) -> dict:
+    """gjx_pairwise_t_mean: ``pairwise_gauss_mean`` over the Student-t scores of ``pairwise_t_lse`` -> dict(mean f32[dv][n_q], lse
+    f32[n_q]):  mean[j][r] = sum_c softmax_c(bias[c] - 1/2 (nu + d) log(1 + precision |q_r - k_c|^2 / nu)) v[j][c] and the log-sum-exp of
+    the same scores.  ``dof`` is required.  Arguments, views, d, dv <= 32, edge rules (a dead key's values are not looked at; no live
+    key -> mean NaN, lse -inf; a live key's non-finite value -> NaN in that component of every mean), launches, workspace
+    (``gjx_pairwise_gauss_mean_workspace_bytes``) and bit-reproducibility are ``pairwise_gauss_mean``'s; the accuracy note of
+    ``pairwise_t_lse`` holds here (the mean's error is the score's times the spread of the values)."""
+    name = "pairwise_t_mean"
+    (q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre), nu = _pairwise_t_args(name, q_rows, k_rows, bias, precision, dof,
+                                                                                              centre)
+    v_rows, stride_v, dv, n_v = _pairwise_rows("v_rows", v_rows)
+    if n_v != n_k:
+        raise ValueError(f"{name}: {n_k} keys, {n_v} values")
+    if dv > A.PAIRWISE_MAX_DIM:
+        raise ValueError(f"{name}: at most {A.PAIRWISE_MAX_DIM} value components, not {dv}")
+    dev = q_rows.device
+    if out is None:
+        out = torch.empty((dv, n_q), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (dv, n_q) or not out.is_contiguous():
+        raise ValueError(f"{name}: out must be a contiguous f32[dv][n_q]")
+    if lse_out is None:
+        lse_out = torch.empty(n_q, dtype=torch.float32, device=dev)
+    elif lse_out.dtype != torch.float32 or lse_out.numel() != n_q or not lse_out.is_contiguous():
+        raise ValueError(f"{name}: lse_out must be a contiguous f32[n_q]")
+    if ws is None:
+        ws = torch.empty(load().gjx_pairwise_gauss_mean_workspace_bytes(n_q, n_k, d, dv), dtype=torch.uint8, device=dev)   # partials only
+    check(load().gjx_pairwise_t_mean(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(v_rows), stride_v, dv, _ptr(bias), p,
+                                     nu, _ptr(centre), _ptr(out), _ptr(lse_out), _ptr(ws), ws.numel(), _stream()), "gjx_pairwise_t_mean")
+    return {"mean": out, "lse": lse_out}
+
+
+def _ffbs_dof(name: str, dof, precision):
+    """``dof`` of ffbs_weights / ffbs_pair_moments, checked before any device work -> None, or the number"""
+    if dof is None:
+        return None
+    if isinstance(precision, (list, tuple)):
+        raise ValueError(f"{name}: dof with per-step precisions is not served: pass one number as precision")
+    nu, p = float(dof), float(precision)
+    if not (nu > 0.0 and nu < float("inf")):
+        raise ValueError(f"{name}: dof must be positive and finite, not {dof}")
+    if not (p > 0.0 and p < float("inf")):
+        raise ValueError(f"{name}: precision must be positive and finite, not {precision}")
+    return nu
+
+
 def _ffbs_precision_tables(name: str, precision, T: int, d: int, K: int):
     """``precision`` of the ffbs_* calls, checked before any device work -> None for a number; for a list or tuple of one f32[d][K] or
     f32[d] per step (the last is not read) a function entry -> its f32[d][K] table (a constant f32[d] is expanded once)"""
@@ -1061,7 +1145,7 @@ def ffbs_map_path(states, loglik_steps, means, precision, log_prior=None) -> dic
     return {"idx": idx, "path": path, "log_joint": log_joint}
 
 
-def ffbs_pair_moments(states, logw_steps, means, precision: float, weights=None) -> dict:
+def ffbs_pair_moments(states, logw_steps, means, precision: float, weights=None, dof=None) -> dict:
     """The lag-one expectations of marginal backward smoothing (FFBSm) for t = 1 .. T-1 -> dict(mean f32[T-1][d] = E[x_t], mean_prev
     f32[T-1][d] = E[x_{t-1}], cross f32[T-1][d][d] = Cov[x_t, x_{t-1}] (centred), ess f32[T-1]) given y_{1:T}; arguments as
     ``ffbs_weights``, whose output ``weights`` f32[T][K] is (computed when None).  The pair (x_t^j, x_{t-1}^i) has weight
@@ -1072,16 +1156,19 @@ def ffbs_pair_moments(states, logw_steps, means, precision: float, weights=None)
     components.  O(T K^2 d); outputs and workspace are allocated once, nothing is read back.
     ``precision`` may be the per-step list of ``ffbs_weights`` (which then gets the same list): the parents are the keys, so step t's
     call is ``pairwise_gauss_mean`` with the matrix precision[t-1] of the keys and the parents' normaliser
-    1/2 sum_j log precision[t-1][j][i], which differs per key and does not cancel in the softmax, added to the bias."""
+    1/2 sum_j log precision[t-1][j][i], which differs per key and does not cancel in the softmax, added to the bias.
+    ``dof`` (a number nu > 0): the transition is x_{t+1} = m(x_t) + eps with eps ~ t_nu(0, I / precision), as in ``ffbs_weights`` (which
+    then gets the same ``dof``); step t's call is ``pairwise_t_mean``.  Not with a per-step precision list."""
     T = len(states)
     if T == 0 or len(logw_steps) != T or len(means) != T:
         raise ValueError("ffbs_pair_moments: states, logw_steps and means must have one entry per step")
+    dof = _ffbs_dof("ffbs_pair_moments", dof, precision)
     d, K = int(states[0].shape[0]), int(states[0].shape[1])
     table = _ffbs_precision_tables("ffbs_pair_moments", precision, T, d, K)
     dev = states[0].device
     _cross_rows("ffbs_pair_moments", "states", states[0])                     # (at most 16 rows: raised here as the moments call does)
     if weights is None:
-        weights = ffbs_weights(states, logw_steps, means, precision)
+        weights = ffbs_weights(states, logw_steps, means, precision, dof=dof)
     if T == 1:
         e = lambda *s: torch.empty((0,) + s, dtype=torch.float32, device=dev)
         return {"mean": e(d), "mean_prev": e(d), "cross": e(d, d), "ess": e()}
@@ -1097,12 +1184,15 @@ def ffbs_pair_moments(states, logw_steps, means, precision: float, weights=None)
         if table is not None:
             P = table(precision[t - 1])
             bias = bias + 0.5 * torch.log(P).sum(0)
+        if dof is not None:
+            pairwise_t_mean(states[t], means[t - 1], states[t - 1], bias, P, dof, centre, ws, out=cond[t - 1], lse_out=lse)
+            continue
         pairwise_gauss_mean(states[t], means[t - 1], states[t - 1], bias, P, centre, ws, out=cond[t - 1], lse_out=lse)
     m = weighted_cross_moments_steps([(states[t], cond[t - 1], None, t) for t in range(1, T)], torch.log(weights))
     return {"mean": m["mean_a"], "mean_prev": m["mean_b"], "cross": m["cross"], "ess": m["stats"][:, 3]}
 
 
-def ffbs_weights(states, logw_steps, means, precision: float) -> torch.Tensor:
+def ffbs_weights(states, logw_steps, means, precision: float, dof=None) -> torch.Tensor:
     """Marginal backward-smoothing weights (FFBSm, Doucet, Godsill & Andrieu 2000) of a recorded filter run whose transition is
     additive-Gaussian, x_{t+1} ~ N(m(x_t), I / precision) -> f32[T][K], every row normalised to sum 1: step t's stored particles under
     row t are the smoothing marginal p(x_t | y_{1:T}).  Unlike ``lineage_weights`` these use all K particles of every step and no
@@ -1120,10 +1210,15 @@ def ffbs_weights(states, logw_steps, means, precision: float) -> torch.Tensor:
     it is the same for all of them (precision[T-1] is not read).  The recursion is the same with the per-particle precisions inside the
     two calls (``pairwise_gauss_lse`` with a precision matrix: the parents are the keys of the first call and the queries of the
     second) and the Gaussian's normaliser ln_t^i = 1/2 sum_j log P_t[j][i], which no longer cancels, added to the bias of the first call
-    and to the result of the second.  d <= 16."""
+    and to the result of the second.  d <= 16.
+    Heavy-tailed transitions, x_{t+1} = m(x_t) + eps with eps ~ t_nu(0, I / precision) (multivariate Student-t; stochastic volatility with
+    t innovations, robust tracking): ``dof`` = nu > 0 with one number as ``precision``.  The recursion is the same with two
+    ``pairwise_t_lse`` calls per step in the place of the Gaussian ones; the t's normaliser is constant and cancels.  d <= 32; ``dof``
+    together with a per-step precision list raises ValueError."""
     T = len(states)
     if T == 0 or len(logw_steps) != T or len(means) != T:
         raise ValueError("ffbs_weights: states, logw_steps and means must have one entry per step")
+    dof = _ffbs_dof("ffbs_weights", dof, precision)
     d, K = int(states[0].shape[0]), int(states[0].shape[1])
     dev = states[0].device
     ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
@@ -1149,6 +1244,11 @@ def ffbs_weights(states, logw_steps, means, precision: float) -> torch.Tensor:
             pairwise_gauss_lse(states[t + 1], means[t], lw_t + ln_t, P, centre, ws, out=D, precision_of="keys")
             pairwise_gauss_lse(means[t], states[t + 1], out[t + 1] - D, P, centre, ws, out=back, precision_of="queries")
             out[t] = log_normalised(lw_t + back + ln_t)
+            continue
+        if dof is not None:
+            pairwise_t_lse(states[t + 1], means[t], lw_t, precision, dof, centre, ws, out=D)
+            pairwise_t_lse(means[t], states[t + 1], out[t + 1] - D, precision, dof, centre, ws, out=back)
+            out[t] = log_normalised(lw_t + back)
             continue
         pairwise_gauss_lse(states[t + 1], means[t], lw_t, precision, centre, ws, out=D)
         pairwise_gauss_lse(means[t], states[t + 1], out[t + 1] - D, precision, centre, ws, out=back)

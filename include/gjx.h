@@ -1344,6 +1344,43 @@ int gjx_pairwise_gauss_argmax_diag(const float* q /* f32[d][stride_q] */, int64_
                                    const float* bias /* f32[n_k] or NULL */, const float* prec /* f32[d][stride_p] */, int64_t stride_p,
                                    int32_t prec_side, const float* centre /* f32[d] or NULL */, int32_t* arg /* i32[n_q] */,
                                    float* max /* f32[n_q] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+/* Pairwise Student-t log-sum-exp and weighted mean: gjx_pairwise_gauss_lse and gjx_pairwise_gauss_mean with the pair scored by the
+ * multivariate t with `dof` = nu degrees of freedom and scale matrix I / precision, up to the constant that cancels:
+ *     s_rc       = bias[c] - 1/2 (nu + d) log(1 + precision |q_r - k_c|^2 / nu)
+ *     out[r]     = lse[r] = log sum_c exp(s_rc)
+ *     mean[j][r] = sum_c exp(s_rc - lse[r]) v[j][c]
+ * They are the n_q x n_k parts of marginal backward smoothing (FFBSm) and of its lag-one pair moments for a recorded filter run whose
+ * transition noise is heavy-tailed, x_{t+1} = m(x_t) + eps, eps ~ t_nu(0, I / precision): stochastic volatility with t innovations,
+ * robust tracking with multivariate-t process noise.  The score is not quadratic in (q, k), so no bias, centre or feature map turns
+ * a Gaussian call into this one.  As nu grows the score tends to the Gaussian one and the accuracy falls (below): for nu in the hundreds
+ * call the Gaussian twins.
+ *   dof        > 0 and finite, like precision; precision / dof must be a positive finite float as well
+ *   everything else   exactly as in gjx_pairwise_gauss_lse / gjx_pairwise_gauss_mean, layouts (SoA rows, column stride 1, any row stride
+ *              >= n, dword loads: odd views are served), d, dv <= GJX_PAIRWISE_MAX_DIM and `centre` included
+ * Edge rules (the family's).  A key whose bias is -inf or NaN is DEAD whatever its coordinates and values hold.  No live key: lse = -inf,
+ * mean = NaN.  A query with a non-finite coordinate (or a scaled centred norm precision |q~|^2 / nu that overflows) gives NaN for that
+ * query alone.  A LIVE key with a non-finite coordinate (or an overflowing scaled centred norm), or with bias +inf, makes every output
+ * NaN.  A live key's non-finite value v[j][c] makes mean[j][.] NaN for every query, in that component alone.
+ * Device work.  Two plain launches on `stream`; plan, grid, key splits, staging through double-buffered LDS, partials and merge order
+ * are the Gaussian calls'.  The matrix cores (v_mfma_f32_16x16x4_f32, f32 inputs) produce the scaled squared distance x = precision |q -
+ * k|^2 / nu from the expansion about `centre` (query fragment scaled by -2 precision / nu, the key's scaled norm as the C operand, the
+ * query's in a register); per pair x is clamped at 0 (the expansion cancels), then 1 + x, one v_log_f32, one fused multiply-add with
+ * bias log2 e from a second per-tile LDS array, and from there the streaming log-sum-exp (and the second product of the mean) unchanged.
+ * A poisoned key travels as a NaN in that LDS array.  The second launch folds the splits and adds no query term.  No atomics, every
+ * sum in an order fixed by the shape: bit-reproducible.  The error of out[r] is of the order 2^-24 [(d + 4) precision (|q~_r|^2 +
+ * max_c |k~_c|^2) (nu + d) / nu + (nu + d)]: pass the keys' (weighted) mean as `centre`.
+ * Refusals as the Gaussian calls', with GJX_EINVAL also for a dof, or a precision / dof, that is not > 0 and finite.  The workspace is
+ * the Gaussian call's of the same shape: gjx_pairwise_gauss_lse_workspace_bytes(n_q, n_k, d) and
+ * gjx_pairwise_gauss_mean_workspace_bytes(n_q, n_k, d, dv) bytes; it needs no initialisation.  Nothing is launched on a refusal. */
+int gjx_pairwise_t_lse(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q, const float* k /* f32[d][stride_k] */,
+                       int64_t stride_k, int64_t n_k, int32_t d, const float* bias /* f32[n_k] or NULL */, float precision, float dof,
+                       const float* centre /* f32[d] or NULL */, float* out /* f32[n_q] */, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int gjx_pairwise_t_mean(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q, const float* k /* f32[d][stride_k] */,
+                        int64_t stride_k, int64_t n_k, int32_t d, const float* v /* f32[dv][stride_v] */, int64_t stride_v, int32_t dv,
+                        const float* bias /* f32[n_k] or NULL */, float precision, float dof, const float* centre /* f32[d] or NULL */,
+                        float* mean /* f32[dv][n_q] */, float* lse /* f32[n_q] or NULL */, void* workspace, size_t workspace_bytes,
+                        void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
