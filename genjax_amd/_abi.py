@@ -235,6 +235,9 @@ PROTOTYPES = {
     "gjx_pairwise_gauss_argmax_diag": (C.c_int, [vp, i64, i64, vp, i64, i64, i32, vp, vp, i64, i32, vp, vp, vp, vp, C.c_size_t, vp]),
     "gjx_pairwise_t_lse": (C.c_int, [vp, i64, i64, vp, i64, i64, i32, vp, f32, f32, vp, vp, vp, C.c_size_t, vp]),
     "gjx_pairwise_t_mean": (C.c_int, [vp, i64, i64, vp, i64, i64, i32, vp, i64, i32, vp, f32, f32, vp, vp, vp, vp, C.c_size_t, vp]),
+    "gjx_pairwise_t_pick": (C.c_int, [vp, i64, i64, vp, i64, i64, i32, vp, f32, f32, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "gjx_pairwise_t_argmax_workspace_bytes": (C.c_size_t, [i64, i64, i32]),
+    "gjx_pairwise_t_argmax": (C.c_int, [vp, i64, i64, vp, i64, i64, i32, vp, f32, f32, vp, vp, vp, vp, C.c_size_t, vp]),
     "gjx_program_filter_source": (i64, [PP, i32, C.c_char_p, i64]),
     "gjx_program_filter_precompile": (C.c_int, [PP, i32]),
     "gjx_resample_indices_tiled": (C.c_int, [vp, i64, f64, i64, vp, vp, vp, vp, vp, C.c_size_t, vp]),

@@ -1856,6 +1856,380 @@ static bool pw_t_scalars(float precision, float dof, int32_t d, float* pn, float
   return *pn > 0.0f && *pn < INFINITY;
 }
 
+// ---- gjx_pairwise_t_pick: one key per query with probability proportional to exp(t score), by inverse CDF in key-index order ----
+//
+// gjx_pairwise_gauss_pick's four launches over the t scores.  1. k_pw_lse_t, unchanged: the partials.  2. k_pw_pick_plan_t, one thread per
+// query: k_pw_pick_plan without the query's own term (the t score keeps it inside the logarithm; the query's verdict is the
+// finiteness of pn |q~|^2, and the lse it writes is k_pw_merge_t's expression on the same fold: the same bits).  3. k_pw_pick_t: the
+// block, staging, group skipping and chunk bookkeeping of k_pw_pick around PwT<DC>'s scores.  With the total L known there is no
+// running maximum: per pair v_add, v_max, v_add, v_log_f32, v_fma (the score), v_sub, v_exp_f32, v_add (the mass).  A dead key is
+// b2 = -inf -> mass 0; a poisoned key never gets here with an owner (its NaN total left own = -1 everywhere: every group is skipped).
+// 4. k_pw_pick_finish_t, one thread per query: the 64 keys of the recorded chunk in the VALU, in the DIRECT form pn |q - k|^2 (no
+// expansion, so no centre and no clamp), the fall-backs of k_pw_pick_finish.  Workspace: gjx_pairwise_gauss_pick's layout and size.
+struct PwPickTArgs {
+  PwPickArgs p;            // p.pw.p: the precision
+  float pn, a;             // p / nu;  (nu + d) / 2
+};
+
+__global__ __launch_bounds__(kPwThreads) void k_pw_pick_plan_t(const PwPickTArgs pta) {
+  const PwPickArgs& pa = pta.p;
+  const PwArgs& a = pa.pw;
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  if (r >= a.n_q) return;
+  const bool okq = pw_t_query_norm(a, pta.pn, r) < INFINITY;
+  float m = -INFINITY, s = 0.0f;
+  for (int y = 0; y < a.n_splits; ++y) {
+    const float2 p = a.part[(int64_t)y * a.n_q + r];
+    pw_fold(m, s, p.x, p.y);
+  }
+  const float L = m + __builtin_amdgcn_logf(s);
+  if (a.out) a.out[r] = okq ? L * kPwLn2 : NAN;
+  const float u = pa.u[r];
+  int own = -1;
+  float resid = 0.0f;
+  if (okq && m > -INFINITY && s == s && u == u) {
+    const float target = u >= 1.0f ? INFINITY : fmaxf(u, 0.0f);
+    float cum = 0.0f;
+    for (int y = 0; y < a.n_splits; ++y) {
+      const float2 p = a.part[(int64_t)y * a.n_q + r];
+      const float mass = p.y * __builtin_amdgcn_exp2f(p.x - L);
+      if (mass > 0.0f) {
+        own = y;
+        resid = target - cum;
+        if (cum + mass >= target) break;
+      }
+      cum += mass;
+    }
+  }
+  pa.L[r] = L;
+  pa.resid[r] = resid;
+  pa.own[r] = own;
+  if (own < 0) pa.pick[r] = -1;
+}
+
+template <int DC>
+__global__ __launch_bounds__(kPwThreads) void k_pw_pick_t(const PwPickTArgs pta) {
+  const PwPickArgs& pa = pta.p;
+  const PwArgs& a = pa.pw;
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sn[2][kPwTile];            // kn
+  __shared__ __attribute__((aligned(16))) float sb[2][kPwTile];            // b2
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;
+  const int skey = tid >> 2, spart = tid & 3;
+
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  float qf[kPwGroups][DC], qn[kPwGroups], scen[DC];
+  PwT<DC>::queries(a, pta.pn, q0, col, quad, spart, qf, qn, scen);
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  // per group: the query's L and residual target where this split owns it, the running cumulative, the record
+  float L[kPwGroups], want[kPwGroups], cum[kPwGroups], rb[kPwGroups];
+  int rt[kPwGroups];
+  bool mine[kPwGroups], act[kPwGroups], done[kPwGroups];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    const int qi = q0 + 16 * g + col;
+    mine[g] = qi < a.n_q && pa.own[qi] == (int)blockIdx.y;
+    act[g] = __any(mine[g]) != 0;                         // wave-uniform: somebody in the group is owned here
+    L[g] = mine[g] ? pa.L[qi] : INFINITY;                 // (+inf: every exponential of a query owned elsewhere is 0)
+    want[g] = mine[g] ? pa.resid[qi] : INFINITY;
+    cum[g] = rb[g] = 0.0f;
+    rt[g] = t0;
+    done[g] = false;
+  }
+
+  float v[DC], b;
+  auto load = [&](int tile) {
+    const int key = tile * kPwTile + skey;
+    const bool in = key < a.n_k;
+    b = in ? (a.bias ? a.bias[key] : 0.0f) : -INFINITY;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int ds = 4 * c + spart;
+      v[c] = (in && ds < a.d) ? a.k[(int64_t)ds * a.stride_k + key] - scen[c] : 0.0f;
+    }
+  };
+  auto store = [&](int buf) {
+    float k2 = 0.0f, kn, b2;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) k2 = fmaf(v[c], v[c], k2);
+    const bool zero = PwT<DC>::classify(b, pta.pn, quad_sum(k2), kn, b2);
+#pragma unroll
+    for (int c = 0; c < DC; ++c) sk[buf][(4 * c + spart) * kPwLd + skey] = zero ? 0.0f : v[c];
+    if (spart == 0) { sn[buf][skey] = kn; sb[buf][skey] = b2; }
+  };
+
+  load(t0);
+  store(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) load(t + 1);
+    float af[4][DC];
+    pw_v4f seed[4], b2[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      seed[u] = *reinterpret_cast<const pw_v4f*>(&sn[buf][16 * u + 4 * quad]);
+      b2[u] = *reinterpret_cast<const pw_v4f*>(&sb[buf][16 * u + 4 * quad]);
+#pragma unroll
+      for (int c = 0; c < DC; ++c) af[u][c] = sk[buf][(4 * c + quad) * kPwLd + 16 * u + col];
+    }
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      if (!act[g]) continue;
+      pw_v4f acc[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc[u] = seed[u];
+#pragma unroll
+        for (int c = 0; c < DC; ++c) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][c], qf[g][c], acc[u], 0, 0, 0);
+      }
+      PwT<DC>::scores(acc, b2, qn[g], pta.a, -INFINITY);   // (the maximum is not used: L is known)
+      float e = 0.0f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) e += __builtin_amdgcn_exp2f(acc[u][r] - L[g]);
+      e = pw_rows_sum(e);                                 // the chunk's mass, the same bits in the query's four lanes
+      if (!done[g] && e > 0.0f) {
+        rt[g] = t;
+        rb[g] = cum[g];
+        done[g] = cum[g] + e >= want[g];
+      }
+      cum[g] += e;
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+    const int qi = q0 + 16 * g + col;
+    if (quad == 0 && mine[g]) {
+      pa.rchunk[qi] = rt[g];
+      pa.rbefore[qi] = rb[g];
+    }
+  }
+}
+
+// one thread per query: the recorded chunk key by key, x = pn |q - k|^2 as written
+__global__ __launch_bounds__(kPwThreads) void k_pw_pick_finish_t(const PwPickTArgs pta) {
+  const PwPickArgs& pa = pta.p;
+  const PwArgs& a = pa.pw;
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  if (r >= a.n_q || pa.own[r] < 0) return;                // (no pick: k_pw_pick_plan_t wrote the -1)
+  float qv[GJX_PAIRWISE_MAX_DIM];
+#pragma unroll
+  for (int i = 0; i < GJX_PAIRWISE_MAX_DIM; ++i) qv[i] = i < a.d ? a.q[(int64_t)i * a.stride_q + r] : 0.0f;
+  const float L = pa.L[r], want = pa.resid[r] - pa.rbefore[r];
+  const int t = min(max(pa.rchunk[r], 0), a.n_tiles - 1);
+  const int c0 = t * kPwTile, c1 = min(c0 + kPwTile, a.n_k);
+  float cum = 0.0f, top = -INFINITY;
+  int pick = -1, last = -1, topc = -1;
+  for (int c = c0; c < c1 && pick < 0; ++c) {
+    const float b = a.bias ? a.bias[c] : 0.0f;
+    if (!(b > -INFINITY)) continue;                       // dead
+    float r2 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < GJX_PAIRWISE_MAX_DIM; ++i) {
+      if (i >= a.d) break;
+      const float x = qv[i] - a.k[(int64_t)i * a.stride_k + c];
+      r2 = fmaf(x, x, r2);
+    }
+    const float sc = fmaf(-pta.a, __builtin_amdgcn_logf(1.0f + pta.pn * r2), b * kPwLog2e);
+    if (sc > top) { top = sc; topc = c; }
+    const float e = __builtin_amdgcn_exp2f(sc - L);
+    if (e > 0.0f) {
+      last = c;
+      cum += e;
+      if (cum >= want) pick = c;
+    }
+  }
+  pa.pick[r] = pick >= 0 ? pick : (last >= 0 ? last : topc);
+}
+
+// ---- gjx_pairwise_t_argmax:  max[r] = max_c score(r, c),  arg[r] = the smallest c that attains it, under the t score ----
+//
+// The product form: no transcendental per pair.  With a = (nu + d) / 2, x = pn |q - k|^2 and B the largest live bias,
+//   argmax_c [bias_c - a ln(1 + x_c)]  =  argmin_c (1 + x_c) w_c,     w_c = exp((B - bias_c) / a) >= 1,
+// and max = B - a ln(min).  w_c is computed ONCE per staged key (one v_exp_f32 by the staging thread) and lies in LDS where the lse keeps
+// b2; the matrix cores make x as in k_pw_lse_t (query fragment x -2 pn, kn the C operand, qn + 1 in a register).  Per pair:
+//   v = max(acc + (qn + 1), 1) w         v_add, v_max, v_mul
+// then k_pw_argmax's lane-local tracking with min for max: 8 v_min3_f32 per tile and group, and only where the minimum falls
+// STRICTLY the compare/select chain that finds the first accumulator equal to it.  The four lanes of a query are joined by (smaller
+// value, then smaller index), a split leaves {min, index} in part[split][query], and k_pw_argmax_merge_t, one thread per query, folds
+// the splits in index order with strict <, and takes the one logarithm: max = B - a ln 2 log2(min).
+// B is ONE number per call (k_pw_bias_max, a one-block launch in front, writes it behind the partials): w, and so v, of a key are then
+// the same bits in whatever tile, split or block the key is staged, and bit-equal copies of a key tie exactly: the smallest index wins
+// at every level.  A dead key, a key past n_k and a poisoned key are staged as zero coordinates, kn = 0, w = +inf: v = +inf never
+// falls below anything.  A w that overflows to +inf belongs to a key that cannot win (1 + x is a finite float).  The poison is
+// k_pw_argmax's sticky flag (PwT::classify's NaN b2), joined by __syncthreads_or, written as NaN into the block's partials.  A bad
+// query's NaN accumulators are clamped to 1 by the v_max: what it tracks is discarded by the merge's own verdict on pn |q~|^2.
+// Accuracy: w carries a relative error of about 2^-24 (1 + |B - bias_c| / a), i.e. |B - bias_c| 2^-24 in the score; the winner has
+// |B - bias_c| <= a ln(1 + x_B) <= a x_B with x_B the scaled distance to the key that carries B, which the lse's bound already allows.
+struct PwArgmaxTArgs {
+  PwArgmaxArgs aa;         // aa.pw.out: the maxima, or NULL; aa.pw.part[split][query] = {min of (1 + x) w, the index's bits}
+  float* top;              // [1] B, the largest bias (0 without a bias, -inf where nobody lives), written by k_pw_bias_max
+  float pn, a;             // p / nu;  (nu + d) / 2
+};
+
+// one block: B.  fmaxf drops the NaN of a dead key; -inf is the neutral element; +inf stays (the staging calls that key poison)
+__global__ __launch_bounds__(kPwThreads) void k_pw_bias_max(const PwArgmaxTArgs ata) {
+  __shared__ float sm[kPwThreads / 64];
+  const PwArgs& a = ata.aa.pw;
+  float m = a.bias ? -INFINITY : 0.0f;
+  if (a.bias)
+    for (int c = threadIdx.x; c < a.n_k; c += kPwThreads) m = fmaxf(m, a.bias[c]);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) *ata.top = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+}
+
+template <int DC>
+__global__ __launch_bounds__(kPwThreads) void k_pw_argmax_t(const PwArgmaxTArgs ata) {
+  const PwArgs& a = ata.aa.pw;
+  __shared__ float sk[2][4 * DC * kPwLd];
+  __shared__ __attribute__((aligned(16))) float sn[2][kPwTile];            // kn
+  __shared__ __attribute__((aligned(16))) float sw[2][kPwTile];            // w
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int col = lane & 15, quad = lane >> 4;            // the MFMA's view of the lane
+  const int skey = tid >> 2, spart = tid & 3;             // the staging's view: key of the tile, components 4 c + spart
+
+  const int q0 = (int)blockIdx.x * kPwBlockQ + wave * 16 * kPwGroups;
+  float qf[kPwGroups][DC], qn[kPwGroups], scen[DC];
+  PwT<DC>::queries(a, ata.pn, q0, col, quad, spart, qf, qn, scen);
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) qn[g] += 1.0f;      // 1 + x = acc + (qn + 1)
+  const float B = *ata.top, ia = kPwLog2e / ata.a;
+
+  float v[DC], b;
+  bool bad = false;                                       // this thread staged a poisoned key
+  auto load = [&](int tile) {
+    const int key = tile * kPwTile + skey;
+    const bool in = key < a.n_k;
+    b = in ? (a.bias ? a.bias[key] : 0.0f) : -INFINITY;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) {
+      const int ds = 4 * c + spart;
+      v[c] = (in && ds < a.d) ? a.k[(int64_t)ds * a.stride_k + key] - scen[c] : 0.0f;
+    }
+  };
+  auto store = [&](int buf) {
+    float k2 = 0.0f, kn, b2;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) k2 = fmaf(v[c], v[c], k2);
+    const bool zero = PwT<DC>::classify(b, ata.pn, quad_sum(k2), kn, b2);
+    bad |= b2 != b2;
+#pragma unroll
+    for (int c = 0; c < DC; ++c) sk[buf][(4 * c + spart) * kPwLd + skey] = zero ? 0.0f : v[c];
+    if (spart == 0) { sn[buf][skey] = kn; sw[buf][skey] = zero ? INFINITY : __builtin_amdgcn_exp2f((B - b) * ia); }
+  };
+
+  const int t0 = (int)blockIdx.y * a.tiles_per_split;
+  const int t1 = min(t0 + a.tiles_per_split, a.n_tiles);
+  float m[kPwGroups];
+  int idx[kPwGroups];
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) { m[g] = INFINITY; idx[g] = -1; }
+
+  load(t0);
+  store(0);
+  __syncthreads();
+  for (int t = t0; t < t1; ++t) {
+    const int buf = (t - t0) & 1;
+    const bool more = t + 1 < t1;                         // block-uniform
+    if (more) load(t + 1);
+    float af[4][DC];
+    pw_v4f seed[4], w[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {                         // the tile's four 16-key subtiles
+      seed[u] = *reinterpret_cast<const pw_v4f*>(&sn[buf][16 * u + 4 * quad]);
+      w[u] = *reinterpret_cast<const pw_v4f*>(&sw[buf][16 * u + 4 * quad]);
+#pragma unroll
+      for (int c = 0; c < DC; ++c) af[u][c] = sk[buf][(4 * c + quad) * kPwLd + 16 * u + col];
+    }
+#pragma unroll
+    for (int g = 0; g < kPwGroups; ++g) {
+      pw_v4f acc[4];
+      float mn = m[g];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc[u] = seed[u];
+#pragma unroll
+        for (int c = 0; c < DC; ++c) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[u][c], qf[g][c], acc[u], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[u][i] = fmaxf(acc[u][i] + qn[g], 1.0f) * w[u][i];      // (fmaxf drops a bad query's NaN)
+        mn = fminf(fminf(fminf(fminf(mn, acc[u][0]), acc[u][1]), acc[u][2]), acc[u][3]);
+      }
+      if (mn < m[g]) {                                    // some accumulator IS mn: the first of them, in key order
+        int j = 0;
+#pragma unroll
+        for (int u = 3; u >= 0; --u)
+#pragma unroll
+          for (int i = 3; i >= 0; --i) j = acc[u][i] == mn ? 16 * u + i : j;
+        m[g] = mn;
+        idx[g] = t * kPwTile + 4 * quad + j;
+      }
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+  }
+
+  // the four lanes of a query, the block's poison, the partial
+  const bool poisoned = __syncthreads_or(bad) != 0;
+#pragma unroll
+  for (int g = 0; g < kPwGroups; ++g) {
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {
+      const float om = __shfl_xor(m[g], off, 64);
+      const int oi = __shfl_xor(idx[g], off, 64);
+      const bool take = om < m[g] || (om == m[g] && oi < idx[g]);       // (no key yet: +inf and -1 on both sides)
+      m[g] = take ? om : m[g];
+      idx[g] = take ? oi : idx[g];
+    }
+    const int qi = q0 + 16 * g + col;
+    if (quad == 0 && qi < a.n_q)
+      a.part[(int64_t)blockIdx.y * a.n_q + qi] = make_float2(poisoned ? NAN : m[g], __int_as_float(idx[g]));
+  }
+}
+
+// one thread per query: the splits in index order (strict <: the earlier split keeps a tie), the query's verdict, the one logarithm
+__global__ __launch_bounds__(kPwThreads) void k_pw_argmax_merge_t(const PwArgmaxTArgs ata) {
+  const PwArgs& a = ata.aa.pw;
+  const int64_t r = (int64_t)blockIdx.x * kPwThreads + threadIdx.x;
+  if (r >= a.n_q) return;
+  float m = INFINITY;
+  int idx = -1;
+  bool bad = false;
+  for (int y = 0; y < a.n_splits; ++y) {
+    const float2 p = a.part[(int64_t)y * a.n_q + r];
+    bad |= p.x != p.x;
+    if (p.x < m) { m = p.x; idx = __float_as_int(p.y); }
+  }
+  // no live key, or every 1 + x overflowed: m = +inf, idx = -1, max = -inf
+  const bool ok = pw_t_query_norm(a, ata.pn, r) < INFINITY && !bad;
+  ata.aa.arg[r] = ok ? idx : -1;
+  if (a.out) a.out[r] = ok ? fmaf(-ata.a * kPwLn2, __builtin_amdgcn_logf(m), *ata.top) : NAN;
+}
+
+// the instance for DC = ceil(d / 4) chunks of a kernel template over one argument struct
+#define GJX_PW_T_DISPATCH(KERNEL, d, grid, st, args)                                                    \
+  switch (((d) + 3) / 4) {                                                                              \
+    case 1: hipLaunchKernelGGL(KERNEL<1>, grid, dim3(kPwThreads), 0, st, args); break;                  \
+    case 2: hipLaunchKernelGGL(KERNEL<2>, grid, dim3(kPwThreads), 0, st, args); break;                  \
+    case 3: hipLaunchKernelGGL(KERNEL<3>, grid, dim3(kPwThreads), 0, st, args); break;                  \
+    case 4: hipLaunchKernelGGL(KERNEL<4>, grid, dim3(kPwThreads), 0, st, args); break;                  \
+    case 5: hipLaunchKernelGGL(KERNEL<5>, grid, dim3(kPwThreads), 0, st, args); break;                  \
+    case 6: hipLaunchKernelGGL(KERNEL<6>, grid, dim3(kPwThreads), 0, st, args); break;                  \
+    case 7: hipLaunchKernelGGL(KERNEL<7>, grid, dim3(kPwThreads), 0, st, args); break;                  \
+    default: hipLaunchKernelGGL(KERNEL<8>, grid, dim3(kPwThreads), 0, st, args); break;                 \
+  }
+
 }  // namespace gjx
 
 extern "C" size_t gjx_pairwise_gauss_lse_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
@@ -2296,5 +2670,80 @@ extern "C" int gjx_pairwise_t_mean(const float* q, int64_t stride_q, int64_t n_q
   GJX_CHECK_LAUNCH("gjx_pairwise_t_mean(mean)");
   hipLaunchKernelGGL(k_pw_mean_merge_t, dim3((unsigned)((n_q + kPwThreads - 1) / kPwThreads), (unsigned)dv), dim3(kPwThreads), 0, st, mta);
   GJX_CHECK_LAUNCH("gjx_pairwise_t_mean(merge)");
+  return GJX_OK;
+}
+
+extern "C" int gjx_pairwise_t_pick(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k, int32_t d,
+                                   const float* bias, float precision, float dof, const float* centre, const float* u, int32_t* pick,
+                                   float* lse, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace gjx;
+  PwPickTArgs pta;
+  memset(&pta, 0, sizeof(pta));
+  PwPickArgs& pa = pta.p;
+  PwArgs& a = pa.pw;
+  if (!q || !k || !u || !pick || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      stride_q < n_q || stride_k < n_k || !pw_t_scalars(precision, dof, d, &pta.pn, &pta.a))
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_t_pick: bad argument");
+  if (d > GJX_PAIRWISE_MAX_DIM) return gjx_fail(GJX_EUNSUPPORTED, "gjx_pairwise_t_pick: more than GJX_PAIRWISE_MAX_DIM components");
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_gauss_pick_workspace_bytes(n_q, n_k, d))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_t_pick: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = lse;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k; a.p = precision;
+  pa.u = u; pa.pick = pick;
+  pa.L = (float*)(a.part + (size_t)a.n_splits * (size_t)n_q);
+  pa.resid = pa.L + n_q;
+  pa.rbefore = pa.resid + n_q;
+  pa.own = (int32_t*)(pa.rbefore + n_q);
+  pa.rchunk = pa.own + n_q;
+  PwTArgs ta;                                                               // the partials: gjx_pairwise_t_lse's first launch
+  ta.pw = a; ta.pn = pta.pn; ta.a = pta.a;
+  const dim3 grid((unsigned)((n_q + kPwBlockQ - 1) / kPwBlockQ), (unsigned)a.n_splits);
+  const dim3 per_query((unsigned)((n_q + kPwThreads - 1) / kPwThreads));
+  GJX_PW_T_DISPATCH(k_pw_lse_t, d, grid, st, ta)
+  GJX_CHECK_LAUNCH("gjx_pairwise_t_pick(lse)");
+  hipLaunchKernelGGL(k_pw_pick_plan_t, per_query, dim3(kPwThreads), 0, st, pta);
+  GJX_CHECK_LAUNCH("gjx_pairwise_t_pick(plan)");
+  GJX_PW_T_DISPATCH(k_pw_pick_t, d, grid, st, pta)
+  GJX_CHECK_LAUNCH("gjx_pairwise_t_pick(pick)");
+  hipLaunchKernelGGL(k_pw_pick_finish_t, per_query, dim3(kPwThreads), 0, st, pta);
+  GJX_CHECK_LAUNCH("gjx_pairwise_t_pick(finish)");
+  return GJX_OK;
+}
+
+extern "C" size_t gjx_pairwise_t_argmax_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d) {
+  const size_t part = gjx_pairwise_gauss_lse_workspace_bytes(n_q, n_k, d);  // {min, index} per (query, split)
+  return part ? part + 8 : 0;                                               // and B behind them
+}
+
+extern "C" int gjx_pairwise_t_argmax(const float* q, int64_t stride_q, int64_t n_q, const float* k, int64_t stride_k, int64_t n_k, int32_t d,
+                                     const float* bias, float precision, float dof, const float* centre, int32_t* arg, float* max,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace gjx;
+  PwArgmaxTArgs ata;
+  memset(&ata, 0, sizeof(ata));
+  PwArgs& a = ata.aa.pw;
+  if (!q || !k || !arg || !workspace || n_q <= 0 || n_k <= 0 || n_q > INT32_MAX || n_k > INT32_MAX - kPwTile || d <= 0 ||
+      stride_q < n_q || stride_k < n_k || !pw_t_scalars(precision, dof, d, &ata.pn, &ata.a))
+    return gjx_fail(GJX_EINVAL, "gjx_pairwise_t_argmax: bad argument");
+  if (d > GJX_PAIRWISE_MAX_DIM) return gjx_fail(GJX_EUNSUPPORTED, "gjx_pairwise_t_argmax: more than GJX_PAIRWISE_MAX_DIM components");
+  pw_plan(n_q, n_k, d, &a);
+  if (workspace_bytes < gjx_pairwise_t_argmax_workspace_bytes(n_q, n_k, d))
+    return gjx_fail(GJX_EWORKSPACE, "gjx_pairwise_t_argmax: workspace too small");
+  const hipStream_t st = (hipStream_t)stream;
+  a.q = q; a.k = k; a.bias = bias; a.centre = centre; a.out = max;
+  a.part = (float2*)(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+  a.stride_q = stride_q; a.stride_k = stride_k; a.p = precision;
+  ata.aa.arg = arg;
+  ata.top = (float*)(a.part + (size_t)a.n_splits * (size_t)n_q);
+  const dim3 grid((unsigned)((n_q + kPwBlockQ - 1) / kPwBlockQ), (unsigned)a.n_splits);
+  hipLaunchKernelGGL(k_pw_bias_max, dim3(1), dim3(kPwThreads), 0, st, ata);
+  GJX_CHECK_LAUNCH("gjx_pairwise_t_argmax(bias)");
+  GJX_PW_T_DISPATCH(k_pw_argmax_t, d, grid, st, ata)
+  GJX_CHECK_LAUNCH("gjx_pairwise_t_argmax(argmax)");
+  hipLaunchKernelGGL(k_pw_argmax_merge_t, dim3((unsigned)((n_q + kPwThreads - 1) / kPwThreads)), dim3(kPwThreads), 0, st, ata);
+  GJX_CHECK_LAUNCH("gjx_pairwise_t_argmax(merge)");
   return GJX_OK;
 }

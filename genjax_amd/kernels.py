@@ -998,8 +998,67 @@ def pairwise_t_mean(q_rows: torch.Tensor, k_rows: torch.Tensor, v_rows: torch.Te
     return {"mean": out, "lse": lse_out}
 
 
+def _pairwise_t_out(name: str, what: str, out, n_q: int, dtype, dev):
+    """an optional contiguous output [n_q] of the t pick / argmax -> it, allocated when None"""
+    if out is None:
+        return torch.empty(n_q, dtype=dtype, device=dev)
+    if out.dtype != dtype or out.numel() != n_q or not out.is_contiguous():
+        raise ValueError(f"{name}: {what} must be a contiguous {'i32' if dtype == torch.int32 else 'f32'}[n_q]")
+    return out
+
+
+def pairwise_t_pick(q_rows: torch.Tensor, k_rows: torch.Tensor, u: torch.Tensor, bias=None, precision=1.0, dof=None, centre=None,
+                    ws=None, out=None, lse_out=None) -> dict:
+    """gjx_pairwise_t_pick: ``pairwise_gauss_pick`` over the Student-t scores of ``pairwise_t_lse`` -> dict(pick i32[n_q], lse f32[n_q]):
+    pick[r] is the smallest key index c at which the cumulative of exp(bias[c] - 1/2 (nu + d) log(1 + precision |q_r - k_c|^2 / nu)) over
+    the keys in index order reaches u[r] times its total; lse has the bits of ``pairwise_t_lse``.  ``dof`` = nu is required; ``precision``
+    is one number (a tensor is refused: per-particle precisions under the t score are not served).  Arguments, views, d <= 32, edge
+    rules (dead keys never picked; u <= 0 the first and u >= 1 the last key with positive mass; -1 where there is nothing to pick),
+    workspace (``gjx_pairwise_gauss_pick_workspace_bytes``), four launches and bit-reproducibility are ``pairwise_gauss_pick``'s; the
+    accuracy note of ``pairwise_t_lse`` holds for the masses."""
+    name = "pairwise_t_pick"
+    if isinstance(precision, torch.Tensor) and precision.dim() > 0:
+        raise ValueError(f"{name}: precision must be one number under the t score, not a tensor")
+    (q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre), nu = _pairwise_t_args(name, q_rows, k_rows, bias, precision, dof,
+                                                                                              centre)
+    if u.dtype != torch.float32 or u.dim() != 1 or u.numel() != n_q or not u.is_contiguous():
+        raise ValueError(f"{name}: u must be a contiguous f32[n_q]")
+    dev = q_rows.device
+    out = _pairwise_t_out(name, "out", out, n_q, torch.int32, dev)
+    lse_out = _pairwise_t_out(name, "lse_out", lse_out, n_q, torch.float32, dev)
+    if ws is None:
+        ws = torch.empty(load().gjx_pairwise_gauss_pick_workspace_bytes(n_q, n_k, d), dtype=torch.uint8, device=dev)   # partials only
+    check(load().gjx_pairwise_t_pick(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(bias), p, nu, _ptr(centre), _ptr(u),
+                                     _ptr(out), _ptr(lse_out), _ptr(ws), ws.numel(), _stream()), "gjx_pairwise_t_pick")
+    return {"pick": out, "lse": lse_out}
+
+
+def pairwise_t_argmax(q_rows: torch.Tensor, k_rows: torch.Tensor, bias=None, precision=1.0, dof=None, centre=None, ws=None, out=None,
+                      max_out=None) -> dict:
+    """gjx_pairwise_t_argmax: ``pairwise_gauss_argmax`` over the Student-t scores of ``pairwise_t_lse`` -> dict(arg i32[n_q], max
+    f32[n_q]): max[r] = max_c (bias[c] - 1/2 (nu + d) log(1 + precision |q_r - k_c|^2 / nu)) and arg[r] the smallest key index that
+    attains it in the kernel's arithmetic.  ``dof`` = nu is required; ``precision`` is one number (a tensor is refused).  Arguments,
+    views, d <= 32 and edge rules (dead keys never returned; no live key -> -1 / -inf; a non-finite query -> -1 / NaN for it alone; a
+    poisoned live key or a bias of +inf -> -1 / NaN everywhere; exact ties -> the smallest index) are ``pairwise_gauss_argmax``'s.  No
+    transcendental per pair: the kernel minimises (1 + x) exp((B - bias[c]) / a), a = (nu + d) / 2, B the largest bias, and takes one
+    logarithm per query; three launches, bit-reproducible.  Workspace: ``gjx_pairwise_t_argmax_workspace_bytes``."""
+    name = "pairwise_t_argmax"
+    if isinstance(precision, torch.Tensor) and precision.dim() > 0:
+        raise ValueError(f"{name}: precision must be one number under the t score, not a tensor")
+    (q_rows, stride_q, n_q, k_rows, stride_k, n_k, d, bias, p, centre), nu = _pairwise_t_args(name, q_rows, k_rows, bias, precision, dof,
+                                                                                              centre)
+    dev = q_rows.device
+    out = _pairwise_t_out(name, "out", out, n_q, torch.int32, dev)
+    max_out = _pairwise_t_out(name, "max_out", max_out, n_q, torch.float32, dev)
+    if ws is None:
+        ws = torch.empty(load().gjx_pairwise_t_argmax_workspace_bytes(n_q, n_k, d), dtype=torch.uint8, device=dev)   # partials and B
+    check(load().gjx_pairwise_t_argmax(_ptr(q_rows), stride_q, n_q, _ptr(k_rows), stride_k, n_k, d, _ptr(bias), p, nu, _ptr(centre),
+                                       _ptr(out), _ptr(max_out), _ptr(ws), ws.numel(), _stream()), "gjx_pairwise_t_argmax")
+    return {"arg": out, "max": max_out}
+
+
 def _ffbs_dof(name: str, dof, precision):
-    """``dof`` of ffbs_weights / ffbs_pair_moments, checked before any device work -> None, or the number"""
+    """``dof`` of the ffbs_* calls, checked before any device work -> None, or the number"""
     if dof is None:
         return None
     if isinstance(precision, (list, tuple)):
@@ -1036,7 +1095,7 @@ def _ffbs_precision_tables(name: str, precision, T: int, d: int, K: int):
     return table
 
 
-def ffbs_sample_paths(states, logw_steps, means, precision, key, n_paths: int) -> dict:
+def ffbs_sample_paths(states, logw_steps, means, precision, key, n_paths: int, dof=None) -> dict:
     """Backward simulation (FFBSi, Godsill, Doucet & West 2004): ``n_paths`` joint draws from p(x_{0:T-1} | y_{1:T}) over the stored
     particles -> dict(idx i32[T][n_paths], paths f32[T][d][n_paths]), paths[t] = states[t][:, idx[t]]; arguments as ``ffbs_weights``.
     idx[T-1] is a multinomial draw from the last step's filtering weights (``weight_cumsum`` + ``resample_multinomial`` under
@@ -1048,12 +1107,16 @@ def ffbs_sample_paths(states, logw_steps, means, precision, key, n_paths: int) -
     once, nothing is read back.
     ``precision`` may be the per-step list of ``ffbs_weights`` (d <= 16): the parents are the keys, so step t's call is
     ``pairwise_gauss_pick`` with the matrix precision[t] of the keys and the parents' normaliser 1/2 sum_j log precision[t][j][i], which
-    differs per key and does not cancel in the draw, added to the bias."""
+    differs per key and does not cancel in the draw, added to the bias.
+    ``dof`` (a number nu > 0): the transition is x_{t+1} = m(x_t) + eps with eps ~ t_nu(0, I / precision), as in ``ffbs_weights``; step
+    t's call is ``pairwise_t_pick``.  The t's normaliser is the same for every parent and cancels in the draw.  d <= 32; not with a
+    per-step precision list."""
     T, n = len(states), int(n_paths)
     if T == 0 or len(logw_steps) != T or len(means) != T:
         raise ValueError("ffbs_sample_paths: states, logw_steps and means must have one entry per step")
     if n <= 0:
         raise ValueError(f"ffbs_sample_paths: n_paths must be positive, not {n_paths}")
+    dof = _ffbs_dof("ffbs_sample_paths", dof, precision)
     from .core import fold_in
     d, K = int(states[0].shape[0]), int(states[0].shape[1])
     table = _ffbs_precision_tables("ffbs_sample_paths", precision, T, d, K)
@@ -1077,12 +1140,15 @@ def ffbs_sample_paths(states, logw_steps, means, precision, key, n_paths: int) -
         if table is not None:
             P = table(precision[t])
             bias = bias + 0.5 * torch.log(P).sum(0)
-        pairwise_gauss_pick(paths[t + 1], means[t], u, bias, P, centre, ws, out=idx[t], lse_out=lse)
+        if dof is not None:                                                       # (same workspace size)
+            pairwise_t_pick(paths[t + 1], means[t], u, bias, P, dof, centre, ws, out=idx[t], lse_out=lse)
+        else:
+            pairwise_gauss_pick(paths[t + 1], means[t], u, bias, P, centre, ws, out=idx[t], lse_out=lse)
         gather_rows(states[t], idx[t], paths[t])
     return {"idx": idx, "paths": paths}
 
 
-def ffbs_map_path(states, loglik_steps, means, precision, log_prior=None) -> dict:
+def ffbs_map_path(states, loglik_steps, means, precision, log_prior=None, dof=None) -> dict:
     """The single most probable trajectory through the stored particles (particle Viterbi; Godsill, Doucet & West 2001) of a recorded
     filter run with an additive-Gaussian transition -> dict(idx i32[T], path f32[T][d], log_joint f64 scalar), path[t] =
     states[t][:, idx[t]]; ``states``, ``means`` and ``precision`` as in ``ffbs_weights``.
@@ -1099,10 +1165,14 @@ def ffbs_map_path(states, loglik_steps, means, precision, log_prior=None) -> dic
     nothing is read back.
     ``precision`` may be the per-step list of ``ffbs_weights`` (d <= 16): the parents are the keys, so step t's call takes the matrix
     precision[t-1] of the keys, and the parents' normaliser 1/2 sum_j log precision[t-1][j][i] is added to the bias (and so counts in
-    log_joint)."""
+    log_joint).
+    ``dof`` (a number nu > 0): the transition is x_{t+1} = m(x_t) + eps with eps ~ t_nu(0, I / precision), as in ``ffbs_weights``; step
+    t's call is ``pairwise_t_argmax`` (no exponential or logarithm per pair either).  The t's normaliser, the same for every pair of a
+    step, is one of the constants left out of log_joint.  d <= 32; not with a per-step precision list."""
     T = len(states)
     if T == 0 or len(loglik_steps) != T or len(means) != T:
         raise ValueError("ffbs_map_path: states, loglik_steps and means must have one entry per step")
+    dof = _ffbs_dof("ffbs_map_path", dof, precision)
     d, K = int(states[0].shape[0]), int(states[0].shape[1])
     table = _ffbs_precision_tables("ffbs_map_path", precision, T, d, K)
     dev = states[0].device
@@ -1121,7 +1191,8 @@ def ffbs_map_path(states, loglik_steps, means, precision, log_prior=None) -> dic
     delta, log_joint = shifted(ll(0) + (torch.zeros(K, dtype=torch.float64, device=dev) if log_prior is None else log_prior.reshape(-1).double()))
     psi = torch.full((T, K), -1, dtype=torch.int32, device=dev)
     if T > 1:
-        ws = torch.empty(load().gjx_pairwise_gauss_argmax_workspace_bytes(K, K, d), dtype=torch.uint8, device=dev)
+        ws_bytes = load().gjx_pairwise_gauss_argmax_workspace_bytes if dof is None else load().gjx_pairwise_t_argmax_workspace_bytes
+        ws = torch.empty(ws_bytes(K, K, d), dtype=torch.uint8, device=dev)
         top = torch.empty(K, dtype=torch.float32, device=dev)
     for t in range(1, T):
         centre = weighted_moments(states[t], loglik_steps[t], "mean")["mean"]
@@ -1129,7 +1200,10 @@ def ffbs_map_path(states, loglik_steps, means, precision, log_prior=None) -> dic
         if table is not None:
             P = table(precision[t - 1])
             delta = delta + 0.5 * torch.log(P.double()).sum(0)
-        pairwise_gauss_argmax(states[t], means[t - 1], delta.float(), P, centre, ws, out=psi[t], max_out=top)
+        if dof is not None:
+            pairwise_t_argmax(states[t], means[t - 1], delta.float(), P, dof, centre, ws, out=psi[t], max_out=top)
+        else:
+            pairwise_gauss_argmax(states[t], means[t - 1], delta.float(), P, centre, ws, out=psi[t], max_out=top)
         delta, shift = shifted(ll(t) + top.double())
         log_joint = log_joint + shift
     idx = torch.empty(T, dtype=torch.int32, device=dev)

@@ -1381,6 +1381,43 @@ int gjx_pairwise_t_mean(const float* q /* f32[d][stride_q] */, int64_t stride_q,
                         const float* bias /* f32[n_k] or NULL */, float precision, float dof, const float* centre /* f32[d] or NULL */,
                         float* mean /* f32[dv][n_q] */, float* lse /* f32[n_q] or NULL */, void* workspace, size_t workspace_bytes,
                         void* stream);
+/* Pairwise Student-t pick and argmax: gjx_pairwise_gauss_pick and gjx_pairwise_gauss_argmax over the score of gjx_pairwise_t_lse,
+ *     s_rc    = bias[c] - 1/2 (nu + d) log(1 + precision |q_r - k_c|^2 / nu)
+ *     pick[r] = the smallest c with  sum_{c' <= c} exp(s_rc') >= u_r sum_c exp(s_rc),   lse[r] = log sum_c exp(s_rc)
+ *     max[r]  = max_c s_rc,   arg[r] = the SMALLEST key index whose score, as the kernel computes it, attains it
+ * the backward-simulation draws (FFBSi) and the Viterbi step (MAP trajectory) of a recorded filter run with t transition noise.
+ *   dof, precision    as in gjx_pairwise_t_lse;  u, pick, lse as in gjx_pairwise_gauss_pick;  arg, max as in gjx_pairwise_gauss_argmax
+ *   everything else   exactly as in gjx_pairwise_gauss_lse (SoA rows, any row stride >= n, d <= GJX_PAIRWISE_MAX_DIM, `centre`)
+ * Edge rules of the pick (gjx_pairwise_gauss_pick's).  A dead key (bias -inf or NaN) is never picked whatever its coordinates hold.  A
+ * poisoned live key (non-finite coordinate, overflowing scaled centred norm, bias +inf): every pick -1, every lse NaN.  A query with
+ * a non-finite coordinate, or a NaN u_r: pick -1 (and for the query lse NaN) for that query alone.  No live key: -1, lse -inf.  u <= 0
+ * is the first key with positive mass, u >= 1 the last.  lse has the bits of gjx_pairwise_t_lse on the same arguments.
+ * Edge rules of the argmax (gjx_pairwise_gauss_argmax's).  No live key: arg -1, max -inf.  A poisoned live key, or a bias of +inf: -1 /
+ * NaN for every query.  A bad query: -1 / NaN for it alone.  Exact ties go to the smallest index at every level.
+ * Device work, pick.  Four plain launches: gjx_pairwise_t_lse's partials; a per-query plan (fold of the splits, the lse, the owning
+ * split; no query term: it is inside the logarithm); the chunk search, the pick kernel's block, double-buffered staging, group
+ * skipping and bookkeeping around the t score (per pair: add, max, add, v_log_f32, fma, then subtract the known total and
+ * v_exp_f32); a per-query finish that walks the recorded 64-key chunk in the VALU with |q - k|^2 computed directly.
+ * Device work, argmax.  Three plain launches and NO transcendental per pair.  With a = (nu + d) / 2 and B the largest live bias,
+ * argmax_c s_rc = argmin_c (1 + x_rc) w_c with x = precision |q - k|^2 / nu and w_c = exp((B - bias_c) / a) >= 1.  A one-block launch
+ * finds B (one number for the call, so that copies of a key produce the same bits in every split); the main kernel computes w_c once
+ * per staged key (dead, tail and poisoned keys: +inf), per pair max(x' + 1, 1) w_c (add, max, multiply; x' off the matrix cores) and
+ * tracks the lane-local (min, index) with strict improvement; the merge, one thread per query, folds the splits with a strict
+ * comparison and takes one logarithm: max = B - a log(min).  The poison travels as gjx_pairwise_gauss_argmax's flag.  The score error
+ * of this form is that of gjx_pairwise_t_lse plus |B - bias_c| 2^-24, which for any key that can win is inside the same bound.
+ * No atomics, every sum and comparison in an order fixed by the shape: bit-reproducible; nothing of size n_q x n_k is stored.
+ * Refusals as gjx_pairwise_t_lse's, with GJX_EINVAL for a NULL u, pick or arg.  Workspaces, no initialisation needed: the pick takes
+ * gjx_pairwise_gauss_pick_workspace_bytes(n_q, n_k, d); the argmax gjx_pairwise_t_argmax_workspace_bytes(n_q, n_k, d) ({min, index} per
+ * query and split, and B; 0 for shapes the call refuses).  Nothing is launched on a refusal. */
+int gjx_pairwise_t_pick(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q, const float* k /* f32[d][stride_k] */,
+                        int64_t stride_k, int64_t n_k, int32_t d, const float* bias /* f32[n_k] or NULL */, float precision, float dof,
+                        const float* centre /* f32[d] or NULL */, const float* u /* f32[n_q] */, int32_t* pick /* i32[n_q] */,
+                        float* lse /* f32[n_q] or NULL */, void* workspace, size_t workspace_bytes, void* stream);
+size_t gjx_pairwise_t_argmax_workspace_bytes(int64_t n_q, int64_t n_k, int32_t d);
+int gjx_pairwise_t_argmax(const float* q /* f32[d][stride_q] */, int64_t stride_q, int64_t n_q, const float* k /* f32[d][stride_k] */,
+                          int64_t stride_k, int64_t n_k, int32_t d, const float* bias /* f32[n_k] or NULL */, float precision, float dof,
+                          const float* centre /* f32[d] or NULL */, int32_t* arg /* i32[n_q] */, float* max /* f32[n_q] or NULL */,
+                          void* workspace, size_t workspace_bytes, void* stream);
 /* the filter kernel generated for a step program (GJX_FILTER_FORM_WIDE) with `tiles_per_block` in {1, 2, 4, 8, 16} (| 256: the flavour
  * that runs on a collection sharded over peer-mapped windows — system-scope accesses and the verify mode decided at run time; | 512: with
  * the rejuvenation move; | 1024, on its own: multinomial resampling by sorted uniforms): its HIP source
